@@ -32,8 +32,6 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before torch / HIP initialise: see llmrec_amd/__init__.py
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -65,6 +63,9 @@ def parse():
     ap.add_argument("--no-end-to-end", action="store_true", help="nf workload: skip the `python main.py` run timed by the drop-in's own epoch timers (tools/e2e_main.py)")
     ap.add_argument("--no-extra-configs", action="store_true", help="default nf line: skip the MovieLens-shaped (cfg 3) and cfg-5 step times measured in fresh processes")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (logged losses, every trained table / weight) as "
+                         "DIR/<name>.npy in float32 (at most 64 MB in all: a seeded row sample of a larger array, with its row ids)")
     return ap.parse_args()
 
 
@@ -174,8 +175,7 @@ class NetflixShaped:
             self.fused = DataParallelStep(self.model, self.graph, self.hp, rates, self.opt, cap, comm=comm)
         else:
             self.fused = FusedStep(self.model, self.graph, self.hp, rates, self.opt, cap)
-        import llmrec_amd
-        self.use_graph = os.environ.get("LLMREC_GRAPH", "1") == "1" and llmrec_amd.graph_replay_safe()
+        self.use_graph = os.environ.get("LLMREC_GRAPH", "1") == "1"
 
     def step(self):
         """One training step. With the HIP graph: sampler + forward + losses + backward + AdamW are ONE graph
@@ -206,8 +206,10 @@ class NetflixShaped:
             if f.graph_exec is None:
                 self._capture(); n -= 1                        # (the capture's warm-up is one of the n steps)
             return f.run_steps(n)
+        out = None
         for _ in range(n):
-            self.step()
+            out = self.step()
+        return out
 
     def step_modular(self):
         """The same step through torch.autograd over the per-op Functions (reference-shaped path)."""
@@ -1159,7 +1161,7 @@ def row_sharded_measure(name, scaling, seed, device, rank, world, steps, barrier
 def variant_step_time(w: "NetflixShaped", steps: int, env: dict, what: dict):
     """The same workload with one switch of llmrec_amd/fused.py flipped, timed in a FRESH process (python bench.py --workload ... with the switch in
     the environment): a second and third FusedStep inside this process share the HIP runtime's hardware queues with the timed one's graph
-    executables, and with GPU_MAX_HW_QUEUES=8 (llmrec_amd/__init__.py) the third one's step measured 2 x slower than the same step alone."""
+    executables, and the third one's step measured 2 x slower than the same step alone."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", w.shape_name, "--steps", str(steps), "--warmup", "20", "--seed", "0", "--no-parity",
            "--no-kernel-roofline", "--no-cpu-baseline", "--no-row-sharded", "--no-end-to-end"]
@@ -1368,6 +1370,51 @@ def write_detail(line: dict):
     return paths
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(w, last) -> dict:
+    """What the timed path hands its caller after its last step: the logged loss terms and every table / weight the step trains, as float32
+    host arrays in a fixed order. The embedding tables ARE the model a training run produces (the evaluation scores them)."""
+    import numpy as np
+    import torch
+    out = {}
+    if last is not None:
+        vals = [last] if isinstance(last, torch.Tensor) else list(last)
+        names = ("loss", "mf", "emb") if len(vals) == 3 else ["out%d" % i for i in range(len(vals))]
+        for n, v in zip(names, vals):
+            out[n] = np.asarray(v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32).reshape(-1)
+    if hasattr(w, "model"):
+        params = list(w.model.named_parameters())
+    else:
+        st = w.step_obj
+        params = [("user_tab", st.user_tab), ("item_tab", st.item_tab)]
+    for n, p in params:
+        out["param." + n] = p.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(path: str, w, last, budget: int = DUMP_BUDGET_BYTES):
+    """--dump-outputs: step_outputs() as <path>/<name>.npy. Arrays that do not fit an equal share of the budget are cut to a seeded sample of
+    their rows (the same rows in every run of the same shape), stored beside them as <name>.rows.npy."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    outs = step_outputs(w, last)
+    os.makedirs(path, exist_ok=True)
+    small = {k: v for k, v in outs.items() if v.nbytes <= 1 << 20}
+    big = [k for k in outs if k not in small]
+    share = (budget - sum(v.nbytes for v in small.values())) // max(1, len(big)) if big else 0
+    for k, v in outs.items():
+        if k in big and v.nbytes > share:
+            n = max(1, share // (v.nbytes // v.shape[0] + 8))  # (+ 8 bytes of row id per kept row)
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=n, replace=False)).astype(np.int64)
+            np.save(os.path.join(path, k + ".rows.npy"), rows)
+            v = v[rows]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def launch_decision(gpus: int, env, n_devices: int):
     """What `python bench.py --gpus N` does before any work, as a pure function of (flag, environment, visible devices):
       ("run", world)      - run in this process as one rank of `world` (world = WORLD_SIZE when a launcher set it, else 1);
@@ -1467,6 +1514,8 @@ def main():
     dflt = {"nf": (200, 20), "ml": (200, 20), "cfg5": (5, 1)}.get(workload, (20, 3))
     a.steps = dflt[0] if a.steps is None else a.steps
     a.warmup = dflt[1] if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if workload in ("nf", "ml"):
         from llmrec_amd import dist as ldist
@@ -1514,11 +1563,12 @@ def main():
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()                                             # HIP events on the stream the step graphs are launched on
+    last = None
     if hasattr(w, "run_steps"):
-        w.run_steps(a.steps)                                 # exactly a.steps steps (graphs of several steps + single-step graphs)
+        last = w.run_steps(a.steps)                          # exactly a.steps steps (graphs of several steps + single-step graphs)
     else:
         for _ in range(a.steps):
-            step()
+            last = step()
     finish()                                                 # inside the timed region: every step's update is applied
     ev1.record()
     torch.cuda.synchronize(); barrier()
@@ -1529,6 +1579,8 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, w, last)
 
     line = {"metric": "bpr_train_edges_per_sec", "value": a.steps * units / dt, "unit": "edges/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "ms_per_step_hip_events": dt_events / a.steps * 1e3,

@@ -163,7 +163,7 @@ class DataParallelStep(FusedStep):
         graphs = []
         for fn in (first, lambda: self.phase_b(*args), self.phase_c, first_with_update):
             g = torch.cuda.CUDAGraph()                         # capturing records, it does not execute: one step ran (the warm-up)
-            with _capture_without_gc(g):                       # (no Python garbage collection inside a stream capture: llmrec_amd/fused.py)
+            with _capture_without_gc(g, self.multi_stream):     # (no Python garbage collection inside a stream capture: llmrec_amd/fused.py)
                 fn()
             graphs.append(g)
         self.graphs = graphs

@@ -46,9 +46,9 @@ class _capture_without_gc:
     memory and destroy executables in the middle of a stream capture. Hygiene, not a fix for anything observed: the host fault round 4
     chased through the GPU suite turned out to be hipGraphLaunch's own (llmrec_amd/__init__.py)."""
 
-    def __init__(self, graph):
+    def __init__(self, graph, multi_branch: bool):
         from . import require_graph_replay
-        require_graph_replay("llmrec_amd: stream capture")      # the hardware-queue work-around must be in force (llmrec_amd/__init__.py)
+        require_graph_replay("llmrec_amd: stream capture", multi_branch)   # single-branch graphs only (llmrec_amd/__init__.py)
         self.ctx = torch.cuda.graph(graph, capture_error_mode="thread_local")   # other threads (the RCCL watchdog) may touch the runtime
 
     def __enter__(self):
@@ -134,9 +134,9 @@ class FusedStep:
         self.ws_wgrad_multi = None                           # sized at the first backward (needs the gradient tensors)
         self._partials = {}
         # Independent chains (7-stream side features / LLM profile / ID embeddings / the two fusion halves / the logged scalars)
-        # run on five HIP streams in forward and in backward; under capture the fork / join become graph edges, so the
-        # latency-bound Netflix-scale SpMMs overlap the GEMMs. LLMREC_STREAMS=0 keeps everything on one stream (debugging).
-        self.multi_stream = os.environ.get("LLMREC_STREAMS", "1") == "1"
+        # can run on five HIP streams in forward and in backward (LLMREC_STREAMS=1), so that the latency-bound Netflix-scale SpMMs overlap
+        # the GEMMs in eager launches. The default is ONE stream: a captured step must be a single-branch graph (llmrec_amd/__init__.py).
+        self.multi_stream = os.environ.get("LLMREC_STREAMS", "0") == "1"
         self.s1, self.s2, self.s3 = (torch.cuda.Stream(device=dev) for _ in range(3))
         for p in model.parameters():
             if p.requires_grad and p.grad is None and p is not model.batch_norm.weight and p is not model.batch_norm.bias:
@@ -928,7 +928,7 @@ class FusedStep:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with _capture_without_gc(g):
+            with _capture_without_gc(g, self.multi_stream):
                 run()
             ev = self._eval_graphs[key] = (g, idx, sc, q, train, ws, sums, sums_ws, held)     # keeps the captured operands alive
         ev[0].replay()
@@ -986,7 +986,7 @@ class FusedStep:
             torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with _capture_without_gc(g):
+        with _capture_without_gc(g, self.multi_stream):
             one_step()
         self.graph_exec = g
         # with the sampler inside the graph nothing host-side separates two steps: run_steps() replays a graph of `unroll` steps (the
@@ -994,7 +994,7 @@ class FusedStep:
         self.graph_multi, self.graph_unroll = None, 0
         if batcher is not None and unroll > 1:
             g2 = torch.cuda.CUDAGraph()
-            with _capture_without_gc(g2):
+            with _capture_without_gc(g2, self.multi_stream):
                 for _ in range(unroll):
                     one_step()
             self.graph_multi, self.graph_unroll = g2, unroll

@@ -23,7 +23,6 @@ from datetime import datetime
 import math
 import os
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before torch / HIP initialise: see llmrec_amd/__init__.py
 import pickle
 import random
 import sys
@@ -53,10 +52,7 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 def USE_GRAPH():
     """LLMREC_GRAPH (default 1): the fused step and the evaluation are replayed from captured HIP graphs; 0 = the same launches
     issued one by one from Python (debugging, and the A/B of the graph itself)."""
-    if os.environ.get("LLMREC_GRAPH", "1") != "1":
-        return False
-    import llmrec_amd
-    return llmrec_amd.graph_replay_safe()                  # False (with a RuntimeWarning at import) when the hardware-queue work-around cannot hold
+    return os.environ.get("LLMREC_GRAPH", "1") == "1"
 
 
 ATTRIBUTE_KEYS = {                                         # reference main.py:69-72

@@ -148,3 +148,31 @@ def test_eight_rank_cfg4_line_is_composed_without_launching():
     assert w["messages"]["allreduce_I_x_d_bytes"] == 4 * 5_000_000 * 128 * 4 and len(w["chunks"]) == 8
     # a world of one rank: nothing to overlap, one chunk
     assert len(bench.row_sharded_plan("cfg4", "strong", 1)["chunks"]) == 1
+
+
+def test_dump_outputs_keeps_the_budget_and_samples_the_same_rows(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, the logged losses whole, a table over its share cut to a seeded row sample stored with its
+    row ids, the same rows in every run, everything within the budget."""
+    import numpy as np
+    import torch
+
+    class W:
+        model = torch.nn.Module()
+    torch.manual_seed(0)
+    W.model.table = torch.nn.Parameter(torch.randn(300000, 8))          # 9.6 MB: over its share of a 4 MB budget
+    W.model.lin = torch.nn.Linear(16, 8)
+    last = (torch.tensor(1.5), torch.tensor(0.25), torch.tensor(1e-3))
+    budget = 4 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), W, last, budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "mf.npy", "emb.npy", "param.table.npy", "param.table.rows.npy", "param.lin.weight.npy", "param.lin.bias.npy"} == set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= budget + 1024 * len(names)      # (+ the .npy headers)
+    rows = np.load(tmp_path / "a" / "param.table.rows.npy")
+    t = np.load(tmp_path / "a" / "param.table.npy")
+    assert t.dtype == np.float32 and t.shape == (rows.size, 8) and np.array_equal(t, W.model.table.detach().numpy()[rows])
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == 1.5
+    assert np.array_equal(np.load(tmp_path / "a" / "param.lin.weight.npy"), W.model.lin.weight.detach().numpy())

@@ -25,7 +25,7 @@ from oracle import make_trajectory as MT
 
 PATHS = {
     # name: environment of the run
-    "fused": {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "0"},
+    "fused": {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "0", "LLMREC_STREAMS": "1"},
     "streams0": {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "0", "LLMREC_STREAMS": "0"},
     "graph": {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1"},
     "device_sampler": {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1"},

@@ -306,47 +306,39 @@ def test_host_helper_library_exports_what_its_header_declares():
         getattr(lib, n)
 
 
-def test_hardware_queue_pool_is_widened_before_hip_initialises():
-    """llmrec_amd/__init__.py (and tests/conftest.py, bench.py, main.py, __graft_entry__.py) set GPU_MAX_HW_QUEUES - the work-around for
-    hipGraphLaunch's unchecked walk over an executable's internal streams - unless the user chose a value."""
-    import llmrec_amd                                             # noqa: F401
-    assert int(os.environ.get("GPU_MAX_HW_QUEUES", "0")) >= 8
-    for f in ("bench.py", "main.py", "__graft_entry__.py", os.path.join("tests", "conftest.py")):
-        src = open(os.path.join(os.path.dirname(_lib.HEADER), "..", f)).read()
-        assert 'os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")' in src, f
-        assert src.index("GPU_MAX_HW_QUEUES") < (src.index("import torch") if "import torch" in src else len(src)), f
+def test_captured_step_is_single_branch_by_default():
+    """hipGraphLaunch of a multi-branch graph can fault on the host, so the fused step runs on ONE stream unless
+    LLMREC_STREAMS=1 asks for more, and every stream capture passes that choice to the refusal below."""
+    import re
+    src = open(os.path.join(os.path.dirname(_lib.HEADER), "..", "llmrec_amd", "fused.py")).read()
+    assert 'self.multi_stream = os.environ.get("LLMREC_STREAMS", "0") == "1"' in src
+    for f in ("fused.py", "dp.py"):
+        src = open(os.path.join(os.path.dirname(_lib.HEADER), "..", "llmrec_amd", f)).read()
+        calls = re.findall(r"with _capture_without_gc\(([^)]*)\)", src)
+        assert calls and all(c.endswith(", self.multi_stream") for c in calls), (f, calls)
+        assert "with torch.cuda.graph(" not in src and ".capture_begin(" not in src, f        # no capture bypasses the check
 
 
-def test_queue_work_around_decision_is_loud():
-    """VERDICT r04 next #8 / ADVICE r04: the work-around only holds if GPU_MAX_HW_QUEUES >= 8 is in the environment before the HIP runtime
-    initialises; when it cannot hold, graph replay is refused (not silently left to fault)."""
+def test_multi_branch_capture_is_refused():
+    """A capture that would record a multi-branch graph is refused loudly (not left to fault at launch); single-branch captures always
+    pass; LLMREC_UNSAFE_GRAPH=1 is the explicit override."""
     import llmrec_amd
-    qd = llmrec_amd.queue_decision
-    assert qd(None, False) == ("set", True, None)                       # the normal import: set it
-    act, safe, msg = qd(None, True)                                      # the embedder touched the GPU first
-    assert (act, safe) == ("keep", False) and "after the HIP runtime initialised" in msg
-    act, safe, msg = qd("4", False)                                      # a smaller user value is kept, and flagged
-    assert (act, safe) == ("keep", False) and "below 8" in msg
-    assert qd("4", True)[1] is False and qd("junk", False)[1] is False
-    assert qd("8", False) == ("keep", True, None) and qd("16", True) == ("keep", True, None)
-    assert llmrec_amd.graph_replay_safe()                                # this process: conftest set it before torch was imported
-    # a process that initialised torch.cuda first would be refused a capture; simulate the module state
-    saved = (llmrec_amd._graph_safe, llmrec_amd._message)
-    llmrec_amd._graph_safe, llmrec_amd._message = False, "simulated"
+    saved = os.environ.pop("LLMREC_UNSAFE_GRAPH", None)
     try:
-        assert not llmrec_amd.graph_replay_safe()
+        llmrec_amd.require_graph_replay("test", False)
+        assert not llmrec_amd.multi_branch_graphs_allowed()
         try:
-            llmrec_amd.require_graph_replay("test")
+            llmrec_amd.require_graph_replay("test", True)
             raise AssertionError("capture was not refused")
         except RuntimeError as e:
-            assert "refused" in str(e)
+            assert "refused" in str(e) and "multi-branch" in str(e)
         os.environ["LLMREC_UNSAFE_GRAPH"] = "1"
-        try:
-            llmrec_amd.require_graph_replay("test")                      # the explicit override
-        finally:
-            del os.environ["LLMREC_UNSAFE_GRAPH"]
+        assert llmrec_amd.multi_branch_graphs_allowed()
+        llmrec_amd.require_graph_replay("test", True)                     # the explicit override
     finally:
-        llmrec_amd._graph_safe, llmrec_amd._message = saved
+        os.environ.pop("LLMREC_UNSAFE_GRAPH", None)
+        if saved is not None:
+            os.environ["LLMREC_UNSAFE_GRAPH"] = saved
 
 
 def test_topk_key_order_is_the_reference_rank_rule():
