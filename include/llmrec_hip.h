@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LLMREC_ABI_VERSION 6
+#define LLMREC_ABI_VERSION 7
 
 enum {
     LLMREC_OK = 0,
@@ -699,6 +699,26 @@ int64_t llmrec_topk_eval_sums_workspace_bytes(int32_t n_query, int32_t n_ks);
 int llmrec_topk_eval_sums(int32_t n_query, const int64_t* query_users, int32_t K, const int32_t* topk_idx, const int32_t* test_rowptr,
                           const int32_t* test_colidx, int32_t n_ks, const int32_t* ks_host, void* workspace, int64_t workspace_bytes,
                           double* out, llmrec_stream_t stream);
+/* Full-rank AUC (reference utility/batch_test.py:38-68,104-108, --test_flag full) without a score leaving the device. For each query
+ * user u:  T = u's train row;  H = u's held-out row (val or test, as for llmrec_topk_eval_sums) taken as a SET - duplicates and ids outside
+ * [0, n_items) do not count;  C = [0, n_items) \ T the candidates;  P = H & C the positives;  N = C \ H the negatives;  s_i = the score
+ * BITS llmrec_scores_f32 gives (u, i) (the exact-fp32 chain the top-K sweep ranks by). Then
+ *     c2_u  = sum over p in P, n in N of (2 [s_p > s_n] + [s_p == s_n])          (integer; float equality: +0.0 == -0.0 is a tie)
+ *     AUC_u = c2_u / (2 |P| |N|)                                                 (double)
+ *     AUC_u = 0 if |P| == 0 or |N| == 0, or if some s_i with i in C is NaN or +-inf (then c2_u is reported as 0)
+ * - what sklearn's roc_auc_score gives over the candidates, and 0 where it raises (utility/metrics.py auc).
+ * Rows of both CSRs ascending (llmrec_csr_build); train may be null (nothing masked). d a multiple of 16, at most 128.
+ * Outputs, each optional: auc_out[n_query] (double), counts_out[n_query][3] = (c2, |P|, |N|) (int64), sum_out[1] = the sum of the
+ * per-user AUCs by a fixed tree (device memory or mapped pinned host memory, as for llmrec_topk_eval_sums; the caller divides by n_query).
+ * Integer counts and fixed-order sums: the results are deterministic. Four launches, capturable; no allocation. */
+int64_t llmrec_score_auc_workspace_bytes(int32_t n_query, int64_t n_items, int32_t d);
+int llmrec_score_auc_f32(int32_t n_query, const int64_t* query_users,
+                         const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
+                         int64_t n_items, int32_t d,
+                         const int32_t* train_rowptr, const int32_t* train_colidx,
+                         const int32_t* held_rowptr, const int32_t* held_colidx,
+                         double* auc_out, int64_t* counts_out, double* sum_out,
+                         void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * R11  on-device BPR sampler             replaces Data.sample (reference

@@ -1333,6 +1333,279 @@ static int launch_topk(const TopkArgs& a, hipStream_t stream) {
     return LLMREC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// FULL-RANK AUC (reference utility/batch_test.py:38-68,104-108 with --test_flag full; the host loop ran roc_auc_score per user over every
+// candidate). Per query user: T = train row, H = held-out row as a SET (ids outside [0, n_items) dropped), C = [0, n_items) \ T,
+// P = H & C, N = C \ H, s_i = the exact-fp32 score of llmrec_scores_f32 (the MFMA chain of the top-K sweep), and
+//     c2 = sum over p in P, n in N of 2 [s_p > s_n] + [s_p == s_n]          (integer)       AUC = c2 / (2 |P| |N|)
+// (0 when |P| or |N| is 0, or when some s_i of C is NaN / +-inf: roc_auc_score raises there and metrics.auc returns 0).
+// The sweep never has to tell positives from negatives: with, for every candidate c and the user's positives,
+//     w(c) = sum over p in P of 2 [s_p > s_c] + [s_p == s_c] = 2 |P| - #{s_p < s_c} - #{s_p <= s_c},
+// the sum of w over ALL of C is c2 + sum over p, p' in P of (2 [s_p > s_p'] + [s_p == s_p']) = c2 + |P|^2 (a pair of distinct positives
+// adds 2 in either order, a positive with itself 1). So a block sweeps its 16 users x the items exactly as score_topk_kernel does (same
+// MFMA, same operand order: the same bits), drops train items with a walk of the sorted train row, and adds w(c) from two binary searches in
+// the user's positive scores, sorted in LDS. w is additive over a partition of P: users with more than AUC_CHUNK positives are swept once
+// per chunk of their (held-row ordered) positives. Every count is an integer - 64-bit atomics combine the waves and the item parts -, and
+// the AUCs are summed by a fixed tree: the result does not depend on the schedule.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int AUC_CHUNK = 256;    // positives per user and pass staged in LDS
+struct AucArgs {
+    int n_query;
+    const int64_t* query_users;
+    const float* Eu; int64_t ldu;
+    const float* Ei; int64_t ldi;
+    int64_t n_items; int d;
+    const int32_t* train_rowptr; const int32_t* train_colidx;   // (null: nothing masked)
+    const int32_t* held_rowptr; const int32_t* held_colidx;
+    int n_parts;                  // blocks per user tile, each a contiguous range of item tiles; block ids part-major
+    int vec_ok;
+    unsigned long long* tot;      // [n_query] sum over C of w(c)
+    unsigned long long* cand;     // [n_query] |C|
+    int32_t* npos;                // [n_query] |P|
+    uint32_t* bad;                // [n_query] != 0: a candidate's score is not finite
+};
+
+// one score by the k-ordered fma chain of v_mfma_f32_16x16x4_f32 (c, then s, then q: k = 16 c + 4 q + s; see tk_finalize_user): the sweep's bits
+__device__ __forceinline__ float auc_chain(const float* ur, const float* ir, int d, bool vec) {
+    float acc = 0.f;
+#pragma unroll 1
+    for (int c = 0; c < d / 16; ++c) {
+        float4 uv[4], iv[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { uv[q] = ld4g(ur, 16 * c + 4 * q, d, vec); iv[q] = ld4g(ir, 16 * c + 4 * q, d, vec); }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(cmp4(uv[q], s), cmp4(iv[q], s), acc);
+    }
+    return acc;
+}
+// #{i < m : p[i] < v} (or_equal: p[i] <= v) in the ascending list p
+__device__ __forceinline__ int auc_rank(const float* p, int lo, int m, float v, bool or_equal) {
+    int hi = m;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float x = p[mid];
+        if (or_equal ? (x <= v) : (x < v)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void auc_clear_kernel(AucArgs a) {
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < a.n_query; q += gridDim.x * 256) {
+        a.tot[q] = 0ull; a.cand[q] = 0ull; a.npos[q] = 0; a.bad[q] = 0u;
+    }
+}
+
+template <int DK>
+__global__ __launch_bounds__(256) void auc_sweep_kernel(AucArgs a) {
+    __shared__ float raw_s[16][AUC_CHUNK];      // this pass's positives of the block's users, in held-row order
+    __shared__ float pos_s[16][AUC_CHUNK];      // ... sorted ascending
+    __shared__ int32_t cnt_s[16];               // entries of pos_s per user in this pass
+    __shared__ int32_t npos_s[16];              // |P| per user
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int li = lane & 15, lq = lane >> 4;
+    const int n_tiles = (a.n_query + 15) / 16;
+    const int tile = (int)(blockIdx.x % n_tiles), part = (int)(blockIdx.x / n_tiles);
+    const int q0 = tile * 16;
+    const bool has_train = a.train_rowptr != nullptr;
+
+    // A operand: the block's 16 users (rows past n_query repeat the last user; their results are dropped)
+    const int qa = q0 + li < a.n_query ? q0 + li : a.n_query - 1;
+    const int64_t user_a = a.query_users[qa];
+    float4 ua[DK];
+#pragma unroll
+    for (int c = 0; c < DK; ++c) ua[c] = ld4g(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
+
+    // this wave's item tiles: a quarter of the part
+    const int64_t tiles_all = (a.n_items + TK_TILE - 1) / TK_TILE;
+    const int64_t p0 = tiles_all * part / a.n_parts, p1 = tiles_all * (part + 1) / a.n_parts;
+    const int64_t per_wave = (p1 - p0 + 3) / 4;
+    const int64_t t_begin = p0 + w * per_wave < p1 ? p0 + w * per_wave : p1;
+    const int64_t t_end = t_begin + per_wave < p1 ? t_begin + per_wave : p1;
+
+    // lanes 0..15: the first train item at or after the wave's first item (user li); the walk restarts there at every pass
+    int32_t cur0 = 0, end = 0;
+    if (lane < 16 && has_train) {
+        int32_t lo = a.train_rowptr[user_a], hi = a.train_rowptr[user_a + 1];
+        end = hi;
+        const int64_t first = t_begin * TK_TILE;
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (a.train_colidx[mid] < first) lo = mid + 1; else hi = mid;
+        }
+        cur0 = lo;
+    }
+
+    unsigned long long tot[4] = {0ull, 0ull, 0ull, 0ull}, cand[4] = {0ull, 0ull, 0ull, 0ull};
+    bool bad[4] = {false, false, false, false};
+    int n_pass = 1;
+    for (int pass = 0; pass < n_pass; ++pass) {                // (block-uniform)
+        // ---- stage: wave w scores the positives [pass * AUC_CHUNK, (pass + 1) * AUC_CHUNK) of users 4 w .. 4 w + 3 ----
+        // P = the held row's distinct in-range ids (rows are ascending: a duplicate follows its first copy) that the train row does not hold
+        const int c_lo = pass * AUC_CHUNK;
+        for (int j = 0; j < 4; ++j) {
+            const int u = 4 * w + j, q = q0 + u;
+            int total = 0;
+            if (q < a.n_query) {                               // wave-uniform
+                const int64_t user = a.query_users[q];
+                const int32_t hb = a.held_rowptr[user], he = a.held_rowptr[user + 1];
+                const int32_t tb = has_train ? a.train_rowptr[user] : 0, te = has_train ? a.train_rowptr[user + 1] : 0;
+                for (int32_t e0 = hb; e0 < he; e0 += 64) {
+                    const int32_t e = e0 + lane;
+                    bool keep = false;
+                    int32_t it = -1;
+                    if (e < he) {
+                        it = a.held_colidx[e];
+                        keep = it >= 0 && (int64_t)it < a.n_items && (e == hb || a.held_colidx[e - 1] != it);
+                        if (keep && has_train) {
+                            int32_t lo = tb, hi = te;
+                            while (lo < hi) {
+                                const int32_t mid = (lo + hi) >> 1;
+                                if (a.train_colidx[mid] < it) lo = mid + 1; else hi = mid;
+                            }
+                            keep = !(lo < te && a.train_colidx[lo] == it);
+                        }
+                    }
+                    const unsigned long long bal = __ballot(keep);
+                    const int idx = total + __popcll(bal & ((1ull << lane) - 1ull));
+                    if (keep && idx >= c_lo && idx < c_lo + AUC_CHUNK)
+                        raw_s[u][idx - c_lo] = auc_chain(a.Eu + user * a.ldu, a.Ei + (int64_t)it * a.ldi, a.d, a.vec_ok);
+                    total += __popcll(bal);
+                }
+            }
+            if (lane == 0) {
+                cnt_s[u] = total - c_lo < 0 ? 0 : (total - c_lo > AUC_CHUNK ? AUC_CHUNK : total - c_lo);
+                npos_s[u] = total;
+            }
+        }
+        __syncthreads();
+        // ---- sort: rank of each entry = #{smaller} + #{equal, earlier} (a permutation for finite scores; a non-finite one voids the user) ----
+        for (int j = 0; j < 4; ++j) {
+            const int u = 4 * w + j, m = cnt_s[u];
+            for (int i = lane; i < m; i += 64) {
+                const float v = raw_s[u][i];
+                int r = 0;
+                for (int k = 0; k < m; ++k) {
+                    const float o = raw_s[u][k];
+                    r += (o < v) || (o == v && k < i);
+                }
+                pos_s[u][r] = v;
+            }
+        }
+        if (pass == 0) {
+            int mx = 0;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) mx = npos_s[u] > mx ? npos_s[u] : mx;
+            n_pass = mx > AUC_CHUNK ? (mx + AUC_CHUNK - 1) / AUC_CHUNK : 1;
+            if (part == 0 && threadIdx.x < 16 && q0 + (int)threadIdx.x < a.n_query) a.npos[q0 + threadIdx.x] = npos_s[threadIdx.x];
+        }
+        __syncthreads();
+
+        // ---- sweep this wave's item tiles ----
+        int32_t cur = cur0, nxt = INT_MAX;
+        if (lane < 16 && cur < end) nxt = a.train_colidx[cur];
+        int mu[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mu[r] = cnt_s[lq * 4 + r];
+        for (int64_t t = t_begin; t < t_end; ++t) {
+            const int64_t base = t * TK_TILE;
+            float4 b[2][DK];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                int64_t item = base + 16 * n + li;
+                if (item > a.n_items - 1) item = a.n_items - 1;
+#pragma unroll
+                for (int c = 0; c < DK; ++c) b[n][c] = ld4g(a.Ei + item * a.ldi, 16 * c + 4 * lq, a.d, a.vec_ok);
+            }
+            f32x4 acc[2];
+            acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
+#pragma unroll
+            for (int c = 0; c < DK; ++c)
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(cmp4(ua[c], s), cmp4(b[n][c], s), acc[n], 0, 0, 0);
+            // the tile's train items of user li (lanes 0..15; rows ascending, the cursor never falls behind the tile)
+            uint32_t m = 0u;
+            while ((int64_t)nxt < base + TK_TILE) {
+                if ((int64_t)nxt >= base) m |= 1u << (int)(nxt - base);
+                ++cur;
+                nxt = cur < end ? a.train_colidx[cur] : INT_MAX;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t rm = (uint32_t)__shfl((int)m, lq * 4 + r, 64);
+                const int u = lq * 4 + r;
+                const bool row_ok = q0 + u < a.n_query;
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const int col = 16 * n + li;
+                    if (!row_ok || base + col >= a.n_items || ((rm >> col) & 1u)) continue;
+                    const float v = acc[n][r];
+                    if (pass == 0) { cand[r] += 1ull; bad[r] = bad[r] || !__builtin_isfinite(v); }
+                    if (mu[r] > 0) {
+                        const int lt = auc_rank(pos_s[u], 0, mu[r], v, false);
+                        const int le = auc_rank(pos_s[u], lt, mu[r], v, true);
+                        tot[r] += (unsigned long long)(2 * mu[r] - lt - le);
+                    }
+                }
+            }
+        }
+        __syncthreads();                                       // (the stage is rebuilt by the next pass)
+    }
+    // ---- the 16 lanes of a row -> one atomic per (wave, user) ----
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        unsigned long long t_ = tot[r], c_ = cand[r];
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) { t_ += __shfl_xor(t_, off, 64); c_ += __shfl_xor(c_, off, 64); }
+        const unsigned long long anybad = __ballot(bad[r]);
+        const int q = q0 + lq * 4 + r;
+        if (li == 0 && q < a.n_query) {
+            if (t_) atomicAdd(&a.tot[q], t_);
+            if (c_) atomicAdd(&a.cand[q], c_);
+            if ((anybad >> (lq * 16)) & 0xffffull) atomicOr(&a.bad[q], 1u);
+        }
+    }
+}
+
+// per-user AUC (double; optional outputs) and the block's fixed-tree sum -> partial[block] (topk_eval_sums_finish_kernel adds the blocks)
+__global__ __launch_bounds__(ES_THREADS) void auc_finish_kernel(AucArgs a, double* __restrict__ auc_out, int64_t* __restrict__ counts_out,
+                                                                double* __restrict__ partial) {
+    __shared__ double red[ES_THREADS];
+    const int q = blockIdx.x * ES_THREADS + threadIdx.x;
+    double v = 0.0;
+    if (q < a.n_query) {
+        const unsigned long long P = (unsigned long long)a.npos[q], C = a.cand[q], N = C - P;
+        const bool bad = a.bad[q] != 0u;
+        const unsigned long long c2 = bad ? 0ull : a.tot[q] - P * P;
+        if (!bad && P > 0ull && N > 0ull) v = (double)c2 / (2.0 * (double)P * (double)N);
+        if (auc_out) auc_out[q] = v;
+        if (counts_out) { counts_out[3 * (int64_t)q] = (int64_t)c2; counts_out[3 * (int64_t)q + 1] = (int64_t)P; counts_out[3 * (int64_t)q + 2] = (int64_t)N; }
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = ES_THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// item parts of the AUC sweep: at least two blocks per CU, and tables beyond the L2 in parts of 16 384 items (part-major block ids: the blocks
+// resident at one time share a part through the L2, as the bf16 top-K sweep's parts do); every wave keeps >= 16 rounds
+static int auc_plan_parts(int n_query, int64_t n_items) {
+    const int64_t n_tiles = ceil_div(n_query, 16), item_tiles = ceil_div(n_items, TK_TILE);
+    int64_t parts = ceil_div(2 * device_cus(), n_tiles);
+    if (n_items > TK_PARTS_FROM_ITEMS && ceil_div(n_items, 16384) > parts) parts = ceil_div(n_items, 16384);
+    const int64_t most = item_tiles / 64 > 1 ? item_tiles / 64 : 1;
+    if (parts > most) parts = most;
+    while (parts > 1 && n_tiles * parts > 0x7fffffffll) --parts;
+    return (int)(parts > 0 ? parts : 1);
+}
+
 }  // namespace llmrec
 
 using namespace llmrec;
@@ -1525,6 +1798,80 @@ int llmrec_topk_metrics(int32_t n_query, const int64_t* query_users, int32_t K, 
     for (int i = 0; i < n_ks; ++i) { LLMREC_CHECK_ARG(ks_host[i] > 0, "topk_metrics: cut-offs must be positive"); ks.k[i] = ks_host[i]; }
     topk_metrics_kernel<<<(int)ceil_div(n_query, 128), 128, 0, (hipStream_t)stream_>>>(n_query, query_users, K, hits, topk_idx, test_rowptr, ks, out);
     LLMREC_LAUNCH_CHECK();
+    return LLMREC_OK;
+}
+
+static int64_t auc_ws_parts(int32_t n_query, int64_t* off) {   // byte offsets of tot, cand, npos, bad, partial; returns the total
+    const int64_t n = n_query > 0 ? n_query : 1;
+    off[0] = 0;
+    off[1] = off[0] + align_up(8 * n, 256);
+    off[2] = off[1] + align_up(8 * n, 256);
+    off[3] = off[2] + align_up(4 * n, 256);
+    off[4] = off[3] + align_up(4 * n, 256);
+    return off[4] + align_up(8 * ceil_div(n, ES_THREADS), 256);
+}
+
+int64_t llmrec_score_auc_workspace_bytes(int32_t n_query, int64_t n_items, int32_t d) {
+    if (n_query < 0 || n_items <= 0 || d <= 0) return -1;
+    int64_t off[5];
+    return auc_ws_parts(n_query, off);
+}
+
+int llmrec_score_auc_f32(int32_t n_query, const int64_t* query_users,
+                         const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
+                         int64_t n_items, int32_t d,
+                         const int32_t* train_rowptr, const int32_t* train_colidx,
+                         const int32_t* held_rowptr, const int32_t* held_colidx,
+                         double* auc_out, int64_t* counts_out, double* sum_out,
+                         void* workspace, int64_t workspace_bytes, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(n_query >= 0 && n_items > 0 && d > 0, "score_auc: bad sizes");
+    LLMREC_CHECK_ARG(d % 16 == 0 && d <= 128, "score_auc: d = %d must be a multiple of 16, at most 128", d);
+    LLMREC_CHECK_ARG(n_items < (1ll << 31), "score_auc: n_items exceeds int32 item ids");
+    LLMREC_CHECK_ARG((train_rowptr == nullptr) == (train_colidx == nullptr), "score_auc: train CSR incomplete");
+    LLMREC_CHECK_ARG(n_query == 0 || (query_users && Eu && Ei && held_rowptr && held_colidx), "score_auc: null pointer");
+    LLMREC_CHECK_ARG(ldu >= d && ldi >= d, "score_auc: ld < d");
+    const int64_t need = llmrec_score_auc_workspace_bytes(n_query, n_items, d);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 16 != 0) {
+        set_error("score_auc: workspace of %lld bytes needed (16-byte aligned), got %lld", (long long)need, (long long)workspace_bytes);
+        return LLMREC_EWORKSPACE;
+    }
+    if (n_query == 0 && !sum_out) return LLMREC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    int64_t off[5];
+    auc_ws_parts(n_query, off);
+    char* ws = (char*)workspace;
+    AucArgs a;
+    a.n_query = n_query; a.query_users = query_users; a.Eu = Eu; a.ldu = ldu; a.Ei = Ei; a.ldi = ldi;
+    a.n_items = n_items; a.d = d; a.train_rowptr = train_rowptr; a.train_colidx = train_colidx;
+    a.held_rowptr = held_rowptr; a.held_colidx = held_colidx;
+    a.vec_ok = (ldu % 4 == 0) && (ldi % 4 == 0) && (((uintptr_t)Eu | (uintptr_t)Ei) % 16 == 0);
+    a.tot = (unsigned long long*)(ws + off[0]); a.cand = (unsigned long long*)(ws + off[1]);
+    a.npos = (int32_t*)(ws + off[2]); a.bad = (uint32_t*)(ws + off[3]);
+    double* partial = (double*)(ws + off[4]);
+    const int n_blocks = (int)ceil_div(n_query, ES_THREADS);
+    if (n_query > 0) {
+        a.n_parts = auc_plan_parts(n_query, n_items);
+        const int grid = (int)(ceil_div(n_query, 16) * a.n_parts);
+        auc_clear_kernel<<<grid_for(n_query, 256), 256, 0, stream>>>(a);
+        LLMREC_LAUNCH_CHECK();
+        switch (d / 16) {
+            case 1: auc_sweep_kernel<1><<<grid, 256, 0, stream>>>(a); break;
+            case 2: auc_sweep_kernel<2><<<grid, 256, 0, stream>>>(a); break;
+            case 3: auc_sweep_kernel<3><<<grid, 256, 0, stream>>>(a); break;
+            case 4: auc_sweep_kernel<4><<<grid, 256, 0, stream>>>(a); break;
+            case 5: auc_sweep_kernel<5><<<grid, 256, 0, stream>>>(a); break;
+            case 6: auc_sweep_kernel<6><<<grid, 256, 0, stream>>>(a); break;
+            case 7: auc_sweep_kernel<7><<<grid, 256, 0, stream>>>(a); break;
+            default: auc_sweep_kernel<8><<<grid, 256, 0, stream>>>(a); break;
+        }
+        LLMREC_LAUNCH_CHECK();
+        auc_finish_kernel<<<n_blocks, ES_THREADS, 0, stream>>>(a, auc_out, counts_out, partial);
+        LLMREC_LAUNCH_CHECK();
+    }
+    if (sum_out) {
+        topk_eval_sums_finish_kernel<<<1, 256, 0, stream>>>(n_blocks, 1, partial, sum_out);
+        LLMREC_LAUNCH_CHECK();
+    }
     return LLMREC_OK;
 }
 

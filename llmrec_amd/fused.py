@@ -880,19 +880,24 @@ class FusedStep:
         """Nothing is deferred in the single-graph step (DataParallelStep defers its AdamW)."""
 
     # -- evaluation -------------------------------------------------------------------------------
-    def eval_topk(self, query_users: torch.Tensor, train: Optional[ops.Csr], K: int, use_graph: bool = False, held=None, Ks=None):
+    def eval_topk(self, query_users: torch.Tensor, train: Optional[ops.Csr], K: int, use_graph: bool = False, held=None, Ks=None,
+                  auc: bool = False):
         """Reference Trainer.test up to the ranked lists (main.py:297-303, batch_test.py:83-109): no-grad forward +
         scoring + masked top-K for the listed users -> (idx int32 [n, K], scores). With use_graph the whole
         evaluation (~40 launches) is one HIP graph per (query set, K), replayed at every epoch end.
         held = (rowptr, colidx) of the held-out CSR + Ks (use_graph only): the evaluation also ends with llmrec_topk_eval_sums - hits, per-user
         precision / recall / ndcg / hit-ratio and their sums over the users, two launches at the graph's tail writing the 4 x len(Ks)
         doubles into PINNED host memory (self.eval_sums(...) after a stream synchronisation; batch_test.py:160-165 divided by the
-        number of users) - nothing per user leaves the device and no copy follows the replay."""
+        number of users) - nothing per user leaves the device and no copy follows the replay.
+        auc=True (with held, use_graph only; --test_flag full): the graph also ends with llmrec_score_auc_f32 - the full-rank AUC of every
+        listed user against the same held-out rows, summed by a fixed tree into one pinned double (self.eval_auc_sum())."""
+        if auc and (not use_graph or held is None):
+            raise RuntimeError("FusedStep.eval_topk: auc=True needs use_graph=True and the held-out rows")
         if not use_graph:
             self.forward()
             return ops.score_topk(self.E_u, self.E_i, query_users, train, K)
         Ks = tuple(int(k) for k in Ks) if held is not None else None
-        key = (query_users.data_ptr(), query_users.numel(), K, id(train), None if held is None else (held[0].data_ptr(), Ks))
+        key = (query_users.data_ptr(), query_users.numel(), K, id(train), None if held is None else (held[0].data_ptr(), Ks), bool(auc))
         ev = self._eval_graphs.get(key)
         if ev is None:
             q = query_users.to(torch.int64).contiguous()
@@ -904,6 +909,10 @@ class FusedStep:
             if held is not None:
                 sums = torch.zeros(4, len(Ks), dtype=torch.float64).pin_memory()
                 sums_ws = torch.empty(_lib.query("llmrec_topk_eval_sums_workspace_bytes", n, len(Ks)), dtype=torch.uint8, device=q.device)
+            auc_sum = auc_ws = None
+            if auc:
+                auc_sum = torch.zeros(1, dtype=torch.float64).pin_memory()
+                auc_ws = ops.auc_workspace(n, self.I, q.device, self.d)
 
             def run():
                 # the evaluation's graph has TWO branches (the ID chain beside the projection; the profile chain stays on the main stream):
@@ -921,6 +930,10 @@ class FusedStep:
                       K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, ops.topk_mode(None, self.I, self.d, K))
                 if held is not None:
                     ops.topk_eval_sums(idx, q, held[0], held[1], Ks, out=sums, ws=sums_ws)
+                if auc:
+                    _call("llmrec_score_auc_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
+                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+                          _p(held[0]), _p(held[1]), None, None, _c.c_void_p(auc_sum.data_ptr()), _p(auc_ws), auc_ws.numel())
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -930,7 +943,7 @@ class FusedStep:
             g = torch.cuda.CUDAGraph()
             with _capture_without_gc(g, self.multi_stream):
                 run()
-            ev = self._eval_graphs[key] = (g, idx, sc, q, train, ws, sums, sums_ws, held)     # keeps the captured operands alive
+            ev = self._eval_graphs[key] = (g, idx, sc, q, train, ws, sums, sums_ws, held, auc_sum, auc_ws)     # keeps the captured operands alive
         ev[0].replay()
         self._last_eval = ev
         return ev[1], ev[2]
@@ -942,6 +955,14 @@ class FusedStep:
             raise RuntimeError("FusedStep.eval_sums: the last evaluation was not captured with a held-out set")
         torch.cuda.current_stream().synchronize()
         return ev[6]
+
+    def eval_auc_sum(self):
+        """The pinned float64 [1] sum of the per-user AUCs of the LAST eval_topk(..., auc=True) replay; synchronises the current stream first."""
+        ev = getattr(self, "_last_eval", None)
+        if ev is None or ev[9] is None:
+            raise RuntimeError("FusedStep.eval_auc_sum: the last evaluation was not captured with auc=True")
+        torch.cuda.current_stream().synchronize()
+        return ev[9]
 
     def drop_eval_graph(self, query_users: torch.Tensor):
         """Release every captured evaluation (graph, result lists, top-K workspace) of this query tensor."""

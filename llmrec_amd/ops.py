@@ -1135,6 +1135,41 @@ def topk_eval_sums(idx: torch.Tensor, query_users: torch.Tensor, test_rowptr: to
     return out
 
 
+def _rows(csr):
+    """(rowptr, colidx) of an ops.Csr or of a (rowptr, colidx) pair."""
+    return (csr.rowptr, csr.colidx) if hasattr(csr, "rowptr") else (csr[0], csr[1])
+
+
+def auc_workspace(n_query: int, n_items: int, device, d: int = 64) -> torch.Tensor:
+    """Scratch for llmrec_score_auc_f32 (per-user integer counts and the partial sums; independent of the held-out rows)."""
+    return torch.empty(_lib.query("llmrec_score_auc_workspace_bytes", n_query, n_items, d), dtype=torch.uint8, device=device)
+
+
+def score_auc(Eu, Ei, query_users: torch.Tensor, train, held, counts: bool = False, out: Optional[torch.Tensor] = None,
+              ws: Optional[torch.Tensor] = None):
+    """Full-rank AUC per query user on the device (llmrec_score_auc_f32; the contract is in include/llmrec_hip.h): float64 [n], and with
+    counts=True also int64 [n, 3] = (c2, |P|, |N|). train / held: ops.Csr or (rowptr, colidx) (train may be None). out: a float64 tensor of
+    one element - device or PINNED host memory - that receives the sum of the per-user AUCs (fixed-order tree; a pinned one is valid after
+    a stream synchronisation)."""
+    _need_gpu(Eu, Ei, query_users)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    hr, hc = _rows(held)
+    tr, tc = _rows(train) if train is not None else (None, None)
+    _need_gpu(hr, hc, tr, tc)
+    if out is not None and (out.dtype != torch.float64 or out.numel() < 1):
+        raise RuntimeError("score_auc: out must be a float64 tensor of one element")
+    need = _lib.query("llmrec_score_auc_workspace_bytes", n, I, d)
+    if ws is None or ws.numel() < need:
+        ws = auc_workspace(n, I, Eu.device, d)
+    auc = torch.empty(n, dtype=torch.float64, device=Eu.device)
+    cnt = torch.empty(n, 3, dtype=torch.int64, device=Eu.device) if counts else None
+    _lib.call("llmrec_score_auc_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d, _p(tr), _p(tc), _p(hr), _p(hc),
+              _p(auc), _p(cnt), _c.c_void_p(out.data_ptr()) if out is not None else None, _p(ws), ws.numel(), _stream())
+    return (auc, cnt) if counts else auc
+
+
 def sample_bpr(seed: int, step: int, exist_users: torch.Tensor, n_items: int, train: Csr, B: int):
     dev = exist_users.device
     u = torch.empty(B, dtype=torch.int64, device=dev)

@@ -69,6 +69,30 @@ def _progress(it):
         return it
 
 
+def test_full_on_device(ua_embeddings, ia_embeddings, users_to_test, is_val, topk=None):
+    """--test_flag full (reference utility/batch_test.py:38-68,104-108) without test_torch's host loop over score blocks: the ranking
+    metrics exactly as the 'part' evaluation computes them (masked top-K, hits and per-user metrics on the device), and the full-rank AUC of
+    every user by llmrec_score_auc_f32 - integer pair counts on the device, summed by a fixed tree into one pinned double. No score block
+    leaves the device and sklearn is not needed. topk: optional (query tensor, ranked lists) already computed for exactly users_to_test."""
+    from llmrec_amd import ops
+    result = {'precision': np.zeros(len(Ks)), 'recall': np.zeros(len(Ks)), 'ndcg': np.zeros(len(Ks)),
+              'hit_ratio': np.zeros(len(Ks)), 'auc': 0.}
+    n = len(users_to_test)
+    if n == 0:
+        return result
+    st = data_generator.device_state(ua_embeddings.device)
+    q, idx = topk if topk is not None else topk_lists(ua_embeddings, ia_embeddings, list(users_to_test))
+    rp, ci = st["val"] if is_val else st["test"]
+    sums = ops.topk_metrics(idx, ops.topk_hits(idx, q, rp, ci), q, rp, Ks).sum(0).cpu().numpy() / n
+    for j, k in enumerate(('precision', 'recall', 'ndcg', 'hit_ratio')):
+        result[k] = sums[j]
+    auc_sum = torch.zeros(1, dtype=torch.float64).pin_memory()
+    ops.score_auc(ua_embeddings, ia_embeddings, q, st["train"], (rp, ci), out=auc_sum)
+    torch.cuda.current_stream().synchronize()
+    result['auc'] = float(auc_sum[0]) / n
+    return result
+
+
 class Trainer(object):
     def __init__(self, data_config):
         self.task_name = "%s_%s_%s" % (datetime.now().strftime('%Y-%m-%d %H:%M:%S'), args.dataset, args.cf_model,)
@@ -179,7 +203,7 @@ class Trainer(object):
             self.model_mm.eval()
         fused = self._fused_step()
         with torch.no_grad():
-            if fused and args.test_flag == 'part':
+            if fused:
                 # forward + scoring + masked top-K as ONE graph replay per evaluation (LLMREC_EVAL_GRAPH=0: the same launches issued eagerly).
                 # Round 6, full Netflix-shaped dataset, tools/eval_probe.py, ms per evaluation [20 back to back | one at a time, host
                 # synchronised behind each, as this method runs]: graph with the forward's three side branches 0.73 - 0.76 | 0.595; graph with
@@ -209,17 +233,20 @@ class Trainer(object):
                 if USE_GRAPH() and os.environ.get("LLMREC_EVAL_GRAPH", "1") == "1":
                     # ONE graph replay: forward, scoring, masked top-K AND the metrics (llmrec_topk_eval_sums: hits, per-user values and their
                     # sums, the twelve doubles written into pinned host memory by the graph's last launch): no launch, no copy behind it
-                    fused.eval_topk(q, st["train"], max(Ks_), use_graph=True, held=st["val"] if is_val else st["test"], Ks=Ks_)
+                    # (--test_flag full: the same graph also ends with the full-rank AUC sweep, llmrec_score_auc_f32, and its sum)
+                    full = args.test_flag != 'part'
+                    fused.eval_topk(q, st["train"], max(Ks_), use_graph=True, held=st["val"] if is_val else st["test"], Ks=Ks_, auc=full)
                     sums = fused.eval_sums().numpy() / len(users_to_test)
-                    return {'precision': sums[0].copy(), 'recall': sums[1].copy(), 'ndcg': sums[2].copy(), 'hit_ratio': sums[3].copy(), 'auc': 0.}
+                    auc = float(fused.eval_auc_sum()[0]) / len(users_to_test) if full else 0.
+                    return {'precision': sums[0].copy(), 'recall': sums[1].copy(), 'ndcg': sums[2].copy(), 'hit_ratio': sums[3].copy(), 'auc': auc}
                 idx, _ = fused.eval_topk(q, st["train"], max(Ks_), use_graph=False)
+                if args.test_flag != 'part':
+                    return test_full_on_device(fused.E_u, fused.E_i, users_to_test, is_val, topk=(q, idx))
                 return test_torch(fused.E_u, fused.E_i, users_to_test, is_val, topk=(q, idx))
-            if fused:                                          # same forward, ~40 launches over preallocated buffers
-                fused.forward()
-                ua_embeddings, ia_embeddings = fused.E_u, fused.E_i
-            else:
-                ua_embeddings, ia_embeddings, *rest = self.model_mm(self.ui_graph, self.iu_graph, self.image_ui_graph,
-                                                                    self.image_iu_graph, self.text_ui_graph, self.text_iu_graph)
+            ua_embeddings, ia_embeddings, *rest = self.model_mm(self.ui_graph, self.iu_graph, self.image_ui_graph,
+                                                                self.image_iu_graph, self.text_ui_graph, self.text_iu_graph)
+        if args.test_flag != 'part':
+            return test_full_on_device(ua_embeddings, ia_embeddings, users_to_test, is_val)
         return test_torch(ua_embeddings, ia_embeddings, users_to_test, is_val)
 
     # -- one step ---------------------------------------------------------------------------------
