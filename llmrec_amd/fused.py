@@ -73,6 +73,12 @@ class _capture_without_gc:
 
 
 class FusedStep:
+    # resident blocks the weight-gradient launch is laid out for (llmrec_wgrad_target_t.block_budget; 0 = 256, one per CU). A block of
+    # that launch owns its CU's whole register file, so a 256-block round starves whatever runs beside it: the ID chain's last SpMM took
+    # 81 us beside it and 12 us alone and, once the row list had shortened the GEMM, had become the step's tail. 224 blocks leave 32 CUs
+    # to the other streams: 256 / 240 / 224 / 208 / 192 blocks -> 0.474 / 0.459 / 0.454 / 0.456 / 0.469 ms per step on one box.
+    wgrad_blocks = 224
+
     def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
         or any object with .ui/.iu SparseOperands; rates: (model_cat, user_cat, item_cat)."""
@@ -189,11 +195,6 @@ class FusedStep:
         # and so does user_trans (its gradient is two hops wide: 66 % of the rows).
         self.wgrad_rows = (getattr(type(self), "WGRAD_ROWS", True) and os.environ.get("LLMREC_WGRAD_ROWS", "1") == "1" and self.preprop
                            and len(self.keys) > 0 and self.gemm == "bf16x3")     # (the exact-fp32 launches ignore the list: do not build it)
-        # resident blocks the weight-gradient launch is laid out for (llmrec_wgrad_target_t.block_budget; 0 = 256, one per CU). A block of
-        # that launch owns its CU's whole register file, so a 256-block round starves whatever runs beside it: the ID chain's last SpMM took
-        # 81 us beside it and 12 us alone and, once the row list had shortened the GEMM, had become the step's tail. 224 blocks leave 32 CUs
-        # to the other streams: 256 / 240 / 224 / 208 / 192 blocks -> 0.474 / 0.459 / 0.454 / 0.456 / 0.469 ms per step on one box.
-        self.wgrad_blocks = int(os.environ.get("LLMREC_WGRAD_BLOCKS", "224"))
         if self.wgrad_rows:
             self.act_flags = torch.zeros(U + 16, dtype=torch.uint8, device=dev)[:U]   # all-zero between calls (readable in 16-byte words)
             self.act_rows = torch.zeros(U + 32, dtype=torch.int32, device=dev)
@@ -282,8 +283,6 @@ class FusedStep:
                 partials = self._partials[key] = torch.empty(pl.n_seg * d, dtype=torch.float32, device=X.device)
         if accumulate:
             epilogue = ops.spmm_epilogue(ops.EPI_NONE, 1.0, Y)
-        if epilogue is None and os.environ.get("LLMREC_SPMM_PIPELINE", "1") == "0":      # (A/B switch: one task per lane group)
-            epilogue = ops.spmm_epilogue()
         rp, ci = pl.csr_of(a)
         _call("llmrec_spmm_f32", a.n_rows, a.n_cols, _p(rp), _p(ci), _p(a.val), _p(a.row_scale), _p(a.col_scale),
               _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),
@@ -323,12 +322,9 @@ class FusedStep:
                 ([(self._side(dY_cat, 1), feats[1], roww)], m.text_trans.weight.grad, m.text_trans.bias.grad, False),
                 ([(self._side(dY_cat, 0), feats[0], roww)], m.image_trans.weight.grad, m.image_trans.bias.grad, False)]
 
-    def _project_all(self, which: str = "all"):
-        """All 8 projections in one grouped launch (d <= 64), else one by one. which = "user" / "items": only user_trans' projection /
-        only the seven item-side ones (LLMREC_SPLIT_PROJ: two launches, so that the profile chain can start behind the first)."""
+    def _project_all(self):
+        """All 8 projections in one grouped launch (d <= 64), else one by one."""
         jobs = self.projection_jobs()
-        if which != "all":
-            jobs = [j for j in jobs if (j[2] is self.P_usr) == (which == "user")]
         if self.d > 64 or len(jobs) > _lib.CONST["LLMREC_LINEAR_MAX_PROBLEMS"]:
             if self.preprop:
                 raise RuntimeError("FusedStep: the pre-propagated projection needs the grouped launch (d <= 64); set LLMREC_PREPROPAGATE=0")
@@ -374,17 +370,13 @@ class FusedStep:
         return (_c.c_float * len(r))(*r)
 
     # -- forward ----------------------------------------------------------------------------------
-    def forward(self, sampler=None, after_chain=None, before_fusion=None):
+    def forward(self, sampler=None, after_chain=None, profile_on_main: bool = False):
         """sampler / after_chain: launches for the ID chain's stream, ahead of / behind its SpMMs (the batch and what is derived from it);
-        before_fusion: called behind the join of the side chains, ahead of the fusion launch."""
+        profile_on_main: the profile chain stays on the current stream (the evaluation's graph, see eval_topk)."""
         m, d = self.m, self.d
         self._fork(self.s2)
-        # LLMREC_ID_FIRST=1 (experiment, profiles/experiments/r05_step_chain.md): the ID chain's SpMMs BEFORE the sampler and the row list on
-        # this stream - behind them (one-block kernels that wait 50 - 100 us for a CU beside the projection) the chain ended as late as
-        # the two other chains the fusion joins
-        id_first = os.environ.get("LLMREC_ID_FIRST", "0") == "1"
         with self._on(self.s2):                                          # ID chain: needs no projection
-            if sampler is not None and self.multi_stream and not id_first:   # the batch is first read by the losses, after the join below:
+            if sampler is not None:                                      # the batch is first read by the losses, after the join below:
                 sampler()                                                # sampling rides beside the projection instead of ahead of it
             if self._zero_in_forward and not self.fold:
                 self.opt.advance()                                       # AdamW's step counter / bias corrections, off the critical path
@@ -399,49 +391,33 @@ class FusedStep:
                     self._spmm(self.ui.fwd, i_prev, self.Ul[l], tag=2)
                     self._spmm(self.iu.fwd, self.Ul[l], self.Il[l], tag=2)
                 i_prev = self.Il[l]
-            if sampler is not None and self.multi_stream and id_first:
-                sampler()
-            self._ev_chain = self._mark() if after_chain is not None else None   # the chain's SpMMs are done; what follows on this stream
-            if after_chain is not None:                                          # is not needed by the fusion
+            ev_chain = self._mark() if after_chain is not None else None     # the chain's SpMMs are done; what follows on this stream
+            if after_chain is not None:                                      # is not needed by the fusion
                 after_chain()
         self._stamp(1)
-        split_proj = os.environ.get("LLMREC_SPLIT_PROJ", "0") == "1" and self.multi_stream and self.d <= 64
-        if split_proj:                                                   # user_trans first: the profile chain runs BESIDE the item-side projection
-            self._project_all("user")                                    # and is long done when the fusion joins it (no late second parent)
-            ev1 = self._mark()
-            self._fork_from(ev1, self.s1)
-            with self._on(self.s1):
-                self._spmm(self.iu.fwd, self.P_usr, self.prof_i, tag=1)
-                self._spmm(self.ui.fwd, self.prof_i, self.prof_u, tag=1)
-            self._project_all("items")
-        else:
-            self._project_all()
+        self._project_all()
         self._stamp(2)
-        if not split_proj:
-            ev1 = self._mark()
+        ev1 = self._mark()
         if not self.preprop:
             self._spmm(self.ui.fwd, self.P_cat, self.U_cat)              # 7 streams, one adjacency pass
         self._spmm(self.iu.fwd, self.U_cat, self.I_cat)
-        if not split_proj:
-            if getattr(self, "profile_on_main", False):                  # (evaluation graphs: two branches instead of three, see eval_topk)
+        if profile_on_main:
+            self._spmm(self.iu.fwd, self.P_usr, self.prof_i, tag=1)
+            self._spmm(self.ui.fwd, self.prof_i, self.prof_u, tag=1)
+        else:
+            self._fork_from(ev1, self.s1)
+            with self._on(self.s1):                                      # profile stream: items first
                 self._spmm(self.iu.fwd, self.P_usr, self.prof_i, tag=1)
                 self._spmm(self.ui.fwd, self.prof_i, self.prof_u, tag=1)
-            else:
-                self._fork_from(ev1, self.s1)
-                with self._on(self.s1):                                  # profile stream: items first
-                    self._spmm(self.iu.fwd, self.P_usr, self.prof_i, tag=1)
-                    self._spmm(self.ui.fwd, self.prof_i, self.prof_u, tag=1)
         if self._zero_in_forward and not self.fold:                      # training: the feature regulariser's value needs only U_cat / I_cat -
             self._fork(self.s3)                                          # captured HERE it runs beside the fusion and the BPR launches (captured
             with self._on(self.s3):                                      # after the BPR backward, round 2, the graph ran it last: the step's tail)
                 self._feat_reg()
-        if getattr(self, "_ev_chain", None) is not None and self.multi_stream:
+        if ev_chain is not None:
             self._join(self.s1)
-            torch.cuda.current_stream().wait_event(self._ev_chain)               # (not the stream's tail: after_chain's launches are joined later)
+            torch.cuda.current_stream().wait_event(ev_chain)                     # (not the stream's tail: after_chain's launches are joined later)
         else:
             self._join(self.s1, self.s2)
-        if before_fusion is not None:
-            before_fusion()
 
         # E_u and E_i (Models.py:185-197) in ONE launch: llmrec_fuse_fwd_multi_f32 (two independent row ranges)
         keep = []
@@ -488,30 +464,6 @@ class FusedStep:
             arr[i].g_mf, arr[i].g_emb = self.w_mf[i], self.w_emb[i]
         return arr
 
-    def _bpr_launches(self, users, pos, neg, n_valid, lo: int = 0, hi: Optional[int] = None):
-        """scores -> selection -> backward rows of the problems [lo, hi) (all: the step's three loss launches). The launch that contains
-        problem 0 begins the step (row stamp, AdamW's counter) and stamps the batch's rows."""
-        hp, B = self.hp, users.numel()
-        hi = self.n_prob if hi is None else hi
-        full = self._problems()
-        n = hi - lo
-        probs = full if (lo == 0 and hi == self.n_prob) else (ops.BprProblem * n)(*[full[i] for i in range(lo, hi)])
-        saved = self.saved if lo == 0 else self.saved[lo * ops.bpr_saved_floats(B):]
-        remember = float(1 - hp.prune_loss_drop_rate)
-        first = lo == 0
-        if self.fold and first:                                          # the scores launch begins the step: row stamp + AdamW's counter
-            o = self.opt
-            if o.dev_state is None:
-                o.dev_state = torch.zeros(3, dtype=torch.float32, device=self.E_u.device)
-            _call("llmrec_bpr_multi_scores_step_f32", n, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(saved),
-                  _p(self.row_stamp), _p(o.dev_state), o.lr, o.betas[0], o.betas[1])
-        else:
-            _call("llmrec_bpr_multi_scores_f32", n, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(saved),
-                  _p(self.row_stamp) if first else None)
-        _call("llmrec_bpr_multi_select_bwd_f32", n, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), remember,
-              float(hp.decay), float(hp.batch_size), _p(saved), _p(self.flag_u) if first else None, _p(self.flag_i) if first else None,
-              _p(self.row_stamp), _p(self.bpr_plan))
-
     def loss_backward(self, users, pos, neg, n_valid=None):
         B = users.numel()
         if B > self.b_max:
@@ -522,14 +474,20 @@ class FusedStep:
         # critical path: scores -> [selection + gradient rows] (two launches); the loss VALUES (one more launch) and their assembly for
         # the log line ride on the ID chain's stream (a branch of their own right behind the BPR launches: the graph ran it as the step's tail)
         self._check_scatter_targets()
-        if getattr(self, "_ev_plan", None) is not None:                  # (LLMREC_PLAN_STREAM=late: the plan was built behind the ID chain)
+        if getattr(self, "_ev_plan", None) is not None:                  # (four streams: the plan was built behind the ID chain)
             torch.cuda.current_stream().wait_event(self._ev_plan)
-        if getattr(self, "_bpr_split_done", False):                      # (LLMREC_BPR_SPLIT: problems 1.. were launched beside the fusion)
-            self._bpr_launches(users, pos, neg, n_valid, lo=0, hi=1)
-            self._join(self.s1)
-            self._bpr_split_done = False
+        # the scores launch begins the step (row stamp; folded: AdamW's counter too), the selection stamps the batch's rows
+        if self.fold:
+            o = self.opt
+            if o.dev_state is None:
+                o.dev_state = torch.zeros(3, dtype=torch.float32, device=self.E_u.device)
+            _call("llmrec_bpr_multi_scores_step_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved),
+                  _p(self.row_stamp), _p(o.dev_state), o.lr, o.betas[0], o.betas[1])
         else:
-            self._bpr_launches(users, pos, neg, n_valid)
+            _call("llmrec_bpr_multi_scores_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved),
+                  _p(self.row_stamp))
+        _call("llmrec_bpr_multi_select_bwd_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), remember,
+              float(hp.decay), float(hp.batch_size), _p(self.saved), _p(self.flag_u), _p(self.flag_i), _p(self.row_stamp), _p(self.bpr_plan))
 
         def side():                              # (runs on the ID chain's stream, _backward places it)
             if self.fold:                        # loss values + regulariser (the fusion launch's partial sums) + assembly: one launch
@@ -566,12 +524,11 @@ class FusedStep:
             if dirty:
                 raise RuntimeError("FusedStep: scatter targets not all-zero before the loss backward: %s (an aborted step? call reset_scatter_targets())" % dirty)
 
-    def _backward(self, probs, users, pos, neg, n_valid, replicated_scale: float = 1.0, after_first=None, bpr_bwd_done: bool = False,
-                  side_work=None):
+    def _backward(self, probs, users, pos, neg, n_valid, replicated_scale: float = 1.0, bpr_bwd_done: bool = False, side_work=None):
         """Hand-written backward from the saved BPR state to the parameter gradients (and, with inline_adamw, the update).
         replicated_scale weights the batch-independent loss terms (1 / world on batch-sharded replicas, whose
         gradients are summed over ranks afterwards). bpr_bwd_done: the loss launch already scattered the gradient rows.
-        after_first: side work captured right after the BPR backward; side_work: launches for the ID chain's stream, ahead of its last SpMM."""
+        side_work: launches for the ID chain's stream, ahead of its last SpMM."""
         hp, d, L, S = self.hp, self.d, self.L, self.S
         B = users.numel()
         coef = hp.feat_reg_decay * 0.5 / self.I * replicated_scale
@@ -580,8 +537,6 @@ class FusedStep:
             _call("llmrec_bpr_multi_bwd_f32", self.n_prob, probs, d, _p(users), _p(pos), _p(neg), B, _p(n_valid), float(hp.decay),
                   float(hp.batch_size), _p(self.saved), _p(self.bpr_plan))
         ev_rows = self._mark()                                           # dE_u / dE_i hold the scattered rows: all the ID chain needs
-        if after_first is not None:
-            after_first()
 
         # the backward of both fusions in ONE launch (llmrec_fuse_bwd_src_multi_f32)
         keep = []
@@ -612,10 +567,10 @@ class FusedStep:
         ev_fuse = self._mark()                                           # the fusion backward has read dE_u / dE_i
         m = self.m
         inv = 1.0 / (L + 1)
-        # capture order at this fork (experiment knobs, profiles/experiments/r05_step_chain.md): LLMREC_BWD_MAIN_FIRST=1 captures the critical
-        # transposed side product BEFORE the two side branches; LLMREC_LOSS_STREAM=s3 puts the logged-scalar launch on its own stream
-        main_first = os.environ.get("LLMREC_BWD_MAIN_FIRST", "1" if self.fold else "0") == "1" and self.multi_stream
-        loss_s3 = os.environ.get("LLMREC_LOSS_STREAM", "s3" if self.fold else "s2") == "s3" and self.multi_stream and side_work is not None
+        # four streams, folded step: the critical transposed side product is captured BEFORE the two side branches and the logged-scalar
+        # launch gets a stream of its own (each alone lost, both together won: profiles/experiments/r05_step_chain.md)
+        main_first = self.multi_stream and self.fold
+        loss_s3 = self.multi_stream and self.fold and side_work is not None
         if main_first:
             self._spmm(self.iu.bwd, self.dI_cat, self.dU_cat, accumulate=True)
             if not self.preprop:
@@ -706,29 +661,16 @@ class FusedStep:
             # per step, one launch 0.637 ms). user_trans' gradient is in the same launch since round 3: with the pre-propagated
             # operands nothing separates the two launches in time any more, and side by side each ran at half speed (the chip is
             # power-bound here: profiles/experiments/r03_wgrad.md). The bias gradients (row-weighted when pre-propagated) come out of it too.
-            split_wgrad = os.environ.get("LLMREC_SPLIT_WGRAD", "0") == "1" and self.multi_stream and self.inline_adamw
-            if not split_wgrad:
-                self._join(self.s1)                                      # dP_usr (the profile chain is long done by now)
+            self._join(self.s1)                                          # dP_usr (the profile chain is long done by now)
             if self.ws_wgrad_multi is None:
                 need = ops.linear_wgrad_multi_workspace(targets, self.wgrad_blocks)
                 self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=dY_cat.device) if need >= 0 else False
             if self.ws_wgrad_multi is not False:
                 self._stamp(3)
-                if getattr(self, "_ev_reach", None) is not None:                 # (LLMREC_REACH_LATE: the row list was built behind the ID chain)
+                if getattr(self, "_ev_reach", None) is not None:                 # (four streams: the row list was built behind the ID chain)
                     torch.cuda.current_stream().wait_event(self._ev_reach)
                 lins = (m.item_trans, m.user_trans, m.text_trans, m.image_trans)              # (wgrad_targets' order)
-                if split_wgrad:
-                    # the three item-side Linears first - their only late parent is the transposed side product on THIS stream - then,
-                    # behind the join with the profile chain, user_trans' own launch (two GEMM + two reduction launches instead of one + one)
-                    sel = [0, 2, 3]
-                    ops.linear_wgrad_multi([targets[i] for i in sel], self.ws_wgrad_multi, update=(self.opt, [(lins[i].weight, lins[i].bias) for i in sel]),
-                                           block_budget=self.wgrad_blocks)
-                    self._join(self.s1)
-                    if getattr(self, "ws_wgrad_user", None) is None:
-                        self.ws_wgrad_user = torch.empty(max(ops.linear_wgrad_multi_workspace(targets[1:2], self.wgrad_blocks), 16), dtype=torch.uint8, device=dY_cat.device)
-                    ops.linear_wgrad_multi(targets[1:2], self.ws_wgrad_user, update=(self.opt, [(lins[1].weight, lins[1].bias)]), block_budget=self.wgrad_blocks)
-                    updated = [p_ for l in lins for p_ in (l.weight, l.bias)]
-                elif self.inline_adamw:                                  # the four Linears' AdamW rides in the slab-reduction launch
+                if self.inline_adamw:                                  # the four Linears' AdamW rides in the slab-reduction launch
                     ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, update=(self.opt, [(l.weight, l.bias) for l in lins]), block_budget=self.wgrad_blocks)
                     updated = [p_ for l in lins for p_ in (l.weight, l.bias)]
                 else:
@@ -756,11 +698,11 @@ class FusedStep:
         if loss_s3:
             self._join(self.s3)
 
-    def _train_forward(self, sampler=None, after_chain=None, before_fusion=None):
+    def _train_forward(self, sampler=None, after_chain=None):
         """forward() of a training step: also advances AdamW's counters (and samples the batch) on a side stream."""
         self._zero_in_forward = True
         try:
-            self.forward(sampler, after_chain, before_fusion)
+            self.forward(sampler, after_chain)
         finally:
             self._zero_in_forward = False
 
@@ -781,59 +723,30 @@ class FusedStep:
     def step_eager(self, users, pos, neg, n_valid=None, sampler=None):
         """sampler: optional callable that fills (users, pos, neg, n_valid) on the current stream first (inside the same
         graph when captured; running it on a side stream beside the forward measured no faster)."""
-        side = self.multi_stream                                 # the sampler rides beside the projection (forward())
-        # (Built on the regulariser's stream instead - forked from the main stream, waiting for the sampler's event of the ID chain's stream,
-        #  its own event awaited by the weight gradient - hipGraphInstantiate of this image recursed until the stack ran out: not kept.)
-        # The scatter plan of the loss backward (needed ~200 us later) and the row list (needed by the weight gradient only, at the far end of
-        # the step) ride on the ID chain's stream BEHIND its SpMMs; the fusion waits for the chain's event (self._ev_chain), the loss launches
-        # for the plan's (self._ev_plan), the weight gradient for the list's (self._ev_reach). Measured on one box, 300 steps each, twice
-        # (round 6, profiles/experiments/r06_step_chain.md): both right behind the sampler, ahead of the SpMMs (LLMREC_PLAN_STREAM=early
-        # LLMREC_REACH_LATE=0, the state until then) 0.4539 / 0.4539 ms per step; here 0.4470 / 0.4481. With the plan behind the chain but the
-        # fusion joining the whole stream (the first form of "late") 0.460 / 0.461; the plan on a branch of its own forked from the sampler
-        # 0.534 / 0.534 - the graph runtime then runs the PROJECTION behind the ID chain (not kept).
-        fill = sampler
-        plan_late = self.multi_stream and os.environ.get("LLMREC_PLAN_STREAM", "late") == "late"
-        reach_late = self.multi_stream and self.wgrad_rows and os.environ.get("LLMREC_REACH_LATE", "1") == "1"
-        self._ev_reach = None
+        self._ev_plan = self._ev_reach = None
 
-        def reach():
-            ops.batch_reach_rows(users, pos, neg, n_valid, self.iu.fwd, self.act_flags, self.act_rows, self.act_n)
-
-        def sampler():
-            if fill is not None:
-                fill()
-            if not plan_late:
-                self.build_scatter_plan(users, pos, neg, n_valid)
-            if self.wgrad_rows and not reach_late:
-                reach()
-
-        self._ev_plan = None
-
-        def late_work():
-            if plan_late:
-                self.build_scatter_plan(users, pos, neg, n_valid)
-                self._ev_plan = self._mark()                             # (the loss launches wait for this event, the fusion only for the chain's)
-            if reach_late:
-                reach()
+        def batch_lists():
+            # the scatter plan of the loss backward and the weight gradient's row list. On four streams they ride on the ID chain's stream
+            # BEHIND its SpMMs (the plan is needed ~200 us later, the list at the far end of the step): the fusion waits for the chain's
+            # event, the loss launches for the plan's (self._ev_plan), the weight gradient for the list's (self._ev_reach). Round 6, one
+            # box, 300 steps twice: 0.4539 / 0.4539 ms per step with both ahead of the SpMMs, 0.4470 / 0.4481 behind them
+            # (profiles/experiments/r06_step_chain.md).
+            self.build_scatter_plan(users, pos, neg, n_valid)
+            self._ev_plan = self._mark()
+            if self.wgrad_rows:
+                ops.batch_reach_rows(users, pos, neg, n_valid, self.iu.fwd, self.act_flags, self.act_rows, self.act_n)
                 self._ev_reach = self._mark()
-        late = late_work if (plan_late or reach_late) else None
         self.spmm_edge_units = 0.0
         calls0 = _lib.n_calls
         try:
             self._stamp(0)
-            if sampler is not None and not side:
-                sampler()
-            # LLMREC_BPR_SPLIT=1 (experiment, profiles/experiments/r06_step_chain.md): the seven side problems' loss launches (their tables are
-            # complete BEFORE the fusion) on the profile stream beside the fusion; only problem 0 (E_u / E_i) stays on the critical path
-            split = (os.environ.get("LLMREC_BPR_SPLIT", "0") == "1" and self.fold and self.multi_stream and self.n_prob > 1)
-            self._bpr_split_done = False
-
-            def side_problems():
-                self._fork_from(self._mark(), self.s1)
-                with self._on(self.s1):
-                    self._bpr_launches(users, pos, neg, n_valid, lo=1)
-                self._bpr_split_done = True
-            self._train_forward(sampler if side else None, late, side_problems if split else None)
+            if self.multi_stream:                                # the sampler rides beside the projection (forward())
+                self._train_forward(sampler, batch_lists)
+            else:
+                if sampler is not None:
+                    sampler()
+                batch_lists()
+                self._train_forward()
             self.loss_backward(users, pos, neg, n_valid)
             if not self.inline_adamw:
                 self.opt.step(advanced=True)
@@ -918,13 +831,7 @@ class FusedStep:
                 # the evaluation's graph has TWO branches (the ID chain beside the projection; the profile chain stays on the main stream):
                 # 0.572 ms per replay back to back / 0.599 one at a time, against 0.73 - 0.76 / 0.595 with the training forward's three
                 # side branches - successive launches of a many-branch graph pay for their cross-queue joins (tools/eval_probe.py, round 6)
-                branches, ms = os.environ.get("LLMREC_EVAL_BRANCHES", "2"), self.multi_stream
-                self.profile_on_main = branches == "2"
-                self.multi_stream = ms and branches != "1"
-                try:
-                    self.forward()
-                finally:
-                    self.profile_on_main, self.multi_stream = False, ms
+                self.forward(profile_on_main=True)
                 _call("llmrec_score_topk_mode_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
                       _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
                       K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, ops.topk_mode(None, self.I, self.d, K))

@@ -162,16 +162,14 @@ class SpmmPlan:
 
     @staticmethod
     def build(rowptr: torch.Tensor, t_wave: int = 128, t_block: int = 2048, segment: int = 2048, colidx: Optional[torch.Tensor] = None,
-              order_rows: Optional[bool] = None) -> "SpmmPlan":
+              order_rows: bool = True) -> "SpmmPlan":
         """colidx (pattern-only operands) + order_rows: the plan carries a PERMUTED copy of the CSR - every bucket's rows stored in the order
-        they are visited, by descending length class (by_length_class). order_rows None = on (LLMREC_SPMM_ORDER=0: the operand's own CSR in
-        row order). Measured (profiles/experiments/r06_spmm_order.md): 2 M x 1 M x 40 M edges, d = 64: 1.65 -> 1.39 ms (rows = users),
-        1.14 -> 0.99 ms (rows = items); cfg 4 whole 57.2 -> 53.5 ms per step; the Netflix-shaped step 0.460 -> 0.447 ms. Results never
+        they are visited, by descending length class (by_length_class); order_rows=False: the operand's own CSR in row order. Measured
+        (profiles/experiments/r06_spmm_order.md): 2 M x 1 M x 40 M edges, d = 64: 1.65 -> 1.39 ms (rows = users), 1.14 -> 0.99 ms
+        (rows = items); cfg 4 whole 57.2 -> 53.5 ms per step; the Netflix-shaped step 0.460 -> 0.447 ms. Results never
         depend on the order (bit-identical: tests/test_gpu_ops.py)."""
         n_rows = rowptr.numel() - 1
         dev = rowptr.device
-        if order_rows is None:
-            order_rows = os.environ.get("LLMREC_SPMM_ORDER", "1") != "0"
         order_rows = bool(order_rows) and colidx is not None and n_rows > 0
         scratch = torch.zeros(4, dtype=torch.int32, device=dev)
         counts = (_c.c_int32 * 4)()
@@ -362,7 +360,7 @@ def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tens
                   post_scale: Optional[torch.Tensor] = None, x_row_mask: Optional[torch.Tensor] = None, x_mask_active: int = 0,
                   y_row_flag: Optional[torch.Tensor] = None, z_row_flag: Optional[torch.Tensor] = None,
                   y_row_gate: Optional[torch.Tensor] = None, y_row_needed: Optional[torch.Tensor] = None, rows_listed_only: bool = False,
-                  x_nt_from_row: int = 0, xcd_contiguous: bool = False, no_pipeline: Optional[bool] = None):
+                  x_nt_from_row: int = 0, xcd_contiguous: bool = False, no_pipeline: bool = False):
     """llmrec_spmm_epilogue_t: Y = post_scale . op(alpha * Z + A X); S = forward softmax rows for EPI_SOFTMAX_BWD.
     x_row_mask (uint8 [n_cols]) / x_mask_active: X rows whose byte differs from the active value are promised all-zero and not read;
     y_row_flag (uint8 [n_rows]): receives the active value for rows whose result can be non-zero (z_row_flag: the non-zero rows of Z);
@@ -382,7 +380,7 @@ def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tens
                          y_row_gate.data_ptr() if y_row_gate is not None else None,
                          y_row_needed.data_ptr() if y_row_needed is not None else None, 1 if rows_listed_only else 0, int(x_nt_from_row),
                          1 if xcd_contiguous else 0,
-                         1 if (no_pipeline if no_pipeline is not None else os.environ.get("LLMREC_SPMM_PIPELINE", "1") == "0") else 0)
+                         1 if no_pipeline else 0)
 
 
 def listed_plan(a: Csr, rows: torch.Tensor, d: int, whole_row: bool = False) -> SpmmPlan:
@@ -482,8 +480,6 @@ def spmm_raw(a: Csr, X: torch.Tensor, out: Optional[torch.Tensor] = None, accumu
             Xs = cache[key] = torch.empty(X.shape, dtype=torch.float32, device=X.device)
         _lib.call("llmrec_scale_rows_f32", X.shape[0], d, _p(col_scale), _p(X), _ld(X), _p(Xs), _ld(Xs), _stream())
         X, col_scale = Xs, None
-    if epilogue is None and os.environ.get("LLMREC_SPMM_PIPELINE", "1") == "0":          # (A/B switch: one task per lane group)
-        epilogue = spmm_epilogue()
     rp, ci = pl.csr_of(a)
     _lib.call("llmrec_spmm_f32", a.n_rows, a.n_cols, _p(rp), _p(ci), _p(a.val), _p(a.row_scale),
               _p(col_scale), _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),

@@ -206,9 +206,8 @@ class Trainer(object):
             if fused:
                 # forward + scoring + masked top-K as ONE graph replay per evaluation (LLMREC_EVAL_GRAPH=0: the same launches issued eagerly).
                 # Round 6, full Netflix-shaped dataset, tools/eval_probe.py, ms per evaluation [20 back to back | one at a time, host
-                # synchronised behind each, as this method runs]: graph with the forward's three side branches 0.73 - 0.76 | 0.595; graph with
-                # two branches (profile chain on the main stream: FusedStep.eval_topk's choice) 0.572 | 0.599; one-stream graph 0.601 | 0.620;
-                # eager 0.558 | 0.664 - issued onto an idle GPU the ~40 launches leave the host ~70 us behind the device.
+                # synchronised behind each, as this method runs]: one-stream graph 0.601 | 0.620; eager 0.558 | 0.664 - issued onto an idle
+                # GPU the ~40 launches leave the host ~70 us behind the device (graphs on four streams: FusedStep.eval_topk).
                 # the query tensor is cached on the CONTENT of the user list (a different list of the same length
                 # must not reuse it); the evaluation graph is keyed on that tensor
                 own = getattr(self, "_eval_own", None)          # the list train() itself built once and hands in every epoch: trusted by identity
