@@ -1,6 +1,7 @@
 """bench.py - the driver's measurement contract for the LLMRec Stage-2 hot path on MI355X.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --full ...                           # + every side measurement and check (the legs listed below)
     python bench.py --gpus N ...                         # no launcher in the environment: bench.py re-executes itself as N ranks, or refuses
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
@@ -14,14 +15,16 @@ side features (512/768/1536-d, 5 attribute keys), batch 1024 + 10 % augmented tr
 metric value = BPR train edges/s = steps * batch_size / time (the reference's own timer
 definition, main.py:200,297); the full-rank eval rate (users/s, main.py:297-303) is reported in
 "eval", `python main.py` itself timed by its own epoch timers in "end_to_end". Inputs are resident in HBM
-before the timed region. Beside `value`: the oracle parity gate (run before the timed region), `roofline` of
-the dominant kernel with PMC traffic, `cpu_baseline` (the oracle port live + the unmodified reference's record),
-`spmm_roofline`, the cfg-4-shaped `row_sharded` lines.
+before the timed region. A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line
+(with "eval": the evaluation leg runs ahead of the warm-up in every run, see main()). With --full the line also carries,
+beside `value`: the oracle parity gate (its GPU side runs before the timed region), `roofline` of the dominant kernel with
+PMC traffic, `cpu_baseline` (the oracle port live + the unmodified reference's record), `spmm_roofline`, `exact_f32`,
+`end_to_end`, `ml` / `cfg5`, the cfg-4-shaped `row_sharded` lines.
 
 N > 1 (one process per GPU, RCCL): BASELINE.json configs[3] - the user-ROW-sharded ID path (llmrec_amd/dist_fused.py:
 per layer and direction one I x d exchange) on the 10 M x 1 M x 200 M-edge graph, STRONG scaling, with rank 0's
 single-GPU run of the same workload, the row-restricted-forward variant and the Netflix workload as batch-sharded
-replicas (llmrec_amd/dp.py) in the same line. --workload nf|ml|cfg4|cfg5 selects one explicitly.
+replicas (llmrec_amd/dp.py) in the same line (--full). --workload nf|ml|cfg4|cfg5 selects one explicitly.
 One JSON line on rank 0.
 """
 from __future__ import annotations
@@ -62,6 +65,9 @@ def parse():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity gate that runs before the timed region")
     ap.add_argument("--no-end-to-end", action="store_true", help="nf workload: skip the `python main.py` run timed by the drop-in's own epoch timers (tools/e2e_main.py)")
     ap.add_argument("--no-extra-configs", action="store_true", help="default nf line: skip the MovieLens-shaped (cfg 3) and cfg-5 step times measured in fresh processes")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement and check (parity gate, kernel rooflines, CPU "
+                                                        "baseline, end to end, other configurations and precisions, row-sharded lines); "
+                                                        "the --no-* switches above then skip single ones")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (logged losses, every trained table / weight) as "
@@ -806,7 +812,9 @@ class ParityGate:
     timed path and one evaluation, every compared tensor cloned on the device - and compare() runs the CPU oracle against those snapshots
     AFTER it, so the timed region does not begin behind ~10 s of host-only work."""
 
-    def __init__(self, w: "NetflixShaped", n_eval_users: int = 256, steps: int = 2, tol: float = 1e-4):
+    STEPS = 2                                                  # training steps the gate checks (the first ones of the timed path)
+
+    def __init__(self, w: "NetflixShaped", n_eval_users: int = 256, steps: int = STEPS, tol: float = 1e-4):
         self.w, self.n_eval_users, self.steps, self.tol = w, n_eval_users, steps, tol
         self.snap, self.init, self.eval_snap = [], None, None
 
@@ -1516,6 +1524,8 @@ def main():
     a.warmup = dflt[1] if a.warmup is None else a.warmup
     if a.steps < 1 or a.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:                                           # a plain run: no side leg (the evaluation leg stays: see below)
+        a.no_kernel_roofline = a.no_cpu_baseline = a.no_end_to_end = a.no_extra_configs = a.no_row_sharded = True
 
     if workload in ("nf", "ml"):
         from llmrec_amd import dist as ldist
@@ -1539,11 +1549,18 @@ def main():
     # timed steps -> everything else, the CPU phases (the oracle's side of the parity gate, cpu_baseline) LAST. Round 5 ran the gate's ~10 s
     # of host-only oracle work right before the warm-up: with W = 5 the timed region began inside the power-management transient of the
     # first ~12 ms of load and read 6 % above the steady state. Nothing here adds warm-up steps: the legs ahead of the warm-up are
-    # measurements the line reports (`eval`, `roofline.frac_isolated`).
+    # measurements the line reports (`eval`, `roofline.frac_isolated`). Without --full the gate's training steps run without the gate and the
+    # evaluation leg stays: the warm-up and the timed steps are then the same steps, from the same state and behind the same load, as in a
+    # --full run (without the evaluation leg the 20-step bracket at --warmup 5 read 1 % slower: 0.648 against 0.642 ms, eight alternating
+    # runs each on one box; leaving out the isolated-kernel legs changed nothing).
     gate, parity, eval_read, pre_kernels = None, None, None, None
     single_nf = workload in ("nf", "ml") and world == 1 and os.environ.get("LLMREC_FORCE_DP", "0") != "1"
     if single_nf and not a.no_parity:
-        gate = ParityGate(w).capture()
+        if a.full:
+            gate = ParityGate(w).capture()
+        else:
+            for _ in range(ParityGate.STEPS):
+                w.step()
     if single_nf:
         if w.step_id == 0:
             w.step()                                         # (no gate: the legs below read the gradient buffers of a training step)
@@ -1737,7 +1754,7 @@ def main():
         ex = w.extras(dt / a.steps * 1e3)                    # (collective inside: every rank calls it)
         if rank == 0:
             line.update(ex)
-            if world == 1 and not a.no_parity:
+            if world == 1 and a.full and not a.no_parity:
                 line["parity"] = w.sampled_row_parity()
             if not a.no_kernel_roofline:
                 sp = w.spmm_times_ms()                       # rank 0's local products (no collective inside)
@@ -1752,7 +1769,7 @@ def main():
                                             "the measured ceiling of that access pattern (7.3 - 7.8 TB/s, profiles/r02_gatherbench_v2.txt; DESIGN.md 4)"}
                 if world == 1:
                     line["eval_sample"] = w.eval_sample()
-    if workload not in ("nf", "ml") and world > 1 and auto:
+    if workload not in ("nf", "ml") and world > 1 and auto and a.full:
         import gc
         del w, step
         gc.collect(); torch.cuda.empty_cache()
