@@ -210,6 +210,24 @@ int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
                     const llmrec_spmm_plan_t* plan_host, float* partials,
                     const llmrec_spmm_epilogue_t* epilogue_host /* NULL = none */, llmrec_stream_t stream);
 
+/* Independent products in ONE launch (the latency-bound step: each product alone leaves most CUs idle). Each llmrec_spmm_problem_t carries
+ * exactly the arguments of one llmrec_spmm_f32 call and is checked like one; the problems' blocks follow each other in the given order
+ * (longest first keeps the tail short), and problems with split rows share one finalize launch after the main one. Every row keeps its
+ * summation tree: results are bit-identical to separate calls. n = 1 is llmrec_spmm_f32. Returns LLMREC_EUNSUPPORTED (nothing launched)
+ * if the problems do not all resolve to the same kernel instance (width class, vector loads, weighted, masked, cache policy) - the caller
+ * then issues separate calls - and LLMREC_EINVAL if the output (Y or partials) of one problem overlaps X, Y, Z, S or the partials of
+ * another. Empty problems (n_rows = 0 or d = 0) are skipped. */
+#define LLMREC_SPMM_MAX_PROBLEMS 4
+typedef struct {
+    int64_t n_rows, n_cols;
+    const int32_t* rowptr; const int32_t* colidx; const float* val;
+    const float* row_scale; const float* col_scale;
+    const float* X; int64_t ldx; float* Y; int64_t ldy; int32_t d; int32_t slice_width;
+    const llmrec_spmm_plan_t* plan; float* partials;
+    const llmrec_spmm_epilogue_t* epilogue;      /* NULL = none */
+} llmrec_spmm_problem_t;
+int llmrec_spmm_multi_f32(int32_t n, const llmrec_spmm_problem_t* problems, llmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * R4  side-feature projection            replaces nn.Linear forward / weight-grad
  *                                        (reference Models.py:30-37,145-150; aten::addmm, aten::mm)

@@ -89,8 +89,10 @@ _TRACE = os.environ.get("LLMREC_TRACE_CALLS", "0") == "1"
 n_calls = 0      # entry-point invocations so far (FusedStep reports the per-step delta: a launch-count proxy without a profiler)
 
 
-def call(name: str, *args):
-    """Invoke an int-returning entry point; raise on a non-zero status."""
+EUNSUPPORTED = -4       # LLMREC_EUNSUPPORTED (include/llmrec_hip.h): the arguments are valid but outside what the library compiled
+
+
+def _invoke(name: str, args) -> int:
     global n_calls
     n_calls += 1
     lib = load()
@@ -103,9 +105,30 @@ def call(name: str, *args):
             torch.cuda.synchronize()
     else:
         status = getattr(lib, name)(*args)
+    return status
+
+
+def _raise(name: str, status: int):
+    lib = load()
+    raise RuntimeError("%s failed: %s (%s)" % (
+        name, lib.llmrec_status_string(status).decode(), lib.llmrec_last_error().decode()))
+
+
+def call(name: str, *args):
+    """Invoke an int-returning entry point; raise on a non-zero status."""
+    status = _invoke(name, args)
     if status != 0:
-        raise RuntimeError("%s failed: %s (%s)" % (
-            name, lib.llmrec_status_string(status).decode(), lib.llmrec_last_error().decode()))
+        _raise(name, status)
+
+
+def call_unless_unsupported(name: str, *args) -> bool:
+    """call(), except that LLMREC_EUNSUPPORTED (nothing was launched) returns False: the caller then takes another path."""
+    status = _invoke(name, args)
+    if status == EUNSUPPORTED:
+        return False
+    if status != 0:
+        _raise(name, status)
+    return True
 
 
 def query(name: str, *args) -> int:

@@ -122,7 +122,10 @@ struct SpmmArgs {
     const int32_t* seg_split;
     float* partials;             // [slice][segment][d]
     int32_t n_wave_rows, n_block_rows, n_split_rows, n_segments, segment;
-    int32_t blk_seg, blk_block, blk_wave;     // first block of the block-row / wave-row / short-row ranges
+    // block ranges of the launch (global block ids: a grouped launch, llmrec_spmm_multi_f32, gives each problem a range of its own):
+    // [blk_begin, blk_seg) segments of the split rows, [blk_seg, blk_block) block rows, [blk_block, blk_wave) wave rows,
+    // [blk_wave, blk_end) short rows
+    int32_t blk_begin, blk_seg, blk_block, blk_wave, blk_end;
 };
 
 // Accumulate sum_{j in [s, e)} w_j * X[col_j, chunk columns] into acc, in ascending j order. MASKED: rows of X that are not active
@@ -552,16 +555,13 @@ __device__ __forceinline__ int32_t xcd_range_logical(int32_t b, int32_t base, in
     return off + ((b - base - ((x - r0) & 7)) >> 3);
 }
 
-// ONE launch: [0, blk_seg) segments of the split rows, [blk_seg, blk_block) block rows, [blk_block, blk_wave) wave
-// rows (8 per block), the rest short rows. The heavy blocks come first.
+// One problem's block b (a global block id) of the ranges of SpmmArgs: the heavy blocks come first. The segment partials are indexed by
+// the problem-local block id, so a grouped launch addresses them exactly like a launch of its own.
 template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
-__global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
-    constexpr int ROWW = NCHUNK * LPR * VEC;
-    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
-    const int32_t b = blockIdx.x;
+__device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* red_lds) {
     if (b >= a.blk_wave) {
-        const int64_t lb = a.xcd ? (int64_t)xcd_range_logical(b, a.blk_wave, (int32_t)gridDim.x - a.blk_wave) : (int64_t)b - a.blk_wave;
-        if (!MASKED && !NT && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)gridDim.x - a.blk_wave);     // (block-uniform)
+        const int64_t lb = a.xcd ? (int64_t)xcd_range_logical(b, a.blk_wave, a.blk_end - a.blk_wave) : (int64_t)b - a.blk_wave;
+        if (!MASKED && !NT && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)a.blk_end - a.blk_wave);     // (block-uniform)
         else rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, lb);
         return;
     }
@@ -579,7 +579,8 @@ __global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
         }
         return;
     }
-    const int32_t slice = b / a.n_segments, seg = b - slice * a.n_segments;
+    const int32_t lb = b - a.blk_begin;
+    const int32_t slice = lb / a.n_segments, seg = lb - slice * a.n_segments;
     slot = a.seg_split[seg];
     crow = a.split_rows[slot];
     row = a.slot_row ? a.slot_row[crow] : crow;
@@ -590,7 +591,7 @@ __global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
     const int32_t e = min(s + a.segment, re);
     if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, s, e, red_lds, acc)) {
         if (MASKED && col0 == 0 && k_in_row == 0 && threadIdx.x == 0 && a.y_flag) a.y_flag[row] = (uint8_t)a.x_active;   // conservative
-        float* pr = a.partials + (int64_t)b * a.d;
+        float* pr = a.partials + (int64_t)lb * a.d;
 #pragma unroll
         for (int k = 0; k < NCHUNK; ++k) {
             const int col = (k * LPR + (int)threadIdx.x) * VEC;
@@ -599,15 +600,49 @@ __global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
     }
 }
 
+// ONE launch of one problem (blk_begin = 0, blk_end = the grid).
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+__global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
+    constexpr int ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, (int32_t)blockIdx.x, red_lds);
+}
+
+// Up to LLMREC_SPMM_MAX_PROBLEMS independent problems of ONE kernel instance in one launch (llmrec_spmm_multi_f32): problem q owns the
+// blocks [begin[q], begin[q + 1]). The arguments stay in the kernarg segment: a problem is picked by uniform compares and a switch over
+// compile-time indices (a runtime index into p[] would copy the array to scratch).
+struct SpmmMulti {
+    SpmmArgs p[LLMREC_SPMM_MAX_PROBLEMS];
+    int32_t begin[LLMREC_SPMM_MAX_PROBLEMS];     // first block of each problem; INT32_MAX past the last one
+};
+static_assert(sizeof(SpmmMulti) < 2048, "spmm: the grouped launch's kernarg block must stay well under 4 KB");
+
+__device__ __forceinline__ int spmm_multi_problem(const SpmmMulti& m, int32_t b) {
+    static_assert(LLMREC_SPMM_MAX_PROBLEMS == 4, "spmm_multi_problem picks one of four problems");
+    return (int)(b >= m.begin[1]) + (int)(b >= m.begin[2]) + (int)(b >= m.begin[3]);
+}
+
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+__global__ __launch_bounds__(TPB) void spmm_multi_kernel(SpmmMulti m) {
+    constexpr int ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    const int32_t b = blockIdx.x;
+    switch (spmm_multi_problem(m, b)) {                                   // (block-uniform)
+    case 0: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[0], b, red_lds); break;
+    case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[1], b, red_lds); break;
+    case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[2], b, red_lds); break;
+    default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[3], b, red_lds); break;
+    }
+}
+
 // one block per (split row, slice): the 256/LPR lane groups each add every (256/LPR)-th segment partial (ascending),
 // then the groups are combined through LDS in group order - a fixed summation tree; then the row's epilogue
 template <int LPR, int NCHUNK, int VEC>
-__global__ __launch_bounds__(256) void spmm_finalize_kernel(SpmmArgs a) {
+__device__ __forceinline__ void spmm_finalize_body(const SpmmArgs& a, int32_t blk, float* fin_lds) {
     constexpr int G = 256 / LPR;
     constexpr int ROWW = NCHUNK * LPR * VEC;
-    __shared__ __attribute__((aligned(16))) float fin_lds[G * ROWW];
     const int gl = threadIdx.x & (LPR - 1), g = threadIdx.x / LPR;
-    const int32_t slice = blockIdx.x / a.n_split_rows, slot = blockIdx.x - slice * a.n_split_rows;
+    const int32_t slice = blk / a.n_split_rows, slot = blk - slice * a.n_split_rows;
     const int32_t crow = a.split_rows[slot];
     const int32_t row = a.slot_row ? a.slot_row[crow] : crow;
     const int32_t deg = a.rowptr[crow + 1] - a.rowptr[crow];
@@ -633,6 +668,25 @@ __global__ __launch_bounds__(256) void spmm_finalize_kernel(SpmmArgs a) {
         for (int gg = 0; gg < G; ++gg) { Vec<VEC> o; o.load(fin_lds + gg * ROWW + (k * LPR + gl) * VEC); acc[k].add(o); }
     }
     finish_row<LPR, NCHUNK, VEC>(a, (int64_t)slice * a.d, row, gl, acc);
+}
+
+template <int LPR, int NCHUNK, int VEC>
+__global__ __launch_bounds__(256) void spmm_finalize_kernel(SpmmArgs a) {
+    __shared__ __attribute__((aligned(16))) float fin_lds[(256 / LPR) * NCHUNK * LPR * VEC];
+    spmm_finalize_body<LPR, NCHUNK, VEC>(a, (int32_t)blockIdx.x, fin_lds);
+}
+
+// the grouped launch's finalize: problem q owns the blocks [begin[q], begin[q + 1]) (its split rows x slices)
+template <int LPR, int NCHUNK, int VEC>
+__global__ __launch_bounds__(256) void spmm_finalize_multi_kernel(SpmmMulti m) {
+    __shared__ __attribute__((aligned(16))) float fin_lds[(256 / LPR) * NCHUNK * LPR * VEC];
+    const int32_t b = blockIdx.x;
+    switch (spmm_multi_problem(m, b)) {                                   // (block-uniform)
+    case 0: spmm_finalize_body<LPR, NCHUNK, VEC>(m.p[0], b - m.begin[0], fin_lds); break;
+    case 1: spmm_finalize_body<LPR, NCHUNK, VEC>(m.p[1], b - m.begin[1], fin_lds); break;
+    case 2: spmm_finalize_body<LPR, NCHUNK, VEC>(m.p[2], b - m.begin[2], fin_lds); break;
+    default: spmm_finalize_body<LPR, NCHUNK, VEC>(m.p[3], b - m.begin[3], fin_lds); break;
+    }
 }
 
 // "These rows of A X" with the list and its length on the device (llmrec_spmm_rows_compact_f32): block (j, p) sums piece p of listed row j
@@ -709,76 +763,50 @@ static int launch_rows_compact(SpmmArgs& a, const int32_t* row_list, const int32
     return LLMREC_OK;
 }
 
-template <int LPR, int NCHUNK, int VEC>
-static int launch_spmm(SpmmArgs& a, hipStream_t stream) {
-    const bool weighted = a.val != nullptr || a.col_scale != nullptr;
-    constexpr int GPB = TPB / LPR;
-    const int64_t S = a.n_slices;
-    // unmasked products: the short rows' tasks as software pipelines (rows_body_pipe) - as many tasks per lane group as keep ~4 blocks per CU
-    const int64_t short_tasks = a.listed_only ? 0 : (a.slot_row ? (int64_t)a.n_short_rows : a.n_rows) * S;
-    int64_t pipe = 1;
-    if (!a.x_mask && !(a.nt_from > 0 && !weighted) && !a.no_pipeline) {
-        pipe = short_tasks + (int64_t)GPB * 8192 < (1ll << 31) ? ceil_div(short_tasks, (int64_t)GPB * 1024) : 1;      // (32-bit task ids in the kernel)
-        if (pipe > 8) pipe = 8;
-        if (pipe < 1) pipe = 1;
-    }
-    a.pipe = (int32_t)pipe;
-    const int64_t row_blocks = ceil_div(short_tasks, GPB * pipe);
-    const int64_t wave_blocks = ceil_div(a.n_wave_rows * S, TPB / 64);
-    const int64_t total = a.n_segments * S + a.n_block_rows * S + wave_blocks + row_blocks;
-    if (total > 0x7fffffffll) { set_error("spmm: too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
-    a.blk_seg = (int32_t)(a.n_segments * S);
-    a.blk_block = a.blk_seg + (int32_t)(a.n_block_rows * S);
-    a.blk_wave = a.blk_block + (int32_t)wave_blocks;
-    if (total > 0) {
-        if (a.x_mask) {
-            if (weighted) spmm_kernel<LPR, NCHUNK, VEC, true, true, false><<<(unsigned)total, TPB, 0, stream>>>(a);
-            else spmm_kernel<LPR, NCHUNK, VEC, false, true, false><<<(unsigned)total, TPB, 0, stream>>>(a);
-        } else if (a.nt_from > 0 && !weighted) {             // cache-policy split (pattern-only operands: the propagation products)
-            spmm_kernel<LPR, NCHUNK, VEC, false, false, true><<<(unsigned)total, TPB, 0, stream>>>(a);
-        } else {
-            if (weighted) spmm_kernel<LPR, NCHUNK, VEC, true, false, false><<<(unsigned)total, TPB, 0, stream>>>(a);
-            else spmm_kernel<LPR, NCHUNK, VEC, false, false, false><<<(unsigned)total, TPB, 0, stream>>>(a);
-        }
-        LLMREC_LAUNCH_CHECK();
-    }
-    if (a.n_split_rows > 0) {
-        spmm_finalize_kernel<LPR, NCHUNK, VEC><<<(unsigned)(a.n_split_rows * S), 256, 0, stream>>>(a);
-        LLMREC_LAUNCH_CHECK();
-    }
-    return LLMREC_OK;
-}
+// The compiled kernel family (LPR, NCHUNK, VEC) and variant (WEIGHTED, MASKED, NT) of a product: two products can share a grouped launch
+// only when both agree. The grouped kernels are compiled for the vector-load families (0..6) and the unmasked, default-cache-policy variants:
+// the latency-bound products of the step; masked products and the cache-policy split run in the HBM-bound or row-restricted paths.
+enum { SPMM_V_MASKED_W, SPMM_V_MASKED, SPMM_V_NT, SPMM_V_WEIGHTED, SPMM_V_PLAIN };
+static const int kSpmmFamilyLpr[] = {4, 8, 16, 32, 64, 64, 64, 16, 64, 64};
 
-}  // namespace llmrec
+struct SpmmPrepared {
+    SpmmArgs a;
+    int family, variant;
+    bool empty;                                  // n_rows == 0 or d == 0: nothing to launch
+    int64_t bytes_x, bytes_y, bytes_z, bytes_s, bytes_partials;     // extents, for the grouped launch's aliasing check
+};
 
-using namespace llmrec;
+static int64_t extent_bytes(int64_t rows, int64_t ld, int64_t width) { return rows > 0 && width > 0 ? ((rows - 1) * ld + width) * 4 : 0; }
 
-extern "C" int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
-                               const int32_t* rowptr, const int32_t* colidx, const float* val,
-                               const float* row_scale, const float* col_scale,
-                               const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, int32_t slice_width,
-                               const llmrec_spmm_plan_t* plan_host, float* partials,
-                               const llmrec_spmm_epilogue_t* epilogue_host, llmrec_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// The argument checks and the SpmmArgs of one product (llmrec_spmm_f32 and each problem of llmrec_spmm_multi_f32).
+static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
+    const int64_t n_rows = pr.n_rows, n_cols = pr.n_cols, ldx = pr.ldx, ldy = pr.ldy;
+    const int32_t d = pr.d, slice_width = pr.slice_width;
+    const float* X = pr.X;
+    float* Y = pr.Y;
+    float* partials = pr.partials;
+    const llmrec_spmm_epilogue_t* epilogue_host = pr.epilogue;
+    out = SpmmPrepared{};
     LLMREC_CHECK_ARG(n_rows >= 0 && n_cols >= 0 && d >= 0, "spmm: negative size");
-    if (n_rows == 0 || d == 0) return LLMREC_OK;
-    LLMREC_CHECK_ARG(rowptr && Y && ldy >= d && ldx >= d, "spmm: null pointer or ld < d");
-    LLMREC_CHECK_ARG(plan_host, "spmm: a row plan is required (llmrec_spmm_plan_count / _fill)");
-    const llmrec_spmm_plan_t& p = *plan_host;
+    out.empty = n_rows == 0 || d == 0;
+    if (out.empty) return LLMREC_OK;
+    LLMREC_CHECK_ARG(pr.rowptr && Y && ldy >= d && ldx >= d, "spmm: null pointer or ld < d");
+    LLMREC_CHECK_ARG(pr.plan, "spmm: a row plan is required (llmrec_spmm_plan_count / _fill)");
+    const llmrec_spmm_plan_t& p = *pr.plan;
     LLMREC_CHECK_ARG(p.n_wave_rows >= 0 && p.n_block_rows >= 0 && p.n_split_rows >= 0 && p.n_segments >= 0 && p.segment >= LLMREC_SPMM_LONG_ROW,
                      "spmm: bad plan sizes");
     LLMREC_CHECK_ARG((p.n_wave_rows == 0 || p.wave_rows) && (p.n_block_rows == 0 || p.block_rows) &&
                      (p.n_split_rows == 0 || (p.split_rows && p.split_seg_begin && p.seg_split && partials)), "spmm: row plan incomplete");
     LLMREC_CHECK_ARG(slice_width == 0 || (slice_width > 0 && d % slice_width == 0), "spmm: slice_width must divide d");
-    SpmmArgs a = {};
-    a.n_rows = n_rows; a.rowptr = rowptr; a.colidx = colidx; a.val = val; a.row_scale = row_scale;
-    a.col_scale = col_scale; a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy;
+    SpmmArgs& a = out.a;
+    a.n_rows = n_rows; a.rowptr = pr.rowptr; a.colidx = pr.colidx; a.val = pr.val; a.row_scale = pr.row_scale;
+    a.col_scale = pr.col_scale; a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy;
     a.d = slice_width > 0 ? slice_width : d;
     a.n_slices = slice_width > 0 ? d / slice_width : 1;
     a.wave_rows = p.wave_rows; a.block_rows = p.block_rows; a.split_rows = p.split_rows; a.split_seg_begin = p.split_seg_begin;
     a.seg_split = p.seg_split; a.partials = partials;
     LLMREC_CHECK_ARG(p.n_short_rows >= 0 && p.n_short_rows <= n_rows, "spmm: bad short-row count");
-    LLMREC_CHECK_ARG(!p.slot_row || (!val && !(epilogue_host && epilogue_host->rows_listed_only)), "spmm: a permuted CSR is pattern-only and complete");
+    LLMREC_CHECK_ARG(!p.slot_row || (!pr.val && !(epilogue_host && epilogue_host->rows_listed_only)), "spmm: a permuted CSR is pattern-only and complete");
     a.slot_row = p.slot_row; a.n_short_rows = p.slot_row ? p.n_short_rows : 0;
     a.n_wave_rows = p.n_wave_rows; a.n_block_rows = p.n_block_rows; a.n_split_rows = p.n_split_rows; a.n_segments = p.n_segments;
     a.segment = p.segment;
@@ -813,21 +841,182 @@ extern "C" int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
     const int dd = a.d;
     const bool vec4 = (dd % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && epi_aligned &&
                       (((uintptr_t)X | (uintptr_t)Y | (uintptr_t)partials) % 16 == 0);
-    if (vec4) {
-        if (dd <= 16) return launch_spmm<4, 1, 4>(a, stream);
-        if (dd <= 32) return launch_spmm<8, 1, 4>(a, stream);
-        if (dd <= 64) return launch_spmm<16, 1, 4>(a, stream);
-        if (dd <= 128) return launch_spmm<32, 1, 4>(a, stream);
-        if (dd <= 256) return launch_spmm<64, 1, 4>(a, stream);
-        if (dd <= 512) return launch_spmm<64, 2, 4>(a, stream);
-        if (dd <= 1024) return launch_spmm<64, 4, 4>(a, stream);
-    } else {
-        if (dd <= 16) return launch_spmm<16, 1, 1>(a, stream);
-        if (dd <= 64) return launch_spmm<64, 1, 1>(a, stream);
-        if (dd <= 256) return launch_spmm<64, 4, 1>(a, stream);
+    int f = -1;
+    if (vec4) f = dd <= 16 ? 0 : dd <= 32 ? 1 : dd <= 64 ? 2 : dd <= 128 ? 3 : dd <= 256 ? 4 : dd <= 512 ? 5 : dd <= 1024 ? 6 : -1;
+    else f = dd <= 16 ? 7 : dd <= 64 ? 8 : dd <= 256 ? 9 : -1;
+    if (f < 0) {
+        set_error("spmm: d = %d outside the compiled kernel family (vec4 = %d)", dd, (int)vec4);
+        return LLMREC_EUNSUPPORTED;
     }
-    set_error("spmm: d = %d outside the compiled kernel family (vec4 = %d)", dd, (int)vec4);
-    return LLMREC_EUNSUPPORTED;
+    const bool weighted = a.val != nullptr || a.col_scale != nullptr;
+    out.family = f;
+    out.variant = a.x_mask ? (weighted ? SPMM_V_MASKED_W : SPMM_V_MASKED)
+                : (a.nt_from > 0 && !weighted) ? SPMM_V_NT                // cache-policy split (pattern-only operands: the propagation products)
+                : weighted ? SPMM_V_WEIGHTED : SPMM_V_PLAIN;
+    out.bytes_x = X ? extent_bytes(n_cols, ldx, d) : 0;
+    out.bytes_y = extent_bytes(n_rows, ldy, d);
+    out.bytes_z = a.Z ? extent_bytes(n_rows, a.ldz, d) : 0;
+    out.bytes_s = a.S ? extent_bytes(n_rows, a.lds, d) : 0;
+    out.bytes_partials = partials ? (int64_t)p.n_segments * d * 4 : 0;
+    return LLMREC_OK;
+}
+
+// The block ranges of one problem whose blocks start at `first` (0 for a launch of its own); returns its block count, -1 past 32-bit ids.
+static int64_t spmm_layout(SpmmArgs& a, int lpr, int64_t first) {
+    const bool weighted = a.val != nullptr || a.col_scale != nullptr;
+    const int64_t GPB = TPB / lpr;
+    const int64_t S = a.n_slices;
+    // unmasked products: the short rows' tasks as software pipelines (rows_body_pipe) - as many tasks per lane group as keep ~4 blocks per CU
+    const int64_t short_tasks = a.listed_only ? 0 : (a.slot_row ? (int64_t)a.n_short_rows : a.n_rows) * S;
+    int64_t pipe = 1;
+    if (!a.x_mask && !(a.nt_from > 0 && !weighted) && !a.no_pipeline) {
+        pipe = short_tasks + GPB * 8192 < (1ll << 31) ? ceil_div(short_tasks, GPB * 1024) : 1;      // (32-bit task ids in the kernel)
+        if (pipe > 8) pipe = 8;
+        if (pipe < 1) pipe = 1;
+    }
+    a.pipe = (int32_t)pipe;
+    const int64_t row_blocks = ceil_div(short_tasks, GPB * pipe);
+    const int64_t wave_blocks = ceil_div(a.n_wave_rows * S, TPB / 64);
+    const int64_t total = a.n_segments * S + a.n_block_rows * S + wave_blocks + row_blocks;
+    if (first + total > 0x7fffffffll) return -1;
+    a.blk_begin = (int32_t)first;
+    a.blk_seg = a.blk_begin + (int32_t)(a.n_segments * S);
+    a.blk_block = a.blk_seg + (int32_t)(a.n_block_rows * S);
+    a.blk_wave = a.blk_block + (int32_t)wave_blocks;
+    a.blk_end = (int32_t)(first + total);
+    return total;
+}
+
+// One launch of n >= 1 laid-out problems of one family / variant (n == 1: the single-problem kernels), then the finalize launch of the
+// problems with split rows.
+template <int LPR, int NCHUNK, int VEC>
+static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipStream_t stream) {
+    if (total > 0) {
+        if (n == 1) {
+            const SpmmArgs& a = pp[0].a;
+            switch (variant) {
+            case SPMM_V_MASKED_W: spmm_kernel<LPR, NCHUNK, VEC, true, true, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_MASKED: spmm_kernel<LPR, NCHUNK, VEC, false, true, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_NT: spmm_kernel<LPR, NCHUNK, VEC, false, false, true><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_WEIGHTED: spmm_kernel<LPR, NCHUNK, VEC, true, false, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            default: spmm_kernel<LPR, NCHUNK, VEC, false, false, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            }
+        } else if constexpr (VEC == 4) {                     // (spmm_run groups the vector-load families only)
+            SpmmMulti m = {};
+            for (int q = 0; q < LLMREC_SPMM_MAX_PROBLEMS; ++q) {
+                if (q < n) { m.p[q] = pp[q].a; m.begin[q] = pp[q].a.blk_begin; }
+                else m.begin[q] = 0x7fffffff;
+            }
+            if (variant == SPMM_V_WEIGHTED) spmm_multi_kernel<LPR, NCHUNK, VEC, true, false, false><<<(unsigned)total, TPB, 0, stream>>>(m);
+            else spmm_multi_kernel<LPR, NCHUNK, VEC, false, false, false><<<(unsigned)total, TPB, 0, stream>>>(m);
+        }
+        LLMREC_LAUNCH_CHECK();
+    }
+    // split rows: their segment partials are summed in a fixed order by one more launch (one block per split row and slice)
+    SpmmMulti fin = {};
+    int nf = 0;
+    int64_t fin_total = 0;
+    for (int q = 0; q < n; ++q) {
+        const SpmmArgs& a = pp[q].a;
+        if (a.n_split_rows <= 0) continue;
+        fin.p[nf] = a; fin.begin[nf] = (int32_t)fin_total;
+        fin_total += (int64_t)a.n_split_rows * a.n_slices;
+        ++nf;
+    }
+    if (nf == 1) {
+        spmm_finalize_kernel<LPR, NCHUNK, VEC><<<(unsigned)fin_total, 256, 0, stream>>>(fin.p[0]);
+        LLMREC_LAUNCH_CHECK();
+    } else if constexpr (VEC == 4) {
+        if (nf > 1) {
+            for (int q = nf; q < LLMREC_SPMM_MAX_PROBLEMS; ++q) fin.begin[q] = 0x7fffffff;
+            spmm_finalize_multi_kernel<LPR, NCHUNK, VEC><<<(unsigned)fin_total, 256, 0, stream>>>(fin);
+            LLMREC_LAUNCH_CHECK();
+        }
+    }
+    return LLMREC_OK;
+}
+
+static bool bytes_overlap(const void* p, int64_t np, const void* q, int64_t nq) {
+    if (!p || !q || np <= 0 || nq <= 0) return false;
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + (uintptr_t)nq && b < a + (uintptr_t)np;
+}
+
+// Checks every problem, lays the non-empty ones out back to back (in the caller's order) and launches them together.
+static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_t stream) {
+    LLMREC_CHECK_ARG(n >= 0 && n <= LLMREC_SPMM_MAX_PROBLEMS && (n == 0 || problems), "spmm_multi: n = %d outside 0..%d", n, LLMREC_SPMM_MAX_PROBLEMS);
+    SpmmPrepared pp[LLMREC_SPMM_MAX_PROBLEMS];
+    int m = 0;
+    for (int q = 0; q < n; ++q) {
+        const int rc = spmm_prepare(problems[q], pp[m]);
+        if (rc != LLMREC_OK) return rc;
+        if (!pp[m].empty) ++m;
+    }
+    if (m == 0) return LLMREC_OK;
+    for (int q = 1; q < m; ++q) {
+        if (pp[q].family != pp[0].family || pp[q].variant != pp[0].variant) {
+            set_error("spmm_multi: problem %d resolves to another kernel instance than problem 0 (family %d / %d, variant %d / %d)",
+                      q, pp[q].family, pp[0].family, pp[q].variant, pp[0].variant);
+            return LLMREC_EUNSUPPORTED;
+        }
+    }
+    if (m > 1 && !(pp[0].family <= 6 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED))) {
+        set_error("spmm_multi: grouped launches are compiled for the unmasked products with vector loads and the default cache policy only");
+        return LLMREC_EUNSUPPORTED;
+    }
+    // what one problem writes (Y, its partials) must not be read or written by another one: they run concurrently
+    for (int i = 0; i < m; ++i) {
+        for (int j = 0; j < m; ++j) {
+            if (i == j) continue;
+            const SpmmArgs &ai = pp[i].a, &aj = pp[j].a;
+            const void* wr[2] = {ai.Y, ai.partials};
+            const int64_t wn[2] = {pp[i].bytes_y, pp[i].bytes_partials};
+            const void* rd[5] = {aj.X, aj.Y, aj.Z, aj.S, aj.partials};
+            const int64_t rn[5] = {pp[j].bytes_x, pp[j].bytes_y, pp[j].bytes_z, pp[j].bytes_s, pp[j].bytes_partials};
+            for (int u = 0; u < 2; ++u)
+                for (int v = 0; v < 5; ++v)
+                    LLMREC_CHECK_ARG(!bytes_overlap(wr[u], wn[u], rd[v], rn[v]), "spmm_multi: the output of problem %d overlaps an operand of problem %d", i, j);
+        }
+    }
+    const int lpr = kSpmmFamilyLpr[pp[0].family];
+    int64_t total = 0;
+    for (int q = 0; q < m; ++q) {
+        const int64_t t = spmm_layout(pp[q].a, lpr, total);
+        if (t < 0) { set_error("spmm: too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
+        total += t;
+    }
+    const int v = pp[0].variant;
+    switch (pp[0].family) {
+    case 0: return launch_spmm<4, 1, 4>(m, pp, v, total, stream);
+    case 1: return launch_spmm<8, 1, 4>(m, pp, v, total, stream);
+    case 2: return launch_spmm<16, 1, 4>(m, pp, v, total, stream);
+    case 3: return launch_spmm<32, 1, 4>(m, pp, v, total, stream);
+    case 4: return launch_spmm<64, 1, 4>(m, pp, v, total, stream);
+    case 5: return launch_spmm<64, 2, 4>(m, pp, v, total, stream);
+    case 6: return launch_spmm<64, 4, 4>(m, pp, v, total, stream);
+    case 7: return launch_spmm<16, 1, 1>(m, pp, v, total, stream);
+    case 8: return launch_spmm<64, 1, 1>(m, pp, v, total, stream);
+    default: return launch_spmm<64, 4, 1>(m, pp, v, total, stream);
+    }
+}
+
+}  // namespace llmrec
+
+using namespace llmrec;
+
+extern "C" int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
+                               const int32_t* rowptr, const int32_t* colidx, const float* val,
+                               const float* row_scale, const float* col_scale,
+                               const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t d, int32_t slice_width,
+                               const llmrec_spmm_plan_t* plan_host, float* partials,
+                               const llmrec_spmm_epilogue_t* epilogue_host, llmrec_stream_t stream_) {
+    llmrec_spmm_problem_t pr = {n_rows, n_cols, rowptr, colidx, val, row_scale, col_scale, X, ldx, Y, ldy, d, slice_width,
+                                plan_host, partials, epilogue_host};
+    return spmm_run(1, &pr, (hipStream_t)stream_);
+}
+
+extern "C" int llmrec_spmm_multi_f32(int32_t n, const llmrec_spmm_problem_t* problems, llmrec_stream_t stream_) {
+    return spmm_run(n, problems, (hipStream_t)stream_);
 }
 
 extern "C" int64_t llmrec_spmm_rows_compact_workspace_bytes(int64_t capacity, int32_t d) {

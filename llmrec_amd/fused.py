@@ -1,4 +1,4 @@
-"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of 28 HIP launches (36 with LLMREC_FOLD=0)
+"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of 24 HIP launches (30 on four streams)
 over preallocated buffers, with the backward pass written out by hand (no autograd graph), captured into one
 HIP graph; likewise an evaluation (forward + scoring + masked top-K).
 
@@ -270,10 +270,10 @@ class FusedStep:
         if self.stamps is not None:
             _call("llmrec_timestamp", self.stamps.data_ptr() + 8 * slot)
 
-    def _spmm(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None):
-        """Y = epilogue(A X) (llmrec_spmm_f32); accumulate: Y += A X. tag: one partial-sum scratch per concurrent chain."""
+    def _spmm_args(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None):
+        """(slice width, plan, partials, epilogue) of one product. tag: one partial-sum scratch per concurrent chain - and so per problem
+        of a grouped launch."""
         d = X.shape[1]
-        self.spmm_edge_units += a.nnz * (d / 64.0)
         sw, pl = a.plan_for(d, whole_row=epilogue is not None and epilogue.op != ops.EPI_NONE)
         partials = None
         if pl.n_seg:
@@ -283,10 +283,44 @@ class FusedStep:
                 partials = self._partials[key] = torch.empty(pl.n_seg * d, dtype=torch.float32, device=X.device)
         if accumulate:
             epilogue = ops.spmm_epilogue(ops.EPI_NONE, 1.0, Y)
+        return sw, pl, partials, epilogue
+
+    def _spmm(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None):
+        """Y = epilogue(A X) (llmrec_spmm_f32); accumulate: Y += A X. tag: one partial-sum scratch per concurrent chain."""
+        d = X.shape[1]
+        self.spmm_edge_units += a.nnz * (d / 64.0)
+        sw, pl, partials, epilogue = self._spmm_args(a, X, Y, accumulate, tag, epilogue)
         rp, ci = pl.csr_of(a)
         _call("llmrec_spmm_f32", a.n_rows, a.n_cols, _p(rp), _p(ci), _p(a.val), _p(a.row_scale), _p(a.col_scale),
               _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),
               _c.byref(epilogue) if epilogue is not None else None)
+
+    def _spmm_group(self, jobs):
+        """Independent products [(a, X, Y, kwargs of _spmm)] in ONE llmrec_spmm_multi_f32 launch, longest first (one stream: each of these
+        latency-bound products alone leaves most CUs idle). Separate launches when the group has one product, when a graph is in the
+        HBM-bound regime (nnz >= ops.SPMM_LATENCY_NNZ: one product fills the chip) or when the library refuses the group. Bit-identical
+        either way: a row's summation tree does not depend on the launch it runs in."""
+        jobs = [j for j in jobs if j is not None]
+        if len(jobs) == 1 or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs):
+            for a, X, Y, kw in jobs:
+                self._spmm(a, X, Y, **kw)
+            return
+        order = sorted(jobs, key=lambda j: -j[0].nnz * j[1].shape[1])             # (stable)
+        probs, keep = [], []
+        for a, X, Y, kw in order:
+            sw, pl, partials, epi = self._spmm_args(a, X, Y, **kw)
+            rp, ci = pl.csr_of(a)
+            pc = pl.c_struct()
+            keep.append(epi)
+            probs.append(ops.SpmmProblemC(a.n_rows, a.n_cols, rp.data_ptr(), ci.data_ptr(), ops._ptr(a.val), ops._ptr(a.row_scale),
+                                          ops._ptr(a.col_scale), X.data_ptr(), _ld(X), Y.data_ptr(), _ld(Y), X.shape[1], sw,
+                                          _c.addressof(pc), ops._ptr(partials), _c.addressof(epi) if epi is not None else None))
+        if not ops.spmm_multi(probs):
+            for a, X, Y, kw in jobs:
+                self._spmm(a, X, Y, **kw)
+            return
+        for a, X, _, _ in jobs:
+            self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
 
     def _linear(self, X, lin, out):
         _call("llmrec_linear_fwd_f32", X.shape[0], self.d, X.shape[1], _p(X), _ld(X), _p(lin.weight), _ld(lin.weight), _p(lin.bias),
@@ -374,6 +408,69 @@ class FusedStep:
         """sampler / after_chain: launches for the ID chain's stream, ahead of / behind its SpMMs (the batch and what is derived from it);
         profile_on_main: the profile chain stays on the current stream (the evaluation's graph, see eval_topk)."""
         m, d = self.m, self.d
+        if self.multi_stream:
+            self._forward_streams(sampler, after_chain, profile_on_main)
+        else:
+            self._forward_one_stream(sampler, after_chain)
+
+        # E_u and E_i (Models.py:185-197) in ONE launch: llmrec_fuse_fwd_multi_f32 (two independent row ranges)
+        keep = []
+
+        def problem(pr, out, base, layers, cat, prof):
+            means, norms = [base] + layers, self._norm_terms(cat, prof)
+            mp, ml = self._tables(means)
+            npt, nl = self._tables(norms)
+            rates = self._rates()
+            keep.extend((mp, ml, npt, nl, rates))
+            pr.rows, pr.mean_scale, pr.n_mean, pr.n_norm = out.shape[0], 1.0 / len(means), len(means), len(norms)
+            pr.mean_terms, pr.mean_ld = _c.cast(mp, _c.c_void_p), _c.cast(ml, _c.c_void_p)
+            pr.norm_terms, pr.norm_ld, pr.rates = _c.cast(npt, _c.c_void_p), _c.cast(nl, _c.c_void_p), _c.cast(rates, _c.c_void_p)
+            pr.out, pr.ldo = out.data_ptr(), _ld(out)
+        arr = (ops.FuseFwdProblem * 2)()
+        problem(arr[0], self.E_i, m.item_id_embedding.weight, self.Il, self.I_cat, self.prof_i)
+        problem(arr[1], self.E_u, m.user_id_embedding.weight, self.Ul, self.U_cat, self.prof_u)
+        if self.fold and self._zero_in_forward:                          # + the regulariser's sum of squares over the image / text streams (terms 0, 1)
+            n_part = _c.c_int32(0)
+            _call("llmrec_fuse_fwd_multi_sumsq_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part))
+            self.ss_n = int(n_part.value)
+        else:
+            _call("llmrec_fuse_fwd_multi_f32", 2, arr, d)
+
+    def _chain_fwd_jobs(self):
+        """The ID chain's 2 L products [(a, X, Y, kwargs)] in dependency order; the last layer's carry the row softmax as the epilogue."""
+        jobs, i_prev = [], self.m.item_id_embedding.weight
+        for l in range(self.L):
+            kw = dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_SOFTMAX)) if l == self.L - 1 else dict(tag=2)
+            jobs.append((self.ui.fwd, i_prev, self.Ul[l], kw))
+            jobs.append((self.iu.fwd, self.Ul[l], self.Il[l], dict(kw)))
+            i_prev = self.Il[l]
+        return jobs
+
+    def _forward_one_stream(self, sampler, after_chain):
+        """The forward's products on ONE stream, as dependency groups of grouped SpMM launches: the k-th product of the ID chain, of the
+        side chain and of the profile chain share a launch (_spmm_group). The chain runs behind the projection so that its first two layers
+        pair with the side and profile products."""
+        if sampler is not None:
+            sampler()
+        if self._zero_in_forward and not self.fold:
+            self.opt.advance()
+        if after_chain is not None:                                      # (reads the batch only)
+            after_chain()
+        self._stamp(1)
+        self._project_all()
+        self._stamp(2)
+        side = [(self.ui.fwd, self.P_cat, self.U_cat, {})] if not self.preprop else []
+        side.append((self.iu.fwd, self.U_cat, self.I_cat, {}))
+        prof = [(self.iu.fwd, self.P_usr, self.prof_i, dict(tag=1)), (self.ui.fwd, self.prof_i, self.prof_u, dict(tag=1))]
+        chain = self._chain_fwd_jobs()
+        for k in range(max(len(chain), len(side), len(prof))):
+            self._spmm_group([c[k] if k < len(c) else None for c in (chain, side, prof)])
+        if self._zero_in_forward and not self.fold:
+            self._feat_reg()
+
+    def _forward_streams(self, sampler, after_chain, profile_on_main):
+        """The forward's products on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule)."""
+        m = self.m
         self._fork(self.s2)
         with self._on(self.s2):                                          # ID chain: needs no projection
             if sampler is not None:                                      # the batch is first read by the losses, after the join below:
@@ -418,29 +515,6 @@ class FusedStep:
             torch.cuda.current_stream().wait_event(ev_chain)                     # (not the stream's tail: after_chain's launches are joined later)
         else:
             self._join(self.s1, self.s2)
-
-        # E_u and E_i (Models.py:185-197) in ONE launch: llmrec_fuse_fwd_multi_f32 (two independent row ranges)
-        keep = []
-
-        def problem(pr, out, base, layers, cat, prof):
-            means, norms = [base] + layers, self._norm_terms(cat, prof)
-            mp, ml = self._tables(means)
-            npt, nl = self._tables(norms)
-            rates = self._rates()
-            keep.extend((mp, ml, npt, nl, rates))
-            pr.rows, pr.mean_scale, pr.n_mean, pr.n_norm = out.shape[0], 1.0 / len(means), len(means), len(norms)
-            pr.mean_terms, pr.mean_ld = _c.cast(mp, _c.c_void_p), _c.cast(ml, _c.c_void_p)
-            pr.norm_terms, pr.norm_ld, pr.rates = _c.cast(npt, _c.c_void_p), _c.cast(nl, _c.c_void_p), _c.cast(rates, _c.c_void_p)
-            pr.out, pr.ldo = out.data_ptr(), _ld(out)
-        arr = (ops.FuseFwdProblem * 2)()
-        problem(arr[0], self.E_i, m.item_id_embedding.weight, self.Il, self.I_cat, self.prof_i)
-        problem(arr[1], self.E_u, m.user_id_embedding.weight, self.Ul, self.U_cat, self.prof_u)
-        if self.fold and self._zero_in_forward:                          # + the regulariser's sum of squares over the image / text streams (terms 0, 1)
-            n_part = _c.c_int32(0)
-            _call("llmrec_fuse_fwd_multi_sumsq_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part))
-            self.ss_n = int(n_part.value)
-        else:
-            _call("llmrec_fuse_fwd_multi_f32", 2, arr, d)
 
     def outputs(self):
         """The reference's 14-tuple as views of the forward buffers (Models.py:199)."""
@@ -571,31 +645,8 @@ class FusedStep:
         # launch gets a stream of its own (each alone lost, both together won: profiles/experiments/r05_step_chain.md)
         main_first = self.multi_stream and self.fold
         loss_s3 = self.multi_stream and self.fold and side_work is not None
-        if main_first:
-            self._spmm(self.iu.bwd, self.dI_cat, self.dU_cat, accumulate=True)
-            if not self.preprop:
-                self._spmm(self.ui.bwd, self.dU_cat, self.dP_cat)
-            self._fork_from(ev_fuse, self.s1)
-        else:
-            self._fork(self.s1)
-        if loss_s3:
-            self._fork_from(ev_rows, self.s3)
-            with self._on(self.s3):
-                side_work()
-            side_work = None
-        with self._on(self.s1):
-            # profile chain: prof_u = ui(prof_i), prof_i = iu(P_usr); user_trans' weight gradient joins the item-side ones below
-            self._spmm(self.ui.bwd, self.dprof_u, self.dprof_i, accumulate=True, tag=1)
-            self._spmm(self.iu.bwd, self.dprof_i, self.dP_usr, tag=1)
-            if self.gemm != "bf16x3":
-                self._wgrad(self.dP_usr, m.user_feats, m.user_trans, False, ws=self.ws_wgrad_b)
 
-        def id_chain():
-            # ID chain (items of layer l+1 from the new users; softmax on the last layer)
-            # every "+ mean term" and every softmax backward below is an epilogue of the SpMM that produces the tensor:
-            #   dI[L] = inv dE_i                      -> g = softmax_bwd(I_L, dI[L])            (one row kernel, no SpMM feeds it)
-            #   dU[l+1] = inv dE_u + A_iu^T g         -> h = softmax_bwd(U_L, dU[l+1]) on the last layer
-            #   dI[l]   = inv dE_i + A_ui^T h         -> (l > 0) feeds the next round as g; (l = 0) IS the item table's gradient
+        def chain_head():
             # U^0 only enters the mean: the user table's gradient needs nothing else. It and the logged loss values go first: whatever
             # this stream still has queued when the weight-gradient GEMM takes every CU (about when the chain's last SpMM starts)
             # waits for the GEMM's blocks to retire and becomes the step's tail.
@@ -607,24 +658,31 @@ class FusedStep:
                     self.opt.step_params(self._emb_params[:1])
             if side_work is not None:
                 side_work()
-            g = self.bufI
             if L >= 1:                                                                    # dI[L] = inv dE_i (mean part), g = softmax_bwd(I_L, dI[L])
-                self._softmax_bwd(self.Il[L - 1], self.dE_i, self.tmpI, alpha=inv); g = self.tmpI
+                self._softmax_bwd(self.Il[L - 1], self.dE_i, self.tmpI, alpha=inv)
+
+        def chain_jobs():
+            # ID chain (items of layer l+1 from the new users; softmax on the last layer)
+            # every "+ mean term" and every softmax backward below is an epilogue of the SpMM that produces the tensor:
+            #   dI[L] = inv dE_i                      -> g = softmax_bwd(I_L, dI[L])            (one row kernel, no SpMM feeds it)
+            #   dU[l+1] = inv dE_u + A_iu^T g         -> h = softmax_bwd(U_L, dU[l+1]) on the last layer
+            #   dI[l]   = inv dE_i + A_ui^T h         -> (l > 0) feeds the next round as g; (l = 0) IS the item table's gradient
+            jobs, g = [], self.tmpI if L >= 1 else self.bufI
             for l in range(L - 1, -1, -1):
-                last = l == L - 1
-                if last:
-                    self._spmm(self.iu.bwd, g, self.tmpU, tag=2,
-                               epilogue=ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, inv, self.dE_u, self.Ul[l]))   # h
+                if l == L - 1:
+                    jobs.append((self.iu.bwd, g, self.tmpU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, inv, self.dE_u, self.Ul[l]))))
                     h = self.tmpU
                 else:
-                    self._spmm(self.iu.bwd, g, self.bufU, tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_u))
+                    jobs.append((self.iu.bwd, g, self.bufU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_u))))
                     h = self.bufU
                 dst = m.item_id_embedding.weight.grad if l == 0 else self.bufI
-                self._spmm(self.ui.bwd, h, dst, tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_i))
+                jobs.append((self.ui.bwd, h, dst, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_i))))
                 g = self.bufI
+            return jobs
+
+        def chain_tail():
             if L == 0:
                 self._axpy(inv, self.dE_i, m.item_id_embedding.weight.grad, False)
-
             # after the last reader of dE_u / dE_i (this chain and the fusion backward): clear the touched rows. (The wait below is for
             # an EARLY event. A wait for a late one anywhere in this stream's chain - e.g. for the transposed side product, had the row
             # stamps needed a clean-up - makes the graph runtime start the WHOLE chain late: profiles/experiments/r03_wgrad.md, last table.)
@@ -639,18 +697,54 @@ class FusedStep:
                 if self.inline_adamw:                                             # the item table's gradient is final: update it here,
                     self.opt.step_params(self._emb_params[1:])                    # beside the weight-gradient GEMM
 
-        # the ID chain depends on the BPR rows only, not on the fusion backward: it starts beside it (captured after it, so that the
-        # fusion backward stays the graph's same-queue successor of the BPR launch) and has most of its SpMMs behind it when the
-        # weight-gradient GEMM takes every CU (one 512-register wave per SIMD leaves no room for a second kernel)
-        if ev_rows is not None:
-            self._fork_from(ev_rows, self.s2)
-        with self._on(self.s2):
-            id_chain()
-        # side chain: I_cat = iu(U_cat), U_cat = ui(P_cat) (or the pre-propagated projection); then the item-side weight gradients
-        if not main_first:
-            self._spmm(self.iu.bwd, self.dI_cat, self.dU_cat, accumulate=True)
-            if not self.preprop:
-                self._spmm(self.ui.bwd, self.dU_cat, self.dP_cat)
+        # side chain: I_cat = iu(U_cat), U_cat = ui(P_cat) (or the pre-propagated projection); profile chain: prof_u = ui(prof_i),
+        # prof_i = iu(P_usr) - user_trans' weight gradient joins the item-side ones below
+        side_jobs = [(self.iu.bwd, self.dI_cat, self.dU_cat, dict(accumulate=True))]
+        if not self.preprop:
+            side_jobs.append((self.ui.bwd, self.dU_cat, self.dP_cat, {}))
+        prof_jobs = [(self.ui.bwd, self.dprof_u, self.dprof_i, dict(accumulate=True, tag=1)), (self.iu.bwd, self.dprof_i, self.dP_usr, dict(tag=1))]
+        if not self.multi_stream:
+            # ONE stream: the k-th product of the ID chain, the side chain and the profile chain share a launch (_spmm_group)
+            chain_head()
+            chain = chain_jobs()
+            for k in range(max(len(chain), len(side_jobs), len(prof_jobs))):
+                self._spmm_group([c[k] if k < len(c) else None for c in (chain, side_jobs, prof_jobs)])
+            if self.gemm != "bf16x3":
+                self._wgrad(self.dP_usr, m.user_feats, m.user_trans, False, ws=self.ws_wgrad_b)
+            chain_tail()
+        else:
+            # four streams, folded step: the critical transposed side product is captured BEFORE the two side branches and the logged-scalar
+            # launch gets a stream of its own (each alone lost, both together won: profiles/experiments/r05_step_chain.md)
+            if main_first:
+                for job in side_jobs:
+                    self._spmm(job[0], job[1], job[2], **job[3])
+                self._fork_from(ev_fuse, self.s1)
+            else:
+                self._fork(self.s1)
+            if loss_s3:
+                self._fork_from(ev_rows, self.s3)
+                with self._on(self.s3):
+                    side_work()
+                side_work = None
+            with self._on(self.s1):
+                for job in prof_jobs:
+                    self._spmm(job[0], job[1], job[2], **job[3])
+                if self.gemm != "bf16x3":
+                    self._wgrad(self.dP_usr, m.user_feats, m.user_trans, False, ws=self.ws_wgrad_b)
+            # the ID chain depends on the BPR rows only, not on the fusion backward: it starts beside it (captured after it, so that the
+            # fusion backward stays the graph's same-queue successor of the BPR launch) and has most of its SpMMs behind it when the
+            # weight-gradient GEMM takes every CU (one 512-register wave per SIMD leaves no room for a second kernel)
+            if ev_rows is not None:
+                self._fork_from(ev_rows, self.s2)
+            with self._on(self.s2):
+                chain_head()
+                for job in chain_jobs():
+                    self._spmm(job[0], job[1], job[2], **job[3])
+                chain_tail()
+            if not main_first:
+                for job in side_jobs:
+                    self._spmm(job[0], job[1], job[2], **job[3])
+        # the item-side weight gradients
         dY_cat = self.dU_cat if self.preprop else self.dP_cat
         targets = self.wgrad_targets(dY_cat, self.dP_usr)
         item_pairs, text_pairs, image_pairs = targets[0][0], targets[2][0], targets[3][0]

@@ -29,6 +29,11 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else _c.c_void_p(t.data_ptr())
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    """a tensor's address for a pointer field of a ctypes struct (None = NULL)"""
+    return None if t is None else t.data_ptr()
+
+
 def _need_gpu(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -68,6 +73,14 @@ class SpmmEpilogueC(_c.Structure):
                 ("post_scale", _c.c_void_p), ("x_row_mask", _c.c_void_p), ("x_mask_active", _c.c_int32), ("y_row_flag", _c.c_void_p),
                 ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32),
                 ("x_nt_from_row", _c.c_int32), ("xcd_contiguous", _c.c_int32), ("no_pipeline", _c.c_int32)]
+
+
+class SpmmProblemC(_c.Structure):
+    """llmrec_spmm_problem_t: the arguments of one llmrec_spmm_f32 call, for llmrec_spmm_multi_f32"""
+    _fields_ = [("n_rows", _c.c_int64), ("n_cols", _c.c_int64), ("rowptr", _c.c_void_p), ("colidx", _c.c_void_p), ("val", _c.c_void_p),
+                ("row_scale", _c.c_void_p), ("col_scale", _c.c_void_p), ("X", _c.c_void_p), ("ldx", _c.c_int64), ("Y", _c.c_void_p),
+                ("ldy", _c.c_int64), ("d", _c.c_int32), ("slice_width", _c.c_int32), ("plan", _c.c_void_p), ("partials", _c.c_void_p),
+                ("epilogue", _c.c_void_p)]
 
 
 EPI_NONE, EPI_SOFTMAX, EPI_SOFTMAX_BWD = 0, 1, 2
@@ -485,6 +498,14 @@ def spmm_raw(a: Csr, X: torch.Tensor, out: Optional[torch.Tensor] = None, accumu
               _p(col_scale), _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),
               _c.byref(epilogue) if epilogue is not None else None, _stream())
     return Y
+
+
+def spmm_multi(problems: Sequence[SpmmProblemC]) -> bool:
+    """Up to LLMREC_SPMM_MAX_PROBLEMS independent products in ONE llmrec_spmm_multi_f32 launch on the current stream (results bit-identical
+    to separate llmrec_spmm_f32 calls). False: the library refused the group (LLMREC_EUNSUPPORTED - e.g. the problems resolve to different
+    kernel instances), nothing was launched and the caller issues the products one by one."""
+    arr = (SpmmProblemC * len(problems))(*problems)
+    return _lib.call_unless_unsupported("llmrec_spmm_multi_f32", len(problems), arr, _stream())
 
 
 class _SpMM(torch.autograd.Function):
