@@ -786,6 +786,12 @@ def test_device_sampler_properties(ops):
     # B > n_exist -> with replacement
     u, _, _ = ops.sample_bpr(1, 0, exist[:50], I, csr, 128)
     assert u.numel() == 128 and set(u.cpu().tolist()) <= set(exist[:50].cpu().tolist())
+    # and the draws are the numpy restatement's, bit for bit (tests/_sampler_ref.py; the grid is in tests/test_gpu_sampler.py)
+    from tests import _sampler_ref as R
+    rp, ci = csr.rowptr.cpu().numpy(), csr.colidx.cpu().numpy()
+    for seed, step, ex, b in [(2022, s_, exist, B) for s_ in range(4)] + [(1, 0, exist[:50], 128)]:
+        for got, want in zip(ops.sample_bpr(seed, step, ex, I, csr, b), R.sample_bpr(seed, step, ex.cpu().numpy(), I, rp, ci, b)):
+            assert torch.equal(got.cpu(), torch.from_numpy(want))
 
 
 def test_sample_batch_one_launch_with_augmented_triples(ops):
@@ -826,6 +832,20 @@ def test_sample_batch_one_launch_with_augmented_triples(ops):
     u2 = torch.empty(B, dtype=torch.int64, device=DEV); p2 = torch.empty_like(u2); n2 = torch.empty_like(u2)
     ops.sample_batch(77, sd, exist, I, csr, B, 0, B, 0, None, None, u2, p2, n2, torch.zeros(1, dtype=torch.int32, device=DEV))
     assert torch.equal(a[0], u2) and torch.equal(a[1], p2) and torch.equal(a[2], n2)
+    # and both ranks' buffers are the numpy restatement's, bit for bit (tests/_sampler_ref.py; the grid is in tests/test_gpu_sampler.py)
+    from tests import _sampler_ref as R
+    rp, ci = csr.rowptr.cpu().numpy(), csr.colidx.cpu().numpy()
+    for step in (0, 5):
+        for r in range(W):
+            step_dev = torch.tensor([step], dtype=torch.int64, device=DEV)
+            u, p, n = (torch.full((B + n_aug,), -7, dtype=torch.int64, device=DEV) for _ in range(3))
+            nv = torch.zeros(1, dtype=torch.int32, device=DEV)
+            ops.sample_batch(77, step_dev, exist, I, csr, B * W, r * B, B, n_aug, aug_pos, aug_neg, u, p, n, nv)
+            wu, wp, wn, w_valid, w_step = R.sample_batch(77, step, np.arange(U), I, rp, ci, B * W, r * B, B, n_aug,
+                                                         aug_pos.cpu().numpy(), aug_neg.cpu().numpy())
+            assert int(nv) == w_valid and int(step_dev) == w_step
+            for got, want in zip((u, p, n), (wu, wp, wn)):
+                assert torch.equal(got.cpu(), torch.from_numpy(want))
 
 
 def test_score_topk_exact_ties_are_ordered_by_item_id(ops):

@@ -285,8 +285,16 @@ class Data(object):
         tr = csr_of(self.train_items)
         train = ops.Csr(self.n_users, self.n_items, tr[0], tr[1], None, None, None, ops.SpmmPlan())
         self._device_state = {"device": device, "train": train, "test": csr_of(self.test_set), "val": csr_of(self.val_set),
-                              "exist_users": torch.tensor(self.exist_users, dtype=torch.int64, device=device)}
+                              "exist_users": torch.tensor(self.checked_exist_users(), dtype=torch.int64, device=device)}
         return self._device_state
+
+    def checked_exist_users(self):
+        """exist_users as the device sampler may use it: llmrec_sample_bpr draws the positive from the user's train row and reads that
+        row's first entry whatever its length, so a listed user without train items is refused here (the constructor never lists one)."""
+        empty = [u for u in self.exist_users if not self.train_items.get(u)]
+        if empty:
+            raise ValueError("exist_users lists %d user(s) with no train items (first: %r)" % (len(empty), empty[0]))
+        return self.exist_users
 
     def sample_device(self, seed, step, device):
         """(users, pos, neg) int64 device tensors from the HIP sampler."""
