@@ -644,7 +644,10 @@ int llmrec_adamw_multi_zero_rows_f32(int32_t n_tensors, const llmrec_adamw_tenso
  * For each listed user: scores over all items (fp32 MFMA), train items removed (CSR row of the
  * user, ascending columns), top K by (score desc, item id asc). The U x I matrix is never
  * written. Missing entries (fewer than K candidates) are -1 / -inf.
- * K <= LLMREC_TOPK_MAX. d a multiple of 16 and <= 128.
+ * K <= LLMREC_TOPK_MAX for the single-sweep calls (llmrec_score_topk_f32 / _ws_f32 / _mode_f32: every
+ * selection structure of the sweeps is a 64-slot list, one slot per lane); llmrec_score_topk_wide_f32
+ * (below) ranks up to LLMREC_TOPK_WIDE_MAX items per user by repeating the sweep over a growing mask.
+ * d a multiple of 16 and <= 128.
  * ------------------------------------------------------------------------------------------ */
 #define LLMREC_TOPK_MAX 64
 int llmrec_score_topk_f32(int32_t n_query, const int64_t* query_users,
@@ -694,6 +697,36 @@ int llmrec_score_topk_mode_f32(int32_t n_query, const int64_t* query_users,
                                int32_t K, int32_t* out_idx, float* out_score,
                                void* workspace, int64_t workspace_bytes, int32_t mode, llmrec_stream_t stream);
 int64_t llmrec_score_topk_stats_offset(int32_t n_query, int64_t n_items);
+/* Cut-offs beyond the 64 slots of a sweep: the same ranking rule (exact-fp32 scores - the bits of llmrec_scores_f32 -, train items removed,
+ * (score desc, item id asc), missing entries -1 / -inf, out_idx / out_score [n_query][K]) for K <= LLMREC_TOPK_WIDE_MAX.
+ *   K <= LLMREC_TOPK_MAX: forwards to llmrec_score_topk_mode_f32 (same launches, same bits; train_nnz is not read).
+ *   K >  LLMREC_TOPK_MAX: ROUNDS. The order is a strict total order, so ranks [c p, c (p + 1)) of a user are the top c of (candidates minus
+ *     the user's first c p items): the masked top-K call runs ceil(K / c) times, c = LLMREC_TOPK_PREFILTER_MAX_K in the prefilter mode and
+ *     LLMREC_TOPK_MAX in the exact mode (the last pass asks for the K - c p items still missing), each time with the items already emitted
+ *     joined to the mask. Every pass is an ordinary llmrec_score_topk_mode_f32 call over a compact copy of the queried user rows (identity
+ *     query list, the same score bits) and a mask CSR of n_query + 1 row pointers that the pass rebuilds on the device: row q = the ascending
+ *     merge of query q's train row (duplicates kept) with the ids emitted for q so far (entries < 0 are never merged). So the first 64
+ *     columns equal the K = 64 answer of the single-sweep call bit for bit, duplicate or unsorted query users are fine, and a pass costs one
+ *     call at K = c plus three small launches (row pointers: one single-block scan; rows: one wave per query; the strided write of the pass's
+ *     columns into the outputs). 1 + passes x (3 + the launches of the call) launches, a function of the host arguments alone; capturable,
+ *     deterministic (no atomics), no allocation.
+ *   train_nnz: the capacity reserved for train entries in the rebuilt mask - at least the sum of the train-row lengths of the query users,
+ *     a user listed twice counted twice (the CSR's entry count when the query users are distinct; 0 without a train CSR). A smaller value
+ *     is a caller error that the device detects before anything is written: every list then comes back empty (-1 / -inf).
+ *     train_nnz + n_query * K must stay below 2^31.
+ *   Workspace (required for K > LLMREC_TOPK_MAX, 16-byte aligned; too small: LLMREC_EWORKSPACE). With A(x) = x rounded up to 256:
+ *     llmrec_score_topk_wide_workspace_bytes = llmrec_score_topk_workspace_bytes(n_query, n_items, d)                       for K <= 64, else that
+ *       + A(4 n_query d4) + A(8 n_query) + 2 A(4 (n_query + 1)) + A(4 n_query) + 256 + 2 A(4 (train_nnz + n_query K)) + 2 A(4 * 64 n_query)
+ *     (d4 = d rounded up to 4: the user rows; the query list; two generations of row pointers; the per-query counts of the last pass; the
+ *     overflow word; two generations of mask columns; the ids and scores of one pass). -1 for bad sizes (K outside 1 .. 1024 included). */
+#define LLMREC_TOPK_WIDE_MAX 1024
+int64_t llmrec_score_topk_wide_workspace_bytes(int32_t n_query, int64_t n_items, int32_t d, int32_t K, int64_t train_nnz);
+int llmrec_score_topk_wide_f32(int32_t n_query, const int64_t* query_users,
+                               const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
+                               int64_t n_items, int32_t d,
+                               const int32_t* train_rowptr, const int32_t* train_colidx,
+                               int32_t K, int32_t* out_idx, float* out_score,
+                               void* workspace, int64_t workspace_bytes, int32_t mode, int64_t train_nnz, llmrec_stream_t stream);
 int llmrec_scores_f32(int32_t n_query, const int64_t* query_users,
                       const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
                       int64_t n_items, int32_t d, float* S, int64_t lds, llmrec_stream_t stream);
@@ -711,7 +744,9 @@ int llmrec_topk_metrics(int32_t n_query, const int64_t* query_users, int32_t K, 
                         const int32_t* test_rowptr, int32_t n_ks, const int32_t* ks_host, double* out, llmrec_stream_t stream);
 /* Round 6 - a whole evaluation's R10 in two launches (what batch_test.py:160-165 accumulates over the users): out[4][n_ks] = the SUMS over the
  * query users of precision, recall, ndcg, hit-ratio at every cut-off (the caller divides by the number of users), from the ranked lists and the
- * held-out CSR directly - the hit flags and the per-user values stay in registers, the users are added by fixed trees (deterministic). K <= 128.
+ * held-out CSR directly - the hit flags and the per-user values stay in registers, the users are added by fixed trees (deterministic). K <= LLMREC_TOPK_WIDE_MAX:
+ * up to K = 128 one thread per user with the hit flags in two 64-bit words; beyond (csrc/topk_wide.hip) one wave per user, a lane-private bit
+ * per rank, the sums over ranks by lane and butterfly (the same values up to the order of the double additions). Same workspace either way.
  * `out` may be device memory or mapped (pinned) host memory: an evaluation graph then ends with the twelve doubles already on the host. */
 int64_t llmrec_topk_eval_sums_workspace_bytes(int32_t n_query, int32_t n_ks);
 int llmrec_topk_eval_sums(int32_t n_query, const int64_t* query_users, int32_t K, const int32_t* topk_idx, const int32_t* test_rowptr,

@@ -37,6 +37,10 @@ void set_error(const char* fmt, ...);
         }                                                                                  \
     } while (0)
 
+// csrc/topk_wide.hip: the wave-per-user first launch of llmrec_topk_eval_sums for lists of more than 128 columns (partial[block][4 n_ks])
+int topk_eval_sums_wide_partials(int32_t n_query, const int64_t* query_users, int32_t K, const int32_t* topk_idx, const int32_t* rowptr,
+                                 const int32_t* colidx, int32_t n_ks, const int32_t* ks_host, double* partial, hipStream_t stream);
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 

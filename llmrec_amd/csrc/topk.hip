@@ -1769,7 +1769,7 @@ int64_t llmrec_topk_eval_sums_workspace_bytes(int32_t n_query, int32_t n_ks) {
 int llmrec_topk_eval_sums(int32_t n_query, const int64_t* query_users, int32_t K, const int32_t* topk_idx, const int32_t* test_rowptr,
                           const int32_t* test_colidx, int32_t n_ks, const int32_t* ks_host, void* workspace, int64_t workspace_bytes,
                           double* out, llmrec_stream_t stream_) {
-    LLMREC_CHECK_ARG(n_query >= 0 && K > 0 && K <= 128 && n_ks >= 1 && n_ks <= 8 && ks_host && out, "topk_eval_sums: bad sizes (K <= 128, at most 8 cut-offs)");
+    LLMREC_CHECK_ARG(n_query >= 0 && K > 0 && K <= LLMREC_TOPK_WIDE_MAX && n_ks >= 1 && n_ks <= 8 && ks_host && out, "topk_eval_sums: bad sizes (K <= %d, at most 8 cut-offs)", LLMREC_TOPK_WIDE_MAX);
     LLMREC_CHECK_ARG(n_query == 0 || (query_users && topk_idx && test_rowptr && test_colidx), "topk_eval_sums: null pointer");
     if (!workspace || workspace_bytes < llmrec_topk_eval_sums_workspace_bytes(n_query, n_ks)) {
         set_error("topk_eval_sums: workspace %lld < %lld", (long long)workspace_bytes, (long long)llmrec_topk_eval_sums_workspace_bytes(n_query, n_ks));
@@ -1779,7 +1779,10 @@ int llmrec_topk_eval_sums(int32_t n_query, const int64_t* query_users, int32_t K
     ks.n = n_ks;
     for (int i = 0; i < n_ks; ++i) { LLMREC_CHECK_ARG(ks_host[i] > 0, "topk_eval_sums: cut-offs must be positive"); ks.k[i] = ks_host[i]; }
     const int n_blocks = (int)ceil_div(n_query, ES_THREADS);
-    if (n_blocks > 0) {
+    if (K > 128) {                                             // (the flags of topk_eval_sums_kernel are two 64-bit words: csrc/topk_wide.hip, one wave per user, same partials)
+        const int rc = topk_eval_sums_wide_partials(n_query, query_users, K, topk_idx, test_rowptr, test_colidx, n_ks, ks.k, (double*)workspace, (hipStream_t)stream_);
+        if (rc != LLMREC_OK) return rc;
+    } else if (n_blocks > 0) {
         topk_eval_sums_kernel<<<n_blocks, ES_THREADS, 0, (hipStream_t)stream_>>>(n_query, query_users, K, topk_idx, test_rowptr, test_colidx, ks, (double*)workspace);
         LLMREC_LAUNCH_CHECK();
     }

@@ -911,7 +911,9 @@ class FusedStep:
             n = q.numel()
             idx = torch.empty(n, K, dtype=torch.int32, device=q.device)
             sc = torch.empty(n, K, dtype=torch.float32, device=q.device)
-            ws = ops.topk_workspace(n, self.I, q.device, self.d)
+            wide = K > _lib.CONST["LLMREC_TOPK_MAX"]               # rounds of the sweep inside the graph (llmrec_score_topk_wide_f32)
+            nnz = ops._wide_train_nnz(train, q) if wide else 0
+            ws = ops.topk_workspace(n, self.I, q.device, self.d, K, nnz)
             sums = sums_ws = None
             if held is not None:
                 sums = torch.zeros(4, len(Ks), dtype=torch.float64).pin_memory()
@@ -926,9 +928,14 @@ class FusedStep:
                 # 0.572 ms per replay back to back / 0.599 one at a time, against 0.73 - 0.76 / 0.595 with the training forward's three
                 # side branches - successive launches of a many-branch graph pay for their cross-queue joins (tools/eval_probe.py, round 6)
                 self.forward(profile_on_main=True)
-                _call("llmrec_score_topk_mode_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
-                      _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-                      K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, ops.topk_mode(None, self.I, self.d, K))
+                if wide:
+                    _call("llmrec_score_topk_wide_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
+                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+                          K, _p(idx), _p(sc), _p(ws), ws.numel(), ops.topk_wide_mode(None, self.I, self.d, K), nnz)
+                else:
+                    _call("llmrec_score_topk_mode_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
+                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+                          K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, ops.topk_mode(None, self.I, self.d, K))
                 if held is not None:
                     ops.topk_eval_sums(idx, q, held[0], held[1], Ks, out=sums, ws=sums_ws)
                 if auc:

@@ -1078,16 +1078,49 @@ def topk_set_part_items(items: int = 0):
     _lib.call("llmrec_topk_set_part_items", int(items))
 
 
-def score_topk(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, mode=None, stats: Optional[dict] = None):
-    """Masked top-K item ids (int32 [n_query, K], -1 = none) and scores for the listed users. stats (a dict; synchronises): receives
+def _wide_train_nnz(train: Optional[Csr], q: torch.Tensor) -> int:
+    """llmrec_score_topk_wide_f32's train_nnz: the sum of the train-row lengths of the listed users, a user listed twice counted twice
+    (one device read; callers that capture size their workspace with it beforehand)."""
+    if train is None or q.numel() == 0:
+        return 0
+    rp = train.rowptr
+    return int((rp[q + 1].to(torch.int64) - rp[q].to(torch.int64)).sum().item())
+
+
+def topk_wide_mode(mode=None, n_items: int = 0, d: int = 64, K: int = 50) -> int:
+    """The mode of a call at K > LLMREC_TOPK_MAX (rounds of the single-sweep call, llmrec_score_topk_wide_f32): "auto" = the bf16 sweep, 56
+    ranks per pass - a pass asks for at most LLMREC_TOPK_PREFILTER_MAX_K items, so the prefilter always has room to verify, and
+    ceil(K / 56) of its calls cost less than ceil(K / 64) exact sweeps. K <= LLMREC_TOPK_MAX: topk_mode's answer."""
+    return topk_mode(mode, n_items, d, min(K, CONST["LLMREC_TOPK_PREFILTER_MAX_K"]) if K > CONST["LLMREC_TOPK_MAX"] else K)
+
+
+def score_topk(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, mode=None, stats: Optional[dict] = None,
+               train_nnz: Optional[int] = None):
+    """Masked top-K item ids (int32 [n_query, K], -1 = none) and scores for the listed users. K <= LLMREC_TOPK_MAX (64): one sweep
+    (llmrec_score_topk_mode_f32); up to LLMREC_TOPK_WIDE_MAX (1024): rounds of it (llmrec_score_topk_wide_f32), same ranking rule and bits.
+    K > 64 with a train CSR sizes its mask from the queried train rows, which is ONE HOST READ of the device (a synchronisation the K <= 64
+    call does not have; not capturable). train_nnz: an upper bound the caller knows - train.colidx.numel() when the query users are
+    distinct - replaces that read (a bound that is too small returns empty lists, see include/llmrec_hip.h).
+    stats (a dict; synchronises; at K > 64 the words describe single passes and are reported as None): receives
     "fallback_tiles" / "tiles" - the user tiles the bf16 mode's verification sent to the exact sweep -, "drains" - the pool drains of the bf16
     sweep, summed over its blocks - and "bitmap_rows" - the train rows its blocks swept as bitmaps (None outside the bf16 mode)."""
     _need_gpu(Eu, Ei, query_users)
     Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
     q = query_users.to(torch.int64).contiguous()
     n = q.numel()
+    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+        raise RuntimeError("score_topk: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (K, CONST["LLMREC_TOPK_WIDE_MAX"]))
     idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
     sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    if K > CONST["LLMREC_TOPK_MAX"]:
+        nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
+        ws = topk_workspace(n, Ei.shape[0], Eu.device, Eu.shape[1], K, nnz)
+        _lib.call("llmrec_score_topk_wide_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), Ei.shape[0], Eu.shape[1],
+                  _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+                  K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, Ei.shape[0], Eu.shape[1], K), nnz, _stream())
+        if stats is not None:                                                                          # (the words describe single passes)
+            stats.update(tiles=(n + 15) // 16, fallback_tiles=None, drains=None, bitmap_rows=None)
+        return idx, sc
     ws = topk_workspace(n, Ei.shape[0], Eu.device, Eu.shape[1])
     _lib.call("llmrec_score_topk_mode_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), Ei.shape[0], Eu.shape[1],
               _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
@@ -1102,9 +1135,15 @@ def score_topk(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, 
     return idx, sc
 
 
-def topk_workspace(n_query: int, n_items: int, device, d: int = 64) -> Optional[torch.Tensor]:
-    """Scratch for llmrec_score_topk_ws_f32: the item table in fragment order + the part lists of the left-over user tiles."""
-    nbytes = _lib.query("llmrec_score_topk_workspace_bytes", n_query, n_items, d)
+def topk_workspace(n_query: int, n_items: int, device, d: int = 64, K: Optional[int] = None, train_nnz: int = 0) -> Optional[torch.Tensor]:
+    """Scratch for llmrec_score_topk_ws_f32: the item table in fragment order + the part lists of the left-over user tiles. K beyond
+    LLMREC_TOPK_MAX (with train_nnz, see _wide_train_nnz): the larger workspace of llmrec_score_topk_wide_f32."""
+    if K is not None and K > CONST["LLMREC_TOPK_MAX"]:
+        nbytes = _lib.query("llmrec_score_topk_wide_workspace_bytes", n_query, n_items, d, K, train_nnz)
+        if nbytes < 0:
+            raise RuntimeError("topk_workspace: bad sizes (K <= %d, train_nnz + n_query * K < 2^31)" % CONST["LLMREC_TOPK_WIDE_MAX"])
+    else:
+        nbytes = _lib.query("llmrec_score_topk_workspace_bytes", n_query, n_items, d)
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
 
 
@@ -1112,7 +1151,7 @@ def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] =
     """Stage-1 candidate export: the top-k item ids per user WITHOUT masking, i.e. what the reference
     README's `torch.topk(user_emb @ item_emb.T, k=10)` snippet (README.md:243-247) produces for
     `candidate_indices`, as an int64 [n, k] tensor - computed by the scoring kernel, never
-    materialising U x I. Ties are broken by ascending item id."""
+    materialising U x I. Ties are broken by ascending item id. k <= LLMREC_TOPK_WIDE_MAX (1024)."""
     q = torch.arange(Eu.shape[0], device=Eu.device) if query_users is None else query_users
     idx, _ = score_topk(Eu, Ei, q, None, k)
     return idx.to(torch.int64)
@@ -1137,7 +1176,8 @@ def topk_hits(topk_idx: torch.Tensor, query_users: torch.Tensor, test_rowptr: to
 def topk_eval_sums(idx: torch.Tensor, query_users: torch.Tensor, test_rowptr: torch.Tensor, test_colidx: torch.Tensor, Ks,
                    out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[4, len(Ks)] float64: the sums over the query users of precision / recall / ndcg / hit-ratio at every cut-off (llmrec_topk_eval_sums:
-    hits, per-user metrics and their sums in two launches). out: a device tensor or a PINNED host tensor (written by the kernel itself)."""
+    hits, per-user metrics and their sums in two launches; lists of up to LLMREC_TOPK_WIDE_MAX = 1024 columns). out: a device tensor or a
+    PINNED host tensor (written by the kernel itself)."""
     _need_gpu(idx, query_users, test_rowptr, test_colidx)
     n, K = idx.shape
     Ks = [int(k) for k in Ks]
