@@ -616,8 +616,12 @@ int llmrec_adamw_advance(float* state3, float lr, float beta1, float beta2, llmr
 int llmrec_adamw_f32(int64_t n, float* p, const float* g, float* m, float* v, const float* state3,
                      float lr, float beta1, float beta2, float eps, float weight_decay, llmrec_stream_t stream);
 
-/* the same update for up to LLMREC_ADAMW_MAX_TENSORS parameters in one launch */
+/* the same update for up to LLMREC_ADAMW_MAX_TENSORS parameters in one launch: one block per LLMREC_ADAMW_CHUNK elements of a tensor. A
+ * chunk that lies inside its tensor and whose p / g / m / v / g_out are 16-byte aligned moves as float4 (every load of a thread issued
+ * before its first arithmetic); a tensor's tail chunk and misaligned views take 4-byte accesses. Both call one per-element update: the
+ * bits are those of llmrec_adamw_f32 either way. */
 #define LLMREC_ADAMW_MAX_TENSORS 16
+#define LLMREC_ADAMW_CHUNK 1024
 typedef struct { float* p; const float* g; float* m; float* v; int64_t n;
                  float g_scale;   /* the gradient is g_scale * g (non-zero; 1 = plain): saves a scaling pass over a large table */
                  float* g_out;    /* optional: receives the gradient the update used (g_scale * g) - the parameter's .grad when g is another
@@ -634,6 +638,19 @@ int llmrec_adamw_multi_zero_rows_f32(int32_t n_tensors, const llmrec_adamw_tenso
                                      float lr, float beta1, float beta2, float eps, float weight_decay,
                                      int32_t n_jobs, const llmrec_zero_rows_job_t* jobs_host, int32_t B_cap, const int32_t* n_valid_dev,
                                      llmrec_stream_t stream);
+
+/* The three independent row sweeps a one-stream training step issues right behind its loss backward, as ONE launch of three block
+ * ranges: llmrec_fuse_bwd_src_multi_f32 (n_fuse_problems, fuse_host, d), llmrec_adamw_multi_f32 (n_tensors ... weight_decay) and
+ * llmrec_softmax_rows_bwd_scaled_f32 (sm_rows, sm_d, sm_alpha ... sm_lddz), each with the argument checks and, bit for bit, the result
+ * of its own entry point (the kernels share the row / chunk bodies). A member is absent when its count is 0 (n_fuse_problems = 0,
+ * n_tensors = 0, sm_rows = 0). The caller guarantees that no member writes what another reads. Only the instance the step runs is
+ * compiled - 16-byte accesses and d, sm_d <= 64; for anything else the call returns LLMREC_EUNSUPPORTED WITHOUT launching and the caller
+ * issues the three launches itself. */
+int llmrec_step_rows_group_f32(int32_t n_fuse_problems, const llmrec_fuse_bwd_problem_t* fuse_host, int32_t d,
+                               int32_t n_tensors, const llmrec_adamw_tensor_t* tensors_host, const float* state3,
+                               float lr, float beta1, float beta2, float eps, float weight_decay,
+                               int64_t sm_rows, int32_t sm_d, float sm_alpha, const float* sm_Y, int64_t sm_ldy, const float* sm_dY, int64_t sm_lddy,
+                               float* sm_dZ, int64_t sm_lddz, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * R9/R10  full-rank scoring + masked top-K + hit vectors

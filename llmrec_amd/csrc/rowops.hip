@@ -53,10 +53,12 @@ struct RowReg {
     }
 };
 
-#define ROW_LOOP_HEADER                                                                           \
+// vb / nvb: the block's index and the block count of the sweep (a kernel of its own passes blockIdx.x / gridDim.x; a grouped launch
+// - step_rows_group_kernel - the position inside the member's block range)
+#define ROW_LOOP_HEADER(vb, nvb)                                                                  \
     const int gl = threadIdx.x & (RL - 1);                                                        \
-    const int64_t row_stride = (int64_t)gridDim.x * ROWS_PER_BLOCK;                               \
-    for (int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + threadIdx.x / RL; row < rows; row += row_stride)
+    const int64_t row_stride = (int64_t)(nvb) * ROWS_PER_BLOCK;                                   \
+    for (int64_t row = (int64_t)(vb) * ROWS_PER_BLOCK + threadIdx.x / RL; row < rows; row += row_stride)
 
 // ---------------------------------------------------------------------------------------------
 // softmax over d
@@ -64,7 +66,7 @@ struct RowReg {
 template <int VEC, int NCHUNK>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(int64_t rows, int d, const float* __restrict__ Z, int64_t ldz,
                                                           float* __restrict__ Y, int64_t ldy) {
-    ROW_LOOP_HEADER {
+    ROW_LOOP_HEADER(blockIdx.x, gridDim.x) {
         RowReg<VEC, NCHUNK> z;
         z.load(Z + row * ldz, gl, d);
         float mx = -INFINITY;
@@ -94,10 +96,9 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(int64_t rows, int d, c
 }
 
 template <int VEC, int NCHUNK>
-__global__ __launch_bounds__(256) void softmax_bwd_kernel(int64_t rows, int d, const float* __restrict__ Y, int64_t ldy,
-                                                          const float* __restrict__ dY, int64_t lddy,
-                                                          float* __restrict__ dZ, int64_t lddz, float alpha) {
-    ROW_LOOP_HEADER {
+__device__ __forceinline__ void softmax_bwd_rows(int vb, int nvb, int64_t rows, int d, const float* __restrict__ Y, int64_t ldy,
+                                                 const float* __restrict__ dY, int64_t lddy, float* __restrict__ dZ, int64_t lddz, float alpha) {
+    ROW_LOOP_HEADER(vb, nvb) {
         RowReg<VEC, NCHUNK> y, g;
         y.load(Y + row * ldy, gl, d);
         g.load(dY + row * lddy, gl, d);
@@ -112,6 +113,13 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(int64_t rows, int d, c
             for (int q = 0; q < VEC; ++q) g.x[k][q] = y.x[k][q] * (g.x[k][q] - dot);
         g.store(dZ + row * lddz, gl, d);
     }
+}
+
+template <int VEC, int NCHUNK>
+__global__ __launch_bounds__(256) void softmax_bwd_kernel(int64_t rows, int d, const float* __restrict__ Y, int64_t ldy,
+                                                          const float* __restrict__ dY, int64_t lddy,
+                                                          float* __restrict__ dZ, int64_t lddz, float alpha) {
+    softmax_bwd_rows<VEC, NCHUNK>((int)blockIdx.x, (int)gridDim.x, rows, d, Y, ldy, dY, lddy, dZ, lddz, alpha);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -135,7 +143,7 @@ struct FuseArgs {
 
 template <int VEC, int NCHUNK>
 __global__ __launch_bounds__(256) void fuse_fwd_kernel(int64_t rows, int d, FuseArgs a, float* __restrict__ out, int64_t ldo) {
-    ROW_LOOP_HEADER {
+    ROW_LOOP_HEADER(blockIdx.x, gridDim.x) {
         RowReg<VEC, NCHUNK> acc, t;
         acc.fill(0.f);
         for (int i = 0; i < a.n_mean; ++i) {
@@ -165,7 +173,7 @@ __global__ __launch_bounds__(256) void fuse_fwd_kernel(int64_t rows, int d, Fuse
 template <int VEC, int NCHUNK>
 __global__ __launch_bounds__(256) void fuse_bwd_kernel(int64_t rows, int d, FuseArgs a, const float* __restrict__ dOut,
                                                        int64_t lddo, int accumulate) {
-    ROW_LOOP_HEADER {
+    ROW_LOOP_HEADER(blockIdx.x, gridDim.x) {
         RowReg<VEC, NCHUNK> g, t, o;
         g.load(dOut + row * lddo, gl, d);
         for (int i = 0; i < a.n_norm; ++i) {
@@ -216,13 +224,13 @@ struct FuseMulti {
     int n_sumsq;                                                              // forward: the first n_sumsq norm terms' squared norms are summed
     float* sumsq_partial;                                                     // ... into one partial per block [gridDim.x]
 };
-#define ROW_LOOP_MULTI(m)                                                                          \
-    const int prob = (int)blockIdx.x >= (m).block_begin ? 1 : 0;                                   \
+#define ROW_LOOP_MULTI(m, vb, nvb)                                                                 \
+    const int prob = (vb) >= (m).block_begin ? 1 : 0;                                              \
     const FuseArgs& a = (m).a[prob];                                                               \
     const int64_t rows = (m).rows[prob];                                                           \
     const int gl = threadIdx.x & (RL - 1);                                                         \
-    const int blk = (int)blockIdx.x - (prob ? (m).block_begin : 0);                                \
-    const int nblk = prob ? (int)gridDim.x - (m).block_begin : (m).block_begin;                    \
+    const int blk = (vb) - (prob ? (m).block_begin : 0);                                           \
+    const int nblk = prob ? (nvb) - (m).block_begin : (m).block_begin;                             \
     const int64_t row_stride = (int64_t)nblk * ROWS_PER_BLOCK;                                     \
     for (int64_t row = (int64_t)blk * ROWS_PER_BLOCK + threadIdx.x / RL; row < rows; row += row_stride)
 
@@ -230,7 +238,7 @@ template <int VEC, int NCHUNK>
 __global__ __launch_bounds__(256) void fuse_fwd_multi_kernel(int d, FuseMulti m) {
     __shared__ float ss_red[256];
     float ss = 0.f;                                                     // this thread's share of sum ||x||^2 over the first n_sumsq terms
-    ROW_LOOP_MULTI(m) {
+    ROW_LOOP_MULTI(m, (int)blockIdx.x, (int)gridDim.x) {
         RowReg<VEC, NCHUNK> acc, t;
         acc.fill(0.f);
         for (int i = 0; i < a.n_mean; ++i) {
@@ -270,8 +278,8 @@ __global__ __launch_bounds__(256) void fuse_fwd_multi_kernel(int d, FuseMulti m)
 
 // (accumulate == 2 semantics of fuse_bwd_kernel: d_terms[t] = s_terms[t] (or 0) + the term's gradient)
 template <int VEC, int NCHUNK>
-__global__ __launch_bounds__(256) void fuse_bwd_src_multi_kernel(int d, FuseMulti m) {
-    ROW_LOOP_MULTI(m) {
+__device__ __forceinline__ void fuse_bwd_src_multi_rows(int vb, int nvb, int d, const FuseMulti& m) {
+    ROW_LOOP_MULTI(m, vb, nvb) {
         RowReg<VEC, NCHUNK> g, t, o;
         if (m.row_flags[prob] && !(m.row_stamp[prob] ? m.row_flags[prob][row] == LLMREC_ROW_STAMP(m.row_stamp[prob][0]) : m.row_flags[prob][row] != 0)) {
             // a row the batch did not touch: dOut = 0 and the sources are 0, so every stream's gradient is w (0 - x 0) = +0 and
@@ -320,6 +328,11 @@ __global__ __launch_bounds__(256) void fuse_bwd_src_multi_kernel(int d, FuseMult
             o.store(dst, gl, d);
         }
     }
+}
+
+template <int VEC, int NCHUNK>
+__global__ __launch_bounds__(256) void fuse_bwd_src_multi_kernel(int d, FuseMulti m) {
+    fuse_bwd_src_multi_rows<VEC, NCHUNK>((int)blockIdx.x, (int)gridDim.x, d, m);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -413,7 +426,9 @@ struct AdamwTensors {
     int32_t block_begin[LLMREC_ADAMW_MAX_TENSORS + 1];
     int32_t n_tensors;
 };
-constexpr int ADAMW_PER_BLOCK = 256 * 16;
+constexpr int ADAMW_PER_BLOCK = LLMREC_ADAMW_CHUNK;       // elements per block: ADAMW_VPT float4 per thread on the wide path
+constexpr int ADAMW_VPT = ADAMW_PER_BLOCK / 1024;
+static_assert(ADAMW_VPT >= 1 && ADAMW_PER_BLOCK % 1024 == 0, "an AdamW chunk is whole float4 rounds of a 256-thread block");
 
 struct ZeroRowJobs {
     const int64_t* ids[LLMREC_ZERO_ROWS_MAX_JOBS];
@@ -424,18 +439,84 @@ struct ZeroRowJobs {
     const int32_t* n_valid;
 };
 
-__device__ __forceinline__ void adamw_block(const AdamwTensors& t, const float* __restrict__ state, float decay_mul, float b1, float b2, float eps);
+struct AdamwConsts { float decay_mul, b2, eps, step_size, bc2s, w1, w2; };
 
-// all parameters of the model in one launch: block -> (tensor, 4096-element chunk)
+// THE update of one element of a multi-tensor launch (gi = the gradient the update uses): the scalar and the float4 path of adamw_block
+// both call it. Contraction is OFF inside: the compiler fuses a * b + c into an fma where it pays - for the packed two-float
+// instructions the float4 path is compiled to, not for the scalar ones of adamw_kernel and of the weight-gradient reduction's update
+// (dense.hip), which round the product first. Only the fmaf below is fused, everywhere.
+__device__ __forceinline__ void adamw_element(const AdamwConsts& c, float gi, float& p, float& m, float& v) {
+#pragma clang fp contract(off)
+    float pi = p * c.decay_mul;
+    const float mi = m + c.w1 * (gi - m);
+    const float vi = fmaf(c.w2 * gi, gi, v * c.b2);
+    const float denom = sqrtf(vi) / c.bc2s + c.eps;
+    pi = pi - c.step_size * (mi / denom);
+    p = pi; m = mi; v = vi;
+}
+__device__ __forceinline__ float adamw_grad(float gs, float g) { return gs == 1.0f ? g : gs * g; }
+
+// block vb of a multi-tensor update -> (tensor, ADAMW_PER_BLOCK-element chunk). A chunk that lies inside the tensor and whose five pointers
+// are 16-byte aligned moves as float4 - every load of the thread issued before the first arithmetic; the tensor's tail chunk and
+// misaligned views take the 4-byte loop.
+__device__ __forceinline__ void adamw_block(int vb, const AdamwTensors& t, const float* __restrict__ state, float decay_mul, float b1, float b2, float eps) {
+    int k = 0;
+    while (k + 1 < t.n_tensors && vb >= t.block_begin[k + 1]) ++k;
+    const int64_t base = (int64_t)(vb - t.block_begin[k]) * ADAMW_PER_BLOCK;
+    float* __restrict__ p = t.p[k]; const float* __restrict__ g = t.g[k];
+    float* __restrict__ m = t.m[k]; float* __restrict__ v = t.v[k];
+    const int64_t n = t.n[k];
+    const float gs = t.gscale[k];
+    float* __restrict__ go = t.gout[k];
+    AdamwConsts c;
+    c.decay_mul = decay_mul; c.b2 = b2; c.eps = eps;
+    c.step_size = state[1]; c.bc2s = state[2];
+    c.w1 = 1.0f - b1; c.w2 = 1.0f - b2;
+    const bool wide = base + ADAMW_PER_BLOCK <= n &&
+                      (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)go) & 15) == 0;
+    if (wide) {                                                        // (uniform over the block)
+        float4 P[ADAMW_VPT], G[ADAMW_VPT], M[ADAMW_VPT], V[ADAMW_VPT];
+#pragma unroll
+        for (int j = 0; j < ADAMW_VPT; ++j) {
+            const int64_t i = base + (int64_t)(j * 256 + (int)threadIdx.x) * 4;
+            P[j] = *reinterpret_cast<const float4*>(p + i); G[j] = *reinterpret_cast<const float4*>(g + i);
+            M[j] = *reinterpret_cast<const float4*>(m + i); V[j] = *reinterpret_cast<const float4*>(v + i);
+        }
+#pragma unroll
+        for (int j = 0; j < ADAMW_VPT; ++j) {
+            const int64_t i = base + (int64_t)(j * 256 + (int)threadIdx.x) * 4;
+            G[j].x = adamw_grad(gs, G[j].x); G[j].y = adamw_grad(gs, G[j].y); G[j].z = adamw_grad(gs, G[j].z); G[j].w = adamw_grad(gs, G[j].w);
+            if (go) *reinterpret_cast<float4*>(go + i) = G[j];
+            adamw_element(c, G[j].x, P[j].x, M[j].x, V[j].x);
+            adamw_element(c, G[j].y, P[j].y, M[j].y, V[j].y);
+            adamw_element(c, G[j].z, P[j].z, M[j].z, V[j].z);
+            adamw_element(c, G[j].w, P[j].w, M[j].w, V[j].w);
+            *reinterpret_cast<float4*>(p + i) = P[j]; *reinterpret_cast<float4*>(m + i) = M[j]; *reinterpret_cast<float4*>(v + i) = V[j];
+        }
+        return;
+    }
+#pragma unroll 4
+    for (int j = 0; j < ADAMW_PER_BLOCK / 256; ++j) {
+        const int64_t i = base + j * 256 + threadIdx.x;
+        if (i >= n) break;
+        const float gi = adamw_grad(gs, g[i]);
+        if (go) go[i] = gi;
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(c, gi, pi, mi, vi);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+}
+
+// all parameters of the model in one launch: block -> (tensor, chunk)
 __global__ __launch_bounds__(256) void adamw_multi_kernel(AdamwTensors t, const float* __restrict__ state, float decay_mul,
                                                           float b1, float b2, float eps) {
-    adamw_block(t, state, decay_mul, b1, b2, eps);
+    adamw_block((int)blockIdx.x, t, state, decay_mul, b1, b2, eps);
 }
 
 // the same + the row-wise clean-up of the step's scatter targets in the trailing blocks (llmrec_adamw_multi_zero_rows_f32)
 __global__ __launch_bounds__(256) void adamw_multi_zero_rows_kernel(AdamwTensors t, const float* __restrict__ state, float decay_mul,
                                                                     float b1, float b2, float eps, ZeroRowJobs z) {
-    if ((int)blockIdx.x < z.first_block) { adamw_block(t, state, decay_mul, b1, b2, eps); return; }
+    if ((int)blockIdx.x < z.first_block) { adamw_block((int)blockIdx.x, t, state, decay_mul, b1, b2, eps); return; }
     const int rel = (int)blockIdx.x - z.first_block;
     const int job = rel / z.blocks_per_job, blk = rel - job * z.blocks_per_job;
     int B = z.n_valid ? z.n_valid[0] : z.B_cap;
@@ -447,30 +528,19 @@ __global__ __launch_bounds__(256) void adamw_multi_zero_rows_kernel(AdamwTensors
     for (int c = gl; c < z.d[job]; c += 16) row[c] = 0.f;
 }
 
-__device__ __forceinline__ void adamw_block(const AdamwTensors& t, const float* __restrict__ state, float decay_mul, float b1, float b2, float eps) {
-    int k = 0;
-    while (k + 1 < t.n_tensors && (int)blockIdx.x >= t.block_begin[k + 1]) ++k;
-    const int64_t base = (int64_t)(blockIdx.x - t.block_begin[k]) * ADAMW_PER_BLOCK;
-    float* __restrict__ p = t.p[k]; const float* __restrict__ g = t.g[k];
-    float* __restrict__ m = t.m[k]; float* __restrict__ v = t.v[k];
-    const int64_t n = t.n[k];
-    const float gs = t.gscale[k];
-    float* __restrict__ go = t.gout[k];
-    const float step_size = state[1], bc2s = state[2];
-    const float w1 = 1.0f - b1, w2 = 1.0f - b2;
-#pragma unroll 4
-    for (int j = 0; j < 16; ++j) {
-        const int64_t i = base + j * 256 + threadIdx.x;
-        if (i >= n) break;
-        const float gi = gs == 1.0f ? g[i] : gs * g[i];
-        if (go) go[i] = gi;
-        float pi = p[i] * decay_mul;
-        const float mi = m[i] + w1 * (gi - m[i]);
-        const float vi = fmaf(w2 * gi, gi, v[i] * b2);
-        const float denom = sqrtf(vi) / bc2s + eps;
-        pi = pi - step_size * (mi / denom);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-    }
+// ---------------------------------------------------------------------------------------------
+// the step's three independent row sweeps behind the loss backward as ONE launch (llmrec_step_rows_group_f32): blocks
+// [0, adamw_begin) run the fusion backward, [adamw_begin, softmax_begin) the multi-tensor AdamW, the rest the softmax backward - each
+// the body of its own kernel, with the block's position inside the member's range. No member writes what another reads.
+// ---------------------------------------------------------------------------------------------
+struct SoftmaxBwdArgs { int64_t rows; const float* Y; int64_t ldy; const float* dY; int64_t lddy; float* dZ; int64_t lddz; float alpha; int d; };
+
+__global__ __launch_bounds__(256) void step_rows_group_kernel(int d, FuseMulti m, AdamwTensors t, const float* __restrict__ state, float decay_mul,
+                                                              float b1, float b2, float eps, SoftmaxBwdArgs s, int adamw_begin, int softmax_begin) {
+    const int b = (int)blockIdx.x;
+    if (b < adamw_begin) fuse_bwd_src_multi_rows<4, 1>(b, adamw_begin, d, m);
+    else if (b < softmax_begin) adamw_block(b - adamw_begin, t, state, decay_mul, b1, b2, eps);
+    else softmax_bwd_rows<4, 1>(b - softmax_begin, (int)gridDim.x - softmax_begin, s.rows, s.d, s.Y, s.ldy, s.dY, s.lddy, s.dZ, s.lddz, s.alpha);
 }
 
 template <typename F4, typename F1>
@@ -921,11 +991,10 @@ int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_pr
     return LLMREC_OK;
 }
 
-int llmrec_fuse_bwd_src_multi_f32(int32_t n_problems, const llmrec_fuse_bwd_problem_t* p, int32_t d, llmrec_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// the argument block of the paired fusion backward: m, whether every pointer / ld allows 16-byte accesses, and the block count
+static int fill_fuse_bwd_multi(int32_t n_problems, const llmrec_fuse_bwd_problem_t* p, int32_t d, FuseMulti& m, bool& vec4, int& grid) {
     LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= FUSE_MAX_PROBLEMS && p && d > 0, "fuse_bwd_src_multi: 1..%d problems", FUSE_MAX_PROBLEMS);
-    FuseMulti m = {};
-    bool vec4 = d % 4 == 0;
+    vec4 = d % 4 == 0;
     int blocks[FUSE_MAX_PROBLEMS] = {0, 0};
     for (int k = 0; k < n_problems; ++k) {
         const llmrec_fuse_bwd_problem_t& q = p[k];
@@ -949,7 +1018,16 @@ int llmrec_fuse_bwd_src_multi_f32(int32_t n_problems, const llmrec_fuse_bwd_prob
         blocks[k] = grid_for(q.rows, ROWS_PER_BLOCK);
     }
     m.block_begin = blocks[0];
-    const int grid = blocks[0] + blocks[1];
+    grid = blocks[0] + blocks[1];
+    return LLMREC_OK;
+}
+
+int llmrec_fuse_bwd_src_multi_f32(int32_t n_problems, const llmrec_fuse_bwd_problem_t* p, int32_t d, llmrec_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    FuseMulti m = {};
+    bool vec4 = false;
+    int grid = 0;
+    if (int rc = fill_fuse_bwd_multi(n_problems, p, d, m, vec4, grid)) return rc;
     if (grid == 0) return LLMREC_OK;
     int rc = dispatch_rows(d, vec4,
         [&](auto nc) { fuse_bwd_src_multi_kernel<4, decltype(nc)::value><<<grid, 256, 0, stream>>>(d, m); return 0; },
@@ -1057,6 +1135,46 @@ int llmrec_adamw_multi_zero_rows_f32(int32_t n_tensors, const llmrec_adamw_tenso
     if (total == 0) return LLMREC_OK;
     const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
     adamw_multi_zero_rows_kernel<<<total, 256, 0, (hipStream_t)stream_>>>(t, state3, decay_mul, beta1, beta2, eps, z);
+    LLMREC_LAUNCH_CHECK();
+    return LLMREC_OK;
+}
+
+int llmrec_step_rows_group_f32(int32_t n_fuse_problems, const llmrec_fuse_bwd_problem_t* fuse_host, int32_t d,
+                               int32_t n_tensors, const llmrec_adamw_tensor_t* tensors_host, const float* state3,
+                               float lr, float beta1, float beta2, float eps, float weight_decay,
+                               int64_t sm_rows, int32_t sm_d, float sm_alpha, const float* sm_Y, int64_t sm_ldy, const float* sm_dY, int64_t sm_lddy,
+                               float* sm_dZ, int64_t sm_lddz, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(n_fuse_problems >= 0 && n_tensors >= 0 && sm_rows >= 0, "step_rows_group: negative count");
+    FuseMulti m = {};
+    bool fuse_vec4 = true;
+    int fuse_blocks = 0;
+    if (n_fuse_problems > 0)
+        if (int rc = fill_fuse_bwd_multi(n_fuse_problems, fuse_host, d, m, fuse_vec4, fuse_blocks)) return rc;
+    AdamwTensors t = {};
+    int adamw_blocks = 0;
+    if (n_tensors > 0)
+        if (int rc = fill_adamw(t, n_tensors, tensors_host, state3, adamw_blocks)) return rc;
+    SoftmaxBwdArgs s = {};
+    int sm_blocks = 0;
+    bool sm_vec4 = true;
+    if (sm_rows > 0) {
+        LLMREC_CHECK_ARG(sm_d > 0 && sm_Y && sm_dY && sm_dZ && sm_ldy >= sm_d && sm_lddy >= sm_d && sm_lddz >= sm_d,
+                         "step_rows_group: softmax backward: null pointer or ld < d");
+        sm_vec4 = sm_d % 4 == 0 && sm_ldy % 4 == 0 && sm_lddy % 4 == 0 && sm_lddz % 4 == 0 && aligned16(sm_Y) && aligned16(sm_dY) && aligned16(sm_dZ);
+        s.rows = sm_rows; s.d = sm_d; s.alpha = sm_alpha;
+        s.Y = sm_Y; s.ldy = sm_ldy; s.dY = sm_dY; s.lddy = sm_lddy; s.dZ = sm_dZ; s.lddz = sm_lddz;
+        sm_blocks = grid_for(sm_rows, ROWS_PER_BLOCK);
+    }
+    // the one instance the step runs: 16-byte accesses, rows of at most 64 columns (<4, 1>); anything else: the caller's separate launches
+    if ((fuse_blocks > 0 && !(fuse_vec4 && d <= 64)) || (sm_blocks > 0 && !(sm_vec4 && sm_d <= 64))) {
+        set_error("step_rows_group: only the 16-byte, d <= 64 row kernels are grouped (fusion d = %d, softmax d = %d)", d, sm_d);
+        return LLMREC_EUNSUPPORTED;
+    }
+    const int total = fuse_blocks + adamw_blocks + sm_blocks;
+    if (total == 0) return LLMREC_OK;
+    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    step_rows_group_kernel<<<total, 256, 0, (hipStream_t)stream_>>>(d, m, t, state3, decay_mul, beta1, beta2, eps, s, fuse_blocks,
+                                                                    fuse_blocks + adamw_blocks);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }

@@ -637,7 +637,11 @@ class FusedStep:
                 [self._side(self.sc_I, 0), self._side(self.sc_I, 1), None] + [self._side(self.sc_I, 2 + k) for k in range(len(self.keys))], self.flag_i)
         problem(arr[1], self.dE_u, self.U_cat, self.prof_u, self.dU_cat, self.dprof_u,
                 [self._side(self.sc_U, 0), self._side(self.sc_U, 1), self.sc_prof] + [None] * len(self.keys), self.flag_u)
-        _call("llmrec_fuse_bwd_src_multi_f32", 2, arr, d)
+        # one stream, folded step: the fusion backward, the user table's AdamW and the ID chain's first softmax backward are independent
+        # and adjacent - ONE launch (chain_head, llmrec_step_rows_group_f32) instead of three that each wait for the one before
+        rows_group = not self.multi_stream and self.fold
+        if not rows_group:
+            _call("llmrec_fuse_bwd_src_multi_f32", 2, arr, d)
         ev_fuse = self._mark()                                           # the fusion backward has read dE_u / dE_i
         m = self.m
         inv = 1.0 / (L + 1)
@@ -650,6 +654,20 @@ class FusedStep:
             # U^0 only enters the mean: the user table's gradient needs nothing else. It and the logged loss values go first: whatever
             # this stream still has queued when the weight-gradient GEMM takes every CU (about when the chain's last SpMM starts)
             # waits for the GEMM's blocks to retire and becomes the step's tail.
+            if rows_group:
+                # members: AdamW reads dE_u, writes the user table, its moments and its .grad; the fusion backward reads dE_u / dE_i, the
+                # cat / profile terms and the scatter sources, writes dU_cat / dI_cat / dprof_*; the softmax backward reads I_L and dE_i,
+                # writes tmpI. (The rows of dE_* are cleared later, in the item table's launch.)
+                sources = {self._emb_params[0]: (self.dE_u, inv)}
+                sm = (self.Il[L - 1], self.dE_i, self.tmpI, inv) if L >= 1 else None
+                if not self.opt.step_params_rows_group(self._emb_params[:1], sources, arr, d, sm):
+                    _call("llmrec_fuse_bwd_src_multi_f32", 2, arr, d)
+                    self.opt.step_params(self._emb_params[:1], sources=sources)
+                    if sm is not None:
+                        self._softmax_bwd(*sm[:3], alpha=inv)
+                if side_work is not None:
+                    side_work()
+                return
             if self.fold:                                                         # AdamW reads inv * dE_u and stores it as the table's .grad
                 self.opt.step_params(self._emb_params[:1], sources={self._emb_params[0]: (self.dE_u, inv)})
             else:

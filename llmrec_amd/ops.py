@@ -1004,6 +1004,29 @@ class FusedAdamW:
             st = self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
         return st
 
+    def _tensor_array(self, group, sources=None):
+        """(llmrec_adamw_tensor_t array, tensors to keep alive) of one launch's parameters."""
+        arr = (AdamwTensor * max(len(group), 1))()
+        keep = []
+        for i, p in enumerate(group):
+            st = self.state.get(p)
+            if st is None:
+                st = self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+            if not p.is_contiguous():
+                raise RuntimeError("FusedAdamW: contiguous parameters expected")
+            src = sources.get(p) if sources else None
+            if src is not None:
+                g, scale = src
+                if not g.is_contiguous() or g.numel() != p.numel() or not p.grad.is_contiguous():
+                    raise RuntimeError("FusedAdamW: a gradient source is a contiguous tensor of the parameter's size")
+                arr[i].g_scale, arr[i].g_out = float(scale) * float(self.grad_scale.get(p, 1.0)), p.grad.data_ptr()
+            else:
+                g = p.grad.contiguous()
+                arr[i].g_scale, arr[i].g_out = float(self.grad_scale.get(p, 1.0)), None
+            keep.append(g)
+            arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].n = p.data_ptr(), g.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), p.numel()
+        return arr, keep
+
     def _update(self, live, sources=None, zero_rows=None):
         if not live and zero_rows is None:
             return
@@ -1013,25 +1036,7 @@ class FusedAdamW:
             raise RuntimeError("FusedAdamW: the clean-up rides with at most %d tensors" % cap)
         for lo in range(0, max(len(live), 1), cap):
             group = live[lo:lo + cap]
-            arr = (AdamwTensor * max(len(group), 1))()
-            keep = []
-            for i, p in enumerate(group):
-                st = self.state.get(p)
-                if st is None:
-                    st = self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
-                if not p.is_contiguous():
-                    raise RuntimeError("FusedAdamW: contiguous parameters expected")
-                src = sources.get(p) if sources else None
-                if src is not None:
-                    g, scale = src
-                    if not g.is_contiguous() or g.numel() != p.numel() or not p.grad.is_contiguous():
-                        raise RuntimeError("FusedAdamW: a gradient source is a contiguous tensor of the parameter's size")
-                    arr[i].g_scale, arr[i].g_out = float(scale) * float(self.grad_scale.get(p, 1.0)), p.grad.data_ptr()
-                else:
-                    g = p.grad.contiguous()
-                    arr[i].g_scale, arr[i].g_out = float(self.grad_scale.get(p, 1.0)), None
-                keep.append(g)
-                arr[i].p, arr[i].g, arr[i].m, arr[i].v, arr[i].n = p.data_ptr(), g.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), p.numel()
+            arr, keep = self._tensor_array(group, sources)
             if zero_rows is None:
                 _lib.call("llmrec_adamw_multi_f32", len(group), arr, _p(self.dev_state), self.lr, self.betas[0], self.betas[1],
                           self.eps, self.wd, _stream())
@@ -1046,6 +1051,28 @@ class FusedAdamW:
                     raise RuntimeError("FusedAdamW: advance() first")
                 _lib.call("llmrec_adamw_multi_zero_rows_f32", len(group), arr, _p(self.dev_state), self.lr, self.betas[0], self.betas[1],
                           self.eps, self.wd, len(jobs), jarr, int(b_cap), _p(n_valid), _stream())
+
+    @torch.no_grad()
+    def step_params_rows_group(self, params, sources, fuse_problems, d, softmax_bwd) -> bool:
+        """step_params(params, sources) in ONE launch with two row sweeps that are independent of it (llmrec_step_rows_group_f32):
+        fuse_problems = the FuseBwdProblem array of llmrec_fuse_bwd_src_multi_f32 (or None), softmax_bwd = (Y, dY, dZ, alpha) of
+        llmrec_softmax_rows_bwd_scaled_f32 (or None). False: the library refused the group (nothing was launched) - the caller issues
+        the three launches itself."""
+        live = [p for p in params if p.grad is not None]
+        if len(live) > CONST["LLMREC_ADAMW_MAX_TENSORS"]:
+            return False
+        _need_gpu(*live)
+        if live and self.dev_state is None:
+            raise RuntimeError("FusedAdamW: advance() first")
+        arr, keep = self._tensor_array(live, sources)
+        if softmax_bwd is not None:
+            Y, dY, dZ, alpha = softmax_bwd
+            sm = (Y.shape[0], Y.shape[1], float(alpha), _p(Y), _ld(Y), _p(dY), _ld(dY), _p(dZ), _ld(dZ))
+        else:
+            sm = (0, 0, 1.0, None, 0, None, 0, None, 0)
+        return _lib.call_unless_unsupported("llmrec_step_rows_group_f32", len(fuse_problems) if fuse_problems is not None else 0, fuse_problems,
+                                            int(d), len(live), arr, _p(self.dev_state), self.lr, self.betas[0], self.betas[1], self.eps,
+                                            self.wd, *sm, _stream())
 
 
 # ---------------------------------------------------------------------------------------------
