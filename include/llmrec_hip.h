@@ -664,7 +664,12 @@ int llmrec_step_rows_group_f32(int32_t n_fuse_problems, const llmrec_fuse_bwd_pr
  * K <= LLMREC_TOPK_MAX for the single-sweep calls (llmrec_score_topk_f32 / _ws_f32 / _mode_f32: every
  * selection structure of the sweeps is a 64-slot list, one slot per lane); llmrec_score_topk_wide_f32
  * (below) ranks up to LLMREC_TOPK_WIDE_MAX items per user by repeating the sweep over a growing mask.
- * d a multiple of 16 and <= 128.
+ * Tables: 1 <= d <= 128 (d > 128: LLMREC_EUNSUPPORTED, refused before anything is launched or
+ * written), any ld >= d, any 4-byte-aligned base - a column view of a wider table is fine.
+ * The sweeps' vector path (16-byte loads of the rows) needs ldu % 4 == 0, ldi % 4 == 0 and both
+ * bases 16-byte aligned, and the unguarded instances also d % 16 == 0; every other table goes
+ * through guarded loads that read nothing outside [row, row + d): the same bits (their speed
+ * is not measured). llmrec_score_auc_f32 alone needs d % 16 == 0.
  * ------------------------------------------------------------------------------------------ */
 #define LLMREC_TOPK_MAX 64
 int llmrec_score_topk_f32(int32_t n_query, const int64_t* query_users,
@@ -777,7 +782,8 @@ int llmrec_topk_eval_sums(int32_t n_query, const int64_t* query_users, int32_t K
  *     AUC_u = c2_u / (2 |P| |N|)                                                 (double)
  *     AUC_u = 0 if |P| == 0 or |N| == 0, or if some s_i with i in C is NaN or +-inf (then c2_u is reported as 0)
  * - what sklearn's roc_auc_score gives over the candidates, and 0 where it raises (utility/metrics.py auc).
- * Rows of both CSRs ascending (llmrec_csr_build); train may be null (nothing masked). d a multiple of 16, at most 128.
+ * Rows of both CSRs ascending (llmrec_csr_build); train may be null (nothing masked). d a multiple of 16, at most 128 (LLMREC_EINVAL otherwise);
+ * ld and base as for the top-K calls above.
  * Outputs, each optional: auc_out[n_query] (double), counts_out[n_query][3] = (c2, |P|, |N|) (int64), sum_out[1] = the sum of the
  * per-user AUCs by a fixed tree (device memory or mapped pinned host memory, as for llmrec_topk_eval_sums; the caller divides by n_query).
  * Integer counts and fixed-order sums: the results are deterministic. Four launches, capturable; no allocation. */

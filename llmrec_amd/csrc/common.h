@@ -18,6 +18,16 @@ void set_error(const char* fmt, ...);
         }                                                             \
     } while (0)
 
+// the evaluation sweeps (scores, top-K, wide rounds) have instances for up to 8 chunks of 16 columns; an entry refuses a wider table
+// next to its argument checks, before its first launch
+#define LLMREC_CHECK_EVAL_WIDTH(d)                                    \
+    do {                                                              \
+        if ((d) > 128) {                                              \
+            ::llmrec::set_error("score_topk: d = %d > 128", (int)(d)); \
+            return LLMREC_EUNSUPPORTED;                               \
+        }                                                             \
+    } while (0)
+
 #define LLMREC_HIP(call)                                                                   \
     do {                                                                                   \
         hipError_t e__ = (call);                                                           \

@@ -357,7 +357,8 @@ __global__ __launch_bounds__(256) void topk_pack_items_kernel(TopkArgs a, int DK
 
 // FAST: d == 16 DK and 16-byte aligned rows - plain float4 loads. (A branch around a global load makes
 // hipcc wait for each load before issuing the next: the guarded loader costs ~8 exposed L2 latencies per round.)
-// PACKED: the item tiles come from a.packed (fragment order, one contiguous KB per load instruction).
+// PACKED: the item tiles come from a.packed (fragment order, one contiguous KB per load instruction). The user rows are still
+// read from Eu: <DK, false, true> is the packed sweep of a ragged d or an unaligned table (its 16 user rows through ld4g, once).
 template <int DK, bool FAST, bool PACKED>
 __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(TopkArgs a) {
     __shared__ float buf_s[4][16][TK_CAP];
@@ -1264,6 +1265,7 @@ static bool plan_parts(int n_query, int64_t n_items, int d, int* n_parts) {
 
 template <bool SELECT>
 static int launch_topk(const TopkArgs& a, hipStream_t stream) {
+    LLMREC_CHECK_EVAL_WIDTH(a.d);                              // (the entries have refused it already: the switches below cover DK = 1..8)
     const int DK = (a.d + 15) / 16;
     const int n_tiles = (int)ceil_div(a.n_query, 16);
     const int grid = (int)(a.split_from + (int64_t)(n_tiles - a.split_from) * a.n_parts);
@@ -1284,7 +1286,6 @@ static int launch_topk(const TopkArgs& a, hipStream_t stream) {
             case 2: score_topk_pre_kernel<2><<<grid, 256, 0, stream>>>(a, a.pk2, a.cn); break;
             case 3: score_topk_pre_kernel<3><<<grid, 256, 0, stream>>>(a, a.pk2, a.cn); break;
             case 4: score_topk_pre_kernel<4><<<grid, 256, 0, stream>>>(a, a.pk2, a.cn); break;
-            default: set_error("score_topk: d = %d > 128", a.d); return LLMREC_EUNSUPPORTED;
         }
         LLMREC_LAUNCH_CHECK();
         if (a.n_parts > 1) {
@@ -1302,7 +1303,6 @@ static int launch_topk(const TopkArgs& a, hipStream_t stream) {
         switch (DK) {
             LLMREC_TOPK_FB(1) LLMREC_TOPK_FB(2) LLMREC_TOPK_FB(3) LLMREC_TOPK_FB(4)
             LLMREC_TOPK_FB(5) LLMREC_TOPK_FB(6) LLMREC_TOPK_FB(7) LLMREC_TOPK_FB(8)
-            default: set_error("score_topk: d = %d > 128", a.d); return LLMREC_EUNSUPPORTED;
         }
 #undef LLMREC_TOPK_FB
         LLMREC_LAUNCH_CHECK();
@@ -1315,14 +1315,14 @@ static int launch_topk(const TopkArgs& a, hipStream_t stream) {
     }
 #define LLMREC_TOPK_CASE(D) case D: \
         if (!SELECT) scores_kernel<D><<<grid, 256, 0, stream>>>(a); \
-        else if (a.packed) score_topk_kernel<D, true, true><<<grid, 256, 0, stream>>>(a); \
+        else if (a.packed && fast) score_topk_kernel<D, true, true><<<grid, 256, 0, stream>>>(a); \
+        else if (a.packed) score_topk_kernel<D, false, true><<<grid, 256, 0, stream>>>(a); \
         else if (fast) score_topk_kernel<D, true, false><<<grid, 256, 0, stream>>>(a); \
         else score_topk_kernel<D, false, false><<<grid, 256, 0, stream>>>(a); \
         break;
     switch (DK) {
         LLMREC_TOPK_CASE(1) LLMREC_TOPK_CASE(2) LLMREC_TOPK_CASE(3) LLMREC_TOPK_CASE(4)
         LLMREC_TOPK_CASE(5) LLMREC_TOPK_CASE(6) LLMREC_TOPK_CASE(7) LLMREC_TOPK_CASE(8)
-        default: set_error("score_topk: d = %d > 128", a.d); return LLMREC_EUNSUPPORTED;
     }
 #undef LLMREC_TOPK_CASE
     LLMREC_LAUNCH_CHECK();
@@ -1691,6 +1691,7 @@ int llmrec_score_topk_mode_f32(int32_t n_query, const int64_t* query_users,
     LLMREC_CHECK_ARG(query_users && Eu && Ei && out_idx && out_score && ldu >= d && ldi >= d, "score_topk: null pointer or ld < d");
     LLMREC_CHECK_ARG((train_rowptr == nullptr) == (train_colidx == nullptr) || train_rowptr, "score_topk: train CSR incomplete");
     LLMREC_CHECK_ARG(n_items < (1ll << 31), "score_topk: n_items exceeds int32 item ids");
+    LLMREC_CHECK_EVAL_WIDTH(d);                                // (before the pack / norm launches touch the workspace)
     TopkArgs a;
     a.n_query = n_query; a.query_users = query_users; a.Eu = Eu; a.ldu = ldu; a.Ei = Ei; a.ldi = ldi;
     a.n_items = n_items; a.d = d; a.train_rowptr = train_rowptr; a.train_colidx = train_colidx; a.K = K;
@@ -1739,6 +1740,7 @@ int llmrec_scores_f32(int32_t n_query, const int64_t* query_users,
     LLMREC_CHECK_ARG(n_query >= 0 && n_items > 0 && d > 0, "scores: bad sizes");
     if (n_query == 0) return LLMREC_OK;
     LLMREC_CHECK_ARG(query_users && Eu && Ei && S && ldu >= d && ldi >= d && lds >= n_items, "scores: null pointer or ld too small");
+    LLMREC_CHECK_EVAL_WIDTH(d);
     TopkArgs a;
     a.n_query = n_query; a.query_users = query_users; a.Eu = Eu; a.ldu = ldu; a.Ei = Ei; a.ldi = ldi;
     a.n_items = n_items; a.d = d; a.train_rowptr = nullptr; a.train_colidx = nullptr; a.K = 1;

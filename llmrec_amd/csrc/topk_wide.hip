@@ -295,6 +295,7 @@ int llmrec_score_topk_wide_f32(int32_t n_query, const int64_t* query_users,
     LLMREC_CHECK_ARG(query_users && Eu && Ei && out_idx && out_score && ldu >= d && ldi >= d, "score_topk_wide: null pointer or ld < d");
     LLMREC_CHECK_ARG((train_rowptr == nullptr) == (train_colidx == nullptr), "score_topk_wide: train CSR incomplete");
     LLMREC_CHECK_ARG(n_items < (1ll << 31), "score_topk_wide: n_items exceeds int32 item ids");
+    LLMREC_CHECK_EVAL_WIDTH(d);                                // (before the gather and the mask launches of the rounds)
     if (workspace) {
         const int64_t need = llmrec_score_topk_wide_workspace_bytes(n_query, n_items, d, K, K > LLMREC_TOPK_MAX && train_nnz > 0 ? train_nnz : 0);
         if (need >= 0 && workspace_bytes < need) {
