@@ -216,6 +216,7 @@ class FusedStep:
             self.ss_cap = 2 * 2048                                # >= the fusion launch's grid (two problems, <= 2048 blocks each)
             self.ss_partial = torch.zeros(self.ss_cap, dtype=torch.float32, device=dev)
             self.ss_n = 0
+        self._ev_plan = self._ev_reach = None                 # four streams: the scatter plan / the row list are ready (step_eager)
         self._zero_in_forward = False                         # set by step_eager: forward() alone (evaluation) must not advance AdamW
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
@@ -295,6 +296,10 @@ class FusedStep:
               _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),
               _c.byref(epilogue) if epilogue is not None else None)
 
+    def _spmm_jobs(self, jobs):
+        for a, X, Y, kw in jobs:
+            self._spmm(a, X, Y, **kw)
+
     def _spmm_group(self, jobs):
         """Independent products [(a, X, Y, kwargs of _spmm)] in ONE llmrec_spmm_multi_f32 launch, longest first (one stream: each of these
         latency-bound products alone leaves most CUs idle). Separate launches when the group has one product, when a graph is in the
@@ -302,9 +307,7 @@ class FusedStep:
         either way: a row's summation tree does not depend on the launch it runs in."""
         jobs = [j for j in jobs if j is not None]
         if len(jobs) == 1 or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs):
-            for a, X, Y, kw in jobs:
-                self._spmm(a, X, Y, **kw)
-            return
+            return self._spmm_jobs(jobs)
         order = sorted(jobs, key=lambda j: -j[0].nnz * j[1].shape[1])             # (stable)
         probs, keep = [], []
         for a, X, Y, kw in order:
@@ -316,9 +319,7 @@ class FusedStep:
                                           ops._ptr(a.col_scale), X.data_ptr(), _ld(X), Y.data_ptr(), _ld(Y), X.shape[1], sw,
                                           _c.addressof(pc), ops._ptr(partials), _c.addressof(epi) if epi is not None else None))
         if not ops.spmm_multi(probs):
-            for a, X, Y, kw in jobs:
-                self._spmm(a, X, Y, **kw)
-            return
+            return self._spmm_jobs(jobs)
         for a, X, _, _ in jobs:
             self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
 
@@ -349,7 +350,7 @@ class FusedStep:
             feats, roww = self.AX, self.a_rowsum
         else:
             feats, roww = [m.image_feats, m.text_feats] + [m.item_feats[key] for key in self.keys], None
-        rows = (self.act_rows, self.act_n, self.act_expected) if (self.wgrad_rows and self.gemm == "bf16x3") else None
+        rows = (self.act_rows, self.act_n, self.act_expected) if self.wgrad_rows else None
         item_pairs = [(self._side(dY_cat, 2 + k), feats[2 + k], roww, rows) for k in range(len(self.keys))]
         return [(item_pairs, m.item_trans.weight.grad, m.item_trans.bias.grad, False),
                 ([(dP_usr, m.user_feats)], m.user_trans.weight.grad, m.user_trans.bias.grad, False),
@@ -470,24 +471,13 @@ class FusedStep:
 
     def _forward_streams(self, sampler, after_chain, profile_on_main):
         """The forward's products on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule)."""
-        m = self.m
         self._fork(self.s2)
         with self._on(self.s2):                                          # ID chain: needs no projection
             if sampler is not None:                                      # the batch is first read by the losses, after the join below:
                 sampler()                                                # sampling rides beside the projection instead of ahead of it
             if self._zero_in_forward and not self.fold:
                 self.opt.advance()                                       # AdamW's step counter / bias corrections, off the critical path
-            i_prev = m.item_id_embedding.weight
-            for l in range(self.L):
-                last = l == self.L - 1
-                if last:                                                 # row softmax of the last layer = the SpMM's epilogue
-                    sm = ops.spmm_epilogue(ops.EPI_SOFTMAX)
-                    self._spmm(self.ui.fwd, i_prev, self.Ul[l], tag=2, epilogue=sm)
-                    self._spmm(self.iu.fwd, self.Ul[l], self.Il[l], tag=2, epilogue=sm)
-                else:
-                    self._spmm(self.ui.fwd, i_prev, self.Ul[l], tag=2)
-                    self._spmm(self.iu.fwd, self.Ul[l], self.Il[l], tag=2)
-                i_prev = self.Il[l]
+            self._spmm_jobs(self._chain_fwd_jobs())
             ev_chain = self._mark() if after_chain is not None else None     # the chain's SpMMs are done; what follows on this stream
             if after_chain is not None:                                      # is not needed by the fusion
                 after_chain()
@@ -548,7 +538,7 @@ class FusedStep:
         # critical path: scores -> [selection + gradient rows] (two launches); the loss VALUES (one more launch) and their assembly for
         # the log line ride on the ID chain's stream (a branch of their own right behind the BPR launches: the graph ran it as the step's tail)
         self._check_scatter_targets()
-        if getattr(self, "_ev_plan", None) is not None:                  # (four streams: the plan was built behind the ID chain)
+        if self._ev_plan is not None:                                    # (four streams: the plan was built behind the ID chain)
             torch.cuda.current_stream().wait_event(self._ev_plan)
         # the scores launch begins the step (row stamp; folded: AdamW's counter too), the selection stamps the batch's rows
         if self.fold:
@@ -603,16 +593,23 @@ class FusedStep:
         replicated_scale weights the batch-independent loss terms (1 / world on batch-sharded replicas, whose
         gradients are summed over ranks afterwards). bpr_bwd_done: the loss launch already scattered the gradient rows.
         side_work: launches for the ID chain's stream, ahead of its last SpMM."""
-        hp, d, L, S = self.hp, self.d, self.L, self.S
-        B = users.numel()
-        coef = hp.feat_reg_decay * 0.5 / self.I * replicated_scale
+        hp = self.hp
         if not bpr_bwd_done:
             self._check_scatter_targets()
-            _call("llmrec_bpr_multi_bwd_f32", self.n_prob, probs, d, _p(users), _p(pos), _p(neg), B, _p(n_valid), float(hp.decay),
-                  float(hp.batch_size), _p(self.saved), _p(self.bpr_plan))
-        ev_rows = self._mark()                                           # dE_u / dE_i hold the scattered rows: all the ID chain needs
+            _call("llmrec_bpr_multi_bwd_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid),
+                  float(hp.decay), float(hp.batch_size), _p(self.saved), _p(self.bpr_plan))
+        # dE_u / dE_i hold the scattered rows now. (Only the fused loss launch stamps the rows it touched; keep: alive until the launch.)
+        fuse, keep = self._fuse_bwd_problems(hp.feat_reg_decay * 0.5 / self.I * replicated_scale, stamped=bpr_bwd_done)
+        schedule = self._backward_streams if self.multi_stream else self._backward_one_stream
+        schedule(probs, (users, pos, neg, n_valid), fuse, side_work)
+        self._weight_gradients()
+        self._join(self.s2)
+        if self.fold and side_work is not None:                          # (four streams: side_work ran on a stream of its own)
+            self._join(self.s3)
 
-        # the backward of both fusions in ONE launch (llmrec_fuse_bwd_src_multi_f32)
+    def _fuse_bwd_problems(self, coef: float, stamped: bool):
+        """The backward of both fusions as the two problems of ONE launch (llmrec_fuse_bwd_src_multi_f32) -> (problems, the arrays they
+        point into). stamped: the loss launch stamped the batch's rows; the others are written without being read."""
         keep = []
 
         def problem(pr, dout, cat, prof, dcat, dprof, srcs, flags):
@@ -630,139 +627,145 @@ class FusedStep:
             pr.d_terms, pr.d_ld = _c.cast(dp, _c.c_void_p), _c.cast(dl, _c.c_void_p)
             pr.src_terms, pr.src_ld = _c.cast(sp, _c.c_void_p), _c.cast(sl, _c.c_void_p)
             pr.n_reg_terms, pr.reg_two_coef = 2, float(2.0 * coef)
-            if flags is not None and bpr_bwd_done:                      # (only the fused loss launch stamps the rows)
+            if stamped:
                 pr.row_flags, pr.row_stamp = flags.data_ptr(), self.row_stamp.data_ptr()
         arr = (ops.FuseBwdProblem * 2)()
         problem(arr[0], self.dE_i, self.I_cat, self.prof_i, self.dI_cat, self.dprof_i,
                 [self._side(self.sc_I, 0), self._side(self.sc_I, 1), None] + [self._side(self.sc_I, 2 + k) for k in range(len(self.keys))], self.flag_i)
         problem(arr[1], self.dE_u, self.U_cat, self.prof_u, self.dU_cat, self.dprof_u,
                 [self._side(self.sc_U, 0), self._side(self.sc_U, 1), self.sc_prof] + [None] * len(self.keys), self.flag_u)
-        # one stream, folded step: the fusion backward, the user table's AdamW and the ID chain's first softmax backward are independent
-        # and adjacent - ONE launch (chain_head, llmrec_step_rows_group_f32) instead of three that each wait for the one before
-        rows_group = not self.multi_stream and self.fold
-        if not rows_group:
-            _call("llmrec_fuse_bwd_src_multi_f32", 2, arr, d)
-        ev_fuse = self._mark()                                           # the fusion backward has read dE_u / dE_i
-        m = self.m
-        inv = 1.0 / (L + 1)
-        # four streams, folded step: the critical transposed side product is captured BEFORE the two side branches and the logged-scalar
-        # launch gets a stream of its own (each alone lost, both together won: profiles/experiments/r05_step_chain.md)
-        main_first = self.multi_stream and self.fold
-        loss_s3 = self.multi_stream and self.fold and side_work is not None
+        return arr, keep
 
-        def chain_head():
-            # U^0 only enters the mean: the user table's gradient needs nothing else. It and the logged loss values go first: whatever
-            # this stream still has queued when the weight-gradient GEMM takes every CU (about when the chain's last SpMM starts)
-            # waits for the GEMM's blocks to retire and becomes the step's tail.
-            if rows_group:
-                # members: AdamW reads dE_u, writes the user table, its moments and its .grad; the fusion backward reads dE_u / dE_i, the
-                # cat / profile terms and the scatter sources, writes dU_cat / dI_cat / dprof_*; the softmax backward reads I_L and dE_i,
-                # writes tmpI. (The rows of dE_* are cleared later, in the item table's launch.)
-                sources = {self._emb_params[0]: (self.dE_u, inv)}
-                sm = (self.Il[L - 1], self.dE_i, self.tmpI, inv) if L >= 1 else None
-                if not self.opt.step_params_rows_group(self._emb_params[:1], sources, arr, d, sm):
-                    _call("llmrec_fuse_bwd_src_multi_f32", 2, arr, d)
-                    self.opt.step_params(self._emb_params[:1], sources=sources)
-                    if sm is not None:
-                        self._softmax_bwd(*sm[:3], alpha=inv)
-                if side_work is not None:
-                    side_work()
-                return
-            if self.fold:                                                         # AdamW reads inv * dE_u and stores it as the table's .grad
-                self.opt.step_params(self._emb_params[:1], sources={self._emb_params[0]: (self.dE_u, inv)})
-            else:
-                self._axpy(inv, self.dE_u, m.user_id_embedding.weight.grad, False)
-                if self.inline_adamw:                                             # U^0 only enters the mean: the user table's gradient is final here
-                    self.opt.step_params(self._emb_params[:1])
-            if side_work is not None:
-                side_work()
-            if L >= 1:                                                                    # dI[L] = inv dE_i (mean part), g = softmax_bwd(I_L, dI[L])
-                self._softmax_bwd(self.Il[L - 1], self.dE_i, self.tmpI, alpha=inv)
-
-        def chain_jobs():
-            # ID chain (items of layer l+1 from the new users; softmax on the last layer)
-            # every "+ mean term" and every softmax backward below is an epilogue of the SpMM that produces the tensor:
-            #   dI[L] = inv dE_i                      -> g = softmax_bwd(I_L, dI[L])            (one row kernel, no SpMM feeds it)
-            #   dU[l+1] = inv dE_u + A_iu^T g         -> h = softmax_bwd(U_L, dU[l+1]) on the last layer
-            #   dI[l]   = inv dE_i + A_ui^T h         -> (l > 0) feeds the next round as g; (l = 0) IS the item table's gradient
-            jobs, g = [], self.tmpI if L >= 1 else self.bufI
-            for l in range(L - 1, -1, -1):
-                if l == L - 1:
-                    jobs.append((self.iu.bwd, g, self.tmpU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, inv, self.dE_u, self.Ul[l]))))
-                    h = self.tmpU
-                else:
-                    jobs.append((self.iu.bwd, g, self.bufU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_u))))
-                    h = self.bufU
-                dst = m.item_id_embedding.weight.grad if l == 0 else self.bufI
-                jobs.append((self.ui.bwd, h, dst, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_i))))
-                g = self.bufI
-            return jobs
-
-        def chain_tail():
-            if L == 0:
-                self._axpy(inv, self.dE_i, m.item_id_embedding.weight.grad, False)
-            # after the last reader of dE_u / dE_i (this chain and the fusion backward): clear the touched rows. (The wait below is for
-            # an EARLY event. A wait for a late one anywhere in this stream's chain - e.g. for the transposed side product, had the row
-            # stamps needed a clean-up - makes the graph runtime start the WHOLE chain late: profiles/experiments/r03_wgrad.md, last table.)
-            if ev_fuse is not None:
-                torch.cuda.current_stream().wait_event(ev_fuse)
-            if self.fold and L > 0:                                               # clean-up + the item table's AdamW in ONE launch
-                jobs = [(users, self.dE_u), (pos, self.dE_i), (neg, self.dE_i), (users, self.sc_U), (pos, self.sc_I), (neg, self.sc_I),
-                        (users, self.sc_prof)]
-                self.opt.step_params(self._emb_params[1:], zero_rows=(jobs, B, n_valid))
-            else:
-                _call("llmrec_bpr_multi_zero_rows_f32", self.n_prob, probs, d, _p(users), _p(pos), _p(neg), B, _p(n_valid))
-                if self.inline_adamw:                                             # the item table's gradient is final: update it here,
-                    self.opt.step_params(self._emb_params[1:])                    # beside the weight-gradient GEMM
-
-        # side chain: I_cat = iu(U_cat), U_cat = ui(P_cat) (or the pre-propagated projection); profile chain: prof_u = ui(prof_i),
-        # prof_i = iu(P_usr) - user_trans' weight gradient joins the item-side ones below
-        side_jobs = [(self.iu.bwd, self.dI_cat, self.dU_cat, dict(accumulate=True))]
-        if not self.preprop:
-            side_jobs.append((self.ui.bwd, self.dU_cat, self.dP_cat, {}))
-        prof_jobs = [(self.ui.bwd, self.dprof_u, self.dprof_i, dict(accumulate=True, tag=1)), (self.iu.bwd, self.dprof_i, self.dP_usr, dict(tag=1))]
-        if not self.multi_stream:
-            # ONE stream: the k-th product of the ID chain, the side chain and the profile chain share a launch (_spmm_group)
-            chain_head()
-            chain = chain_jobs()
-            for k in range(max(len(chain), len(side_jobs), len(prof_jobs))):
-                self._spmm_group([c[k] if k < len(c) else None for c in (chain, side_jobs, prof_jobs)])
-            if self.gemm != "bf16x3":
-                self._wgrad(self.dP_usr, m.user_feats, m.user_trans, False, ws=self.ws_wgrad_b)
-            chain_tail()
+    def _chain_head(self, side_work, fuse=None):
+        """Head of the ID chain's backward: the user table's gradient and AdamW (U^0 only enters the mean: its gradient needs nothing else),
+        the logged scalars (side_work), the first softmax backward. The first two go first: whatever this stream still has queued when the
+        weight-gradient GEMM takes every CU (about when the chain's last SpMM starts) waits for its blocks to retire and becomes the step's tail.
+        fuse: the fusion backward's problems when it shares the head's launch (one stream, folded step): it, the AdamW and the softmax
+        backward are independent and adjacent - ONE launch (llmrec_step_rows_group_f32) instead of three that each wait for the one before."""
+        L, inv, user = self.L, 1.0 / (self.L + 1), self._emb_params[:1]
+        sources = {user[0]: (self.dE_u, inv)}                                     # AdamW reads inv * dE_u and stores it as the table's .grad
+        sm = (self.Il[L - 1], self.dE_i, self.tmpI, inv) if L >= 1 else None      # dI[L] = inv dE_i (mean part), g = softmax_bwd(I_L, dI[L])
+        if fuse is not None:
+            # members: AdamW reads dE_u, writes the user table, its moments and its .grad; the fusion backward reads dE_u / dE_i, the
+            # cat / profile terms and the scatter sources, writes dU_cat / dI_cat / dprof_*; the softmax backward reads I_L and dE_i,
+            # writes tmpI. (The rows of dE_* are cleared later, in the item table's launch.)
+            if not self.opt.step_params_rows_group(user, sources, fuse, self.d, sm):
+                _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
+                self.opt.step_params(user, sources=sources)
+                if sm is not None:
+                    self._softmax_bwd(*sm[:3], alpha=inv)
+        elif self.fold:
+            self.opt.step_params(user, sources=sources)
         else:
-            # four streams, folded step: the critical transposed side product is captured BEFORE the two side branches and the logged-scalar
-            # launch gets a stream of its own (each alone lost, both together won: profiles/experiments/r05_step_chain.md)
-            if main_first:
-                for job in side_jobs:
-                    self._spmm(job[0], job[1], job[2], **job[3])
-                self._fork_from(ev_fuse, self.s1)
+            self._axpy(inv, self.dE_u, user[0].grad, False)
+            if self.inline_adamw:                                                 # U^0 only enters the mean: the user table's gradient is final here
+                self.opt.step_params(user)
+        if side_work is not None:
+            side_work()
+        if fuse is None and sm is not None:                                       # (with fuse it ran above, in the group or right behind it)
+            self._softmax_bwd(*sm[:3], alpha=inv)
+
+    def _chain_bwd_jobs(self):
+        """The ID chain's 2 L transposed products [(a, X, Y, kwargs)] in dependency order (items of layer l+1 from the new users; softmax
+        on the last layer). Every "+ mean term" and every softmax backward is an epilogue of the SpMM that produces the tensor:
+          dI[L] = inv dE_i                      -> g = softmax_bwd(I_L, dI[L])            (one row kernel, no SpMM feeds it: _chain_head)
+          dU[l+1] = inv dE_u + A_iu^T g         -> h = softmax_bwd(U_L, dU[l+1]) on the last layer
+          dI[l]   = inv dE_i + A_ui^T h         -> (l > 0) feeds the next round as g; (l = 0) IS the item table's gradient"""
+        L, inv = self.L, 1.0 / (self.L + 1)
+        jobs, g = [], self.tmpI if L >= 1 else self.bufI
+        for l in range(L - 1, -1, -1):
+            if l == L - 1:
+                jobs.append((self.iu.bwd, g, self.tmpU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, inv, self.dE_u, self.Ul[l]))))
+                h = self.tmpU
             else:
-                self._fork(self.s1)
-            if loss_s3:
-                self._fork_from(ev_rows, self.s3)
-                with self._on(self.s3):
-                    side_work()
-                side_work = None
-            with self._on(self.s1):
-                for job in prof_jobs:
-                    self._spmm(job[0], job[1], job[2], **job[3])
-                if self.gemm != "bf16x3":
-                    self._wgrad(self.dP_usr, m.user_feats, m.user_trans, False, ws=self.ws_wgrad_b)
-            # the ID chain depends on the BPR rows only, not on the fusion backward: it starts beside it (captured after it, so that the
-            # fusion backward stays the graph's same-queue successor of the BPR launch) and has most of its SpMMs behind it when the
-            # weight-gradient GEMM takes every CU (one 512-register wave per SIMD leaves no room for a second kernel)
-            if ev_rows is not None:
-                self._fork_from(ev_rows, self.s2)
-            with self._on(self.s2):
-                chain_head()
-                for job in chain_jobs():
-                    self._spmm(job[0], job[1], job[2], **job[3])
-                chain_tail()
-            if not main_first:
-                for job in side_jobs:
-                    self._spmm(job[0], job[1], job[2], **job[3])
-        # the item-side weight gradients
+                jobs.append((self.iu.bwd, g, self.bufU, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_u))))
+                h = self.bufU
+            dst = self.m.item_id_embedding.weight.grad if l == 0 else self.bufI
+            jobs.append((self.ui.bwd, h, dst, dict(tag=2, epilogue=ops.spmm_epilogue(ops.EPI_NONE, inv, self.dE_i))))
+            g = self.bufI
+        return jobs
+
+    def _chain_tail(self, probs, batch, ev_fuse=None):
+        """Tail of the ID chain's backward, after the last reader of dE_u / dE_i (the chain and the fusion backward - ev_fuse on four
+        streams): clear the rows the batch touched, update the item table."""
+        users, pos, neg, n_valid = batch
+        B = users.numel()
+        if self.L == 0:
+            self._axpy(1.0 / (self.L + 1), self.dE_i, self.m.item_id_embedding.weight.grad, False)
+        # (The wait below is for an EARLY event. A wait for a late one anywhere in this stream's chain - e.g. for the transposed side
+        # product, had the row stamps needed a clean-up - makes the graph runtime start the WHOLE chain late:
+        # profiles/experiments/r03_wgrad.md, last table.)
+        if ev_fuse is not None:
+            torch.cuda.current_stream().wait_event(ev_fuse)
+        if self.fold and self.L > 0:                                              # clean-up + the item table's AdamW in ONE launch
+            jobs = [(users, self.dE_u), (pos, self.dE_i), (neg, self.dE_i), (users, self.sc_U), (pos, self.sc_I), (neg, self.sc_I),
+                    (users, self.sc_prof)]
+            self.opt.step_params(self._emb_params[1:], zero_rows=(jobs, B, n_valid))
+        else:
+            _call("llmrec_bpr_multi_zero_rows_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid))
+            if self.inline_adamw:                                                 # the item table's gradient is final: update it here,
+                self.opt.step_params(self._emb_params[1:])                        # beside the weight-gradient GEMM
+
+    def _side_bwd_jobs(self):
+        """(side chain, profile chain) of the backward as [(a, X, Y, kwargs)]. Side: I_cat = iu(U_cat), U_cat = ui(P_cat) (or the
+        pre-propagated projection); profile: prof_u = ui(prof_i), prof_i = iu(P_usr) - user_trans' weight gradient joins the item-side ones."""
+        side = [(self.iu.bwd, self.dI_cat, self.dU_cat, dict(accumulate=True))]
+        if not self.preprop:
+            side.append((self.ui.bwd, self.dU_cat, self.dP_cat, {}))
+        prof = [(self.ui.bwd, self.dprof_u, self.dprof_i, dict(accumulate=True, tag=1)), (self.iu.bwd, self.dprof_i, self.dP_usr, dict(tag=1))]
+        return side, prof
+
+    def _backward_one_stream(self, probs, batch, fuse, side_work):
+        """The backward up to the weight gradients on ONE stream: the k-th product of the ID chain, of the side chain and of the profile
+        chain share a launch (_spmm_group); folded, the fusion backward shares the chain head's."""
+        if not self.fold:
+            _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
+        self._chain_head(side_work, fuse if self.fold else None)
+        chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs()
+        for k in range(max(len(chain), len(side), len(prof))):
+            self._spmm_group([c[k] if k < len(c) else None for c in (chain, side, prof)])
+        if self.gemm != "bf16x3":                                        # (bf16x3: user_trans' gradient is in the multi-target launch)
+            self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
+        self._chain_tail(probs, batch)
+
+    def _backward_streams(self, probs, batch, fuse, side_work):
+        """The backward up to the weight gradients on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule):
+        fusion backward and side chain on the current stream, profile chain on s1, ID chain on s2."""
+        ev_rows = self._mark()                                           # dE_u / dE_i hold the scattered rows: all the ID chain needs
+        _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
+        ev_fuse = self._mark()                                           # the fusion backward has read dE_u / dE_i
+        side, prof = self._side_bwd_jobs()
+        # folded step: the critical transposed side product is captured BEFORE the two side branches (main_first) and the logged-scalar
+        # launch gets a stream of its own (loss_s3) - each alone lost, both together won: profiles/experiments/r05_step_chain.md
+        main_first, loss_s3 = self.fold, self.fold and side_work is not None
+        if main_first:
+            self._spmm_jobs(side)
+            self._fork_from(ev_fuse, self.s1)
+        else:
+            self._fork(self.s1)
+        if loss_s3:
+            self._fork_from(ev_rows, self.s3)
+            with self._on(self.s3):
+                side_work()
+            side_work = None
+        with self._on(self.s1):
+            self._spmm_jobs(prof)
+            if self.gemm != "bf16x3":
+                self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
+        # the ID chain depends on the BPR rows only, not on the fusion backward: it starts beside it (captured after it, so that the
+        # fusion backward stays the graph's same-queue successor of the BPR launch) and has most of its SpMMs behind it when the
+        # weight-gradient GEMM takes every CU (one 512-register wave per SIMD leaves no room for a second kernel)
+        self._fork_from(ev_rows, self.s2)
+        with self._on(self.s2):
+            self._chain_head(side_work)
+            self._spmm_jobs(self._chain_bwd_jobs())
+            self._chain_tail(probs, batch, ev_fuse)
+        if not main_first:
+            self._spmm_jobs(side)
+
+    def _weight_gradients(self):
+        """The four Linears' gradients from dU_cat (pre-propagated; else dP_cat) and dP_usr, and - with inline_adamw - their update."""
+        m, S, d = self.m, self.S, self.d
         dY_cat = self.dU_cat if self.preprop else self.dP_cat
         targets = self.wgrad_targets(dY_cat, self.dP_usr)
         item_pairs, text_pairs, image_pairs = targets[0][0], targets[2][0], targets[3][0]
@@ -779,7 +782,7 @@ class FusedStep:
                 self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=dY_cat.device) if need >= 0 else False
             if self.ws_wgrad_multi is not False:
                 self._stamp(3)
-                if getattr(self, "_ev_reach", None) is not None:                 # (four streams: the row list was built behind the ID chain)
+                if self._ev_reach is not None:                           # (four streams: the row list was built behind the ID chain)
                     torch.cuda.current_stream().wait_event(self._ev_reach)
                 lins = (m.item_trans, m.user_trans, m.text_trans, m.image_trans)              # (wgrad_targets' order)
                 if self.inline_adamw:                                  # the four Linears' AdamW rides in the slab-reduction launch
@@ -806,9 +809,6 @@ class FusedStep:
         self._join(self.s1)                                              # user_trans' gradient
         if self.inline_adamw:                                            # whatever the reduction launch did not update (all four Linears on
             self.opt.step_params([p_ for p_ in self._lin_params if all(p_ is not q for q in updated)])   # the per-target fallback paths)
-        self._join(self.s2)
-        if loss_s3:
-            self._join(self.s3)
 
     def _train_forward(self, sampler=None, after_chain=None):
         """forward() of a training step: also advances AdamW's counters (and samples the batch) on a side stream."""
