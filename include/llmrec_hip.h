@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LLMREC_ABI_VERSION 7
+#define LLMREC_ABI_VERSION 8
 
 enum {
     LLMREC_OK = 0,
@@ -142,19 +142,6 @@ typedef struct {
      *                 explicit row list this is "these rows of A X"; all other rows of Y keep their contents. */
     const uint8_t* x_row_mask; int32_t x_mask_active; uint8_t* y_row_flag; const uint8_t* z_row_flag; const uint8_t* y_row_gate;
     const uint8_t* y_row_needed; int32_t rows_listed_only;
-    /* Cache policy (round 5 experiment, profiles/experiments/r05_spmm_nt.md): x_nt_from_row > 0 gathers the X rows with index >= x_nt_from_row
-     * with non-temporal loads, the rows below it with the default policy - meant for operands whose columns are ordered by descending
-     * degree (hot rows first), so that the cold 256-B rows stream through the L2 without displacing the hot set. A hint only: results are
-     * bit-identical. Pattern-only, unmasked products; ignored otherwise. 0 = off. */
-    int32_t x_nt_from_row;
-    /* Block -> row map (round 6 experiment, profiles/experiments/r06_spmm_order.md): xcd_contiguous != 0 gives the workgroups of one XCD (ids
-     * equal mod 8: each XCD has a private L2) a CONTIGUOUS piece of the short-row / wavefront-row / block-row tasks instead of every 8th
-     * block of them - for graphs whose row ids expose communities. Results are bit-identical. 0 = the linear map. */
-    int32_t xcd_contiguous;
-    /* Round 6: the tasks of the lane-group bucket run as software pipelines - a lane group takes several tasks and keeps the next task's indices
-     * and the one after's row pointers in flight while it gathers (one memory round trip per task instead of three; results bit-identical).
-     * no_pipeline != 0 restores one task per lane group (A/B switch). */
-    int32_t no_pipeline;
 } llmrec_spmm_epilogue_t;
 /* Round 5 - "these rows of A X" with the row list AND its length in device memory (the row-restricted forward of the row-sharded step,
  * without a host read-back: llmrec_amd/dist_fused.py). Pattern-only operands (A = diag(row_scale) P).
@@ -214,7 +201,7 @@ int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
  * exactly the arguments of one llmrec_spmm_f32 call and is checked like one; the problems' blocks follow each other in the given order
  * (longest first keeps the tail short), and problems with split rows share one finalize launch after the main one. Every row keeps its
  * summation tree: results are bit-identical to separate calls. n = 1 is llmrec_spmm_f32. Returns LLMREC_EUNSUPPORTED (nothing launched)
- * if the problems do not all resolve to the same kernel instance (width class, vector loads, weighted, masked, cache policy) - the caller
+ * if the problems do not all resolve to the same kernel instance (width class, vector loads, weighted, masked) - the caller
  * then issues separate calls - and LLMREC_EINVAL if the output (Y or partials) of one problem overlaps X, Y, Z, S or the partials of
  * another. Empty problems (n_rows = 0 or d = 0) are skipped. */
 #define LLMREC_SPMM_MAX_PROBLEMS 4

@@ -38,12 +38,6 @@ template <> struct Vec<4> {
     float4 v;
     __device__ __forceinline__ void zero() { v = make_float4(0.f, 0.f, 0.f, 0.f); }
     __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const float4*>(p); }
-    // the same 16 bytes with the non-temporal cache policy (global_load_dwordx4 ... nt): a hint that the line will not be reused
-    __device__ __forceinline__ void load_nt(const float* p) {
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-        v = make_float4(t.x, t.y, t.z, t.w);
-    }
     __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
     __device__ __forceinline__ void add(const Vec& o) { v.x += o.v.x; v.y += o.v.y; v.z += o.v.z; v.w += o.v.w; }
     __device__ __forceinline__ void fma(float w, const Vec& o) {
@@ -65,7 +59,6 @@ template <> struct Vec<1> {
     float v;
     __device__ __forceinline__ void zero() { v = 0.f; }
     __device__ __forceinline__ void load(const float* p) { v = *p; }
-    __device__ __forceinline__ void load_nt(const float* p) { v = __builtin_nontemporal_load(p); }
     __device__ __forceinline__ void store(float* p) const { *p = v; }
     __device__ __forceinline__ void add(const Vec& o) { v += o.v; }
     __device__ __forceinline__ void fma(float w, const Vec& o) { v = fmaf(w, o.v, v); }
@@ -108,10 +101,7 @@ struct SpmmArgs {
     const uint8_t* y_gate;       // rows whose byte != x_active: no active neighbour, zero Z row - written as zeros at once
     const uint8_t* y_needed;     // rows whose byte != x_active are neither computed nor written (short-row range)
     int32_t listed_only;         // no short-row range at all: only the plan's row lists are computed
-    int32_t nt_from;             // (NT kernels) X rows with index >= nt_from are gathered with the non-temporal policy: cache hint only
-    int32_t no_pipeline;         // llmrec_spmm_epilogue_t.no_pipeline
     int32_t pipe;                // > 1: tasks per lane group of the short-row range, run as a software pipeline (rows_body_pipe)
-    int32_t xcd;                 // block -> row map of the short-row / wavefront-row / block-row ranges: XCD-contiguous (xcd_range_logical)
     // plan
     const int32_t* slot_row;     // non-NULL: rowptr / colidx are the PERMUTED CSR of the plan - CSR row `slot` is output row slot_row[slot], the
     int32_t n_short_rows;        // first n_short_rows slots are the lane-group bucket, the plan's lists hold slots (llmrec_spmm_plan_t)
@@ -132,8 +122,8 @@ struct SpmmArgs {
 // (a.x_mask) are known to be all-zero and are not fetched; `any` collects whether this lane saw an active column.
 // unmasked ranges (round 6): the NEXT chunk's column indices (and adjacency values) are fetched while the current chunk's rows are gathered, the
 // col_scale factors of the current chunk ride beside its gathers - one memory round trip per chunk of LPR non-zeros instead of two or three.
-// Same gathers, same order of additions: bit-identical to the loop it replaces.
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool NT>
+// Same gathers, same order of additions as one chunk at a time: bit-identical to the masked loop with every column active.
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED>
 __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK]) {
     int32_t c_next = 0;
     float v_next = 1.0f;
@@ -156,13 +146,11 @@ __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_
 #pragma unroll
                 for (int k = 0; k < NCHUNK; ++k) {
                     const int col = (k * LPR + gl) * VEC;
-                    if (tt < n && col < a.d) {
-                        if (NT && c >= a.nt_from) v[u][k].load_nt(xr + col);     // (uniform per lane group) cold row: do not displace the hot set
-                        else v[u][k].load(xr + col);
-                    } else v[u][k].zero();
+                    if (tt < n && col < a.d) v[u][k].load(xr + col);
+                    else v[u][k].zero();
                 }
             }
-            if (WEIGHTED && t == 0) myw = gl < n ? myw * cs : 0.f;            // val[e] * col_scale[c], as the loop it replaces forms it
+            if (WEIGHTED && t == 0) myw = gl < n ? myw * cs : 0.f;            // val[e] * col_scale[c], as the masked loop forms it
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 float w = 0.f;
@@ -177,24 +165,24 @@ __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_
     }
 }
 
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK], int& any) {
     if constexpr (!MASKED) {
-        if (!a.no_pipeline) { accumulate_range_plain<LPR, NCHUNK, VEC, WEIGHTED, NT>(a, col0, s, e, gl, acc); return; }
-    }
-    for (int32_t base = s; base < e; base += LPR) {        const int n = min(LPR, e - base);
-        int32_t myc = 0;
-        float myw = 0.f;
-        int myact = 0;
-        if (gl < n) {
-            myc = a.colidx[base + gl];
-            if (WEIGHTED) {
-                myw = a.val ? a.val[base + gl] : 1.0f;
-                if (a.col_scale) myw *= a.col_scale[myc];
+        accumulate_range_plain<LPR, NCHUNK, VEC, WEIGHTED>(a, col0, s, e, gl, acc);
+    } else {
+        for (int32_t base = s; base < e; base += LPR) {
+            const int n = min(LPR, e - base);
+            int32_t myc = 0;
+            float myw = 0.f;
+            int myact = 0;
+            if (gl < n) {
+                myc = a.colidx[base + gl];
+                if (WEIGHTED) {
+                    myw = a.val ? a.val[base + gl] : 1.0f;
+                    if (a.col_scale) myw *= a.col_scale[myc];
+                }
+                myact = (int)a.x_mask[myc] == a.x_active; any |= myact;
             }
-            if (MASKED) { myact = (int)a.x_mask[myc] == a.x_active; any |= myact; }
-        }
-        if (MASKED) {
             // only the ACTIVE columns of this chunk are visited (ascending, as in the dense loop: the skipped terms are exact zeros)
             const unsigned long long bal = __ballot(myact != 0);
             const int g0 = (int)(threadIdx.x & 63) / LPR * LPR;
@@ -224,34 +212,6 @@ __device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0
                         if (WEIGHTED) acc[k].fma(w[u], v[u][k]);
                         else acc[k].add(v[u][k]);
                     }
-                }
-            }
-            continue;
-        }
-        for (int t = 0; t < n; t += UNROLL) {
-            Vec<VEC> v[UNROLL][NCHUNK];
-            float w[UNROLL];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                const int tt = t + u;
-                const int32_t c = __shfl(myc, tt & (LPR - 1), LPR);
-                if (WEIGHTED) w[u] = __shfl(myw, tt & (LPR - 1), LPR);
-                const float* xr = a.X + (int64_t)c * a.ldx + col0;
-#pragma unroll
-                for (int k = 0; k < NCHUNK; ++k) {
-                    const int col = (k * LPR + gl) * VEC;
-                    if (tt < n && col < a.d) {
-                        if (NT && c >= a.nt_from) v[u][k].load_nt(xr + col);     // (uniform per lane group) cold row: do not displace the hot set
-                        else v[u][k].load(xr + col);
-                    } else v[u][k].zero();
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-#pragma unroll
-                for (int k = 0; k < NCHUNK; ++k) {
-                    if (WEIGHTED) acc[k].fma(w[u], v[u][k]);
-                    else acc[k].add(v[u][k]);
                 }
             }
         }
@@ -329,7 +289,7 @@ __device__ __forceinline__ void finish_row(const SpmmArgs& a, int64_t col0, int6
 constexpr int TPB = 512;                                        // threads per block: 8 wavefronts
 
 // one lane group per (row, slice) task; rows with more than LLMREC_SPMM_LONG_ROW nnz belong to the other ranges
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ void rows_body(const SpmmArgs& a, int64_t block) {
     constexpr int GPB = TPB / LPR;
     const int gl = threadIdx.x & (LPR - 1);
@@ -362,9 +322,9 @@ __device__ __forceinline__ void rows_body(const SpmmArgs& a, int64_t block) {
         const unsigned long long gm = LPR >= 64 ? ~0ull : (((1ull << LPR) - 1ull) << g0);
         const bool any_g = (bal & gm) != 0ull;
         zero_row = write_row_flag(a, row, any_g, slice == 0 && gl == 0);
-        if (any_g) accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, s, e, gl, acc, any);
+        if (any_g) accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any);
     } else {
-        accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, s, e, gl, acc, any);
+        accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any);
     }
     finish_row<LPR, NCHUNK, VEC>(a, col0, row, gl, acc, zero_row);
 }
@@ -464,7 +424,7 @@ __device__ __forceinline__ void rows_body_pipe(const SpmmArgs& a, int64_t block,
 }
 
 // one wavefront over [s, e): the 64/LPR lane groups take contiguous parts, butterfly sum -> every group holds the total
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ void wave_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int lane, Vec<VEC> (&acc)[NCHUNK], int& any) {
     constexpr int G = 64 / LPR;
     const int gl = lane & (LPR - 1), g = lane / LPR;
@@ -472,7 +432,7 @@ __device__ __forceinline__ void wave_range(const SpmmArgs& a, int64_t col0, int3
     const int32_t gs = min(s + g * per, e), ge = min(gs + per, e);
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
-    accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, gs, ge, gl, acc, any);
+    accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, gs, ge, gl, acc, any);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
 #pragma unroll
@@ -491,7 +451,7 @@ __device__ __forceinline__ void list_task(const SpmmArgs& a, const int32_t* list
 }
 
 // one wavefront per (row, slice) of the wave-row list
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ void wave_rows_body(const SpmmArgs& a, int32_t block) {
     const int lane = threadIdx.x & 63;
     const int64_t task = (int64_t)block * (TPB / 64) + (threadIdx.x >> 6);
@@ -507,20 +467,20 @@ __device__ __forceinline__ void wave_rows_body(const SpmmArgs& a, int32_t block)
             if (base + lane < re) any |= (int)a.x_mask[a.colidx[base + lane]] == a.x_active;
         const bool any_w = __ballot(any != 0) != 0ull;
         zero_row = write_row_flag(a, row, any_w, col0 == 0 && lane == 0);
-        if (any_w) wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, rs, re, lane, acc, any);
+        if (any_w) wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, rs, re, lane, acc, any);
         else {
 #pragma unroll
             for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
         }
     } else {
-        wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], lane, acc, any);
+        wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], lane, acc, any);
     }
     if (lane < LPR) finish_row<LPR, NCHUNK, VEC>(a, col0, row, lane, acc, zero_row);
 }
 
 // one block over [s, e): the 8 waves take contiguous parts, summed through LDS in wave order; the total ends up in the
 // first lane group of wave 0 (returns true there)
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK]) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     constexpr int NW = TPB / 64;
@@ -528,7 +488,7 @@ __device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int
     const int32_t per = (((e - s) + NW - 1) / NW + 63) / 64 * 64;
     const int32_t ws = min(s + w * per, e), we = min(ws + per, e);
     int any = 0;                                                         // (long rows: their output flag is set unconditionally)
-    wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, ws, we, lane, acc, any);
+    wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, ws, we, lane, acc, any);
     if (w > 0 && lane < LPR) {
 #pragma unroll
         for (int k = 0; k < NCHUNK; ++k) acc[k].store(lds + (w - 1) * ROWW + (k * LPR + lane) * VEC);
@@ -543,37 +503,25 @@ __device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int
     return true;
 }
 
-// Consecutive workgroup ids are dealt round-robin to the 8 XCDs, each with a private L2 (4 MB). With the linear block -> row map every XCD
-// therefore walks the WHOLE row range (every 8th block), and on a graph whose ids expose communities each community's X rows are fetched
-// into all eight L2s. xcd = 1 (llmrec_spmm_epilogue_t.xcd_contiguous): within a range [base, base + n) of block ids the blocks of XCD x
-// (ids = x mod 8) take the x-th contiguous piece of the range's tasks, in id order - neighbouring rows run on ONE XCD and each L2 holds
-// the columns of its own eighth of the rows. Only the block -> row map changes: results are bit-identical.
-__device__ __forceinline__ int32_t xcd_range_logical(int32_t b, int32_t base, int32_t n) {
-    const int x = b & 7, r0 = base & 7;
-    int32_t off = 0;
-    for (int xx = 0; xx < x; ++xx) { const int fl = (xx - r0) & 7; off += fl < n ? (n - fl + 7) >> 3 : 0; }
-    return off + ((b - base - ((x - r0) & 7)) >> 3);
-}
-
 // One problem's block b (a global block id) of the ranges of SpmmArgs: the heavy blocks come first. The segment partials are indexed by
 // the problem-local block id, so a grouped launch addresses them exactly like a launch of its own.
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* red_lds) {
     if (b >= a.blk_wave) {
-        const int64_t lb = a.xcd ? (int64_t)xcd_range_logical(b, a.blk_wave, a.blk_end - a.blk_wave) : (int64_t)b - a.blk_wave;
-        if (!MASKED && !NT && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)a.blk_end - a.blk_wave);     // (block-uniform)
-        else rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, lb);
+        const int64_t lb = (int64_t)b - a.blk_wave;
+        if (!MASKED && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)a.blk_end - a.blk_wave);     // (block-uniform)
+        else rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, lb);
         return;
     }
     if (b >= a.blk_block) {
-        wave_rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, a.xcd ? xcd_range_logical(b, a.blk_block, a.blk_wave - a.blk_block) : b - a.blk_block);
+        wave_rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, b - a.blk_block);
         return;
     }
     Vec<VEC> acc[NCHUNK];
     int32_t crow, row, slot; int64_t col0;
     if (b >= a.blk_seg) {
-        list_task(a, a.block_rows, a.n_block_rows, a.xcd ? xcd_range_logical(b, a.blk_seg, a.blk_block - a.blk_seg) : b - a.blk_seg, crow, row, col0, slot);
-        if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], red_lds, acc)) {
+        list_task(a, a.block_rows, a.n_block_rows, b - a.blk_seg, crow, row, col0, slot);
+        if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], red_lds, acc)) {
             if (MASKED && col0 == 0 && threadIdx.x == 0 && a.y_flag) a.y_flag[row] = (uint8_t)a.x_active;   // conservative: "may be non-zero"
             finish_row<LPR, NCHUNK, VEC>(a, col0, row, threadIdx.x, acc);
         }
@@ -589,7 +537,7 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* r
     const int32_t re = a.rowptr[crow + 1];
     const int32_t s = a.rowptr[crow] + k_in_row * a.segment;
     const int32_t e = min(s + a.segment, re);
-    if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, col0, s, e, red_lds, acc)) {
+    if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, red_lds, acc)) {
         if (MASKED && col0 == 0 && k_in_row == 0 && threadIdx.x == 0 && a.y_flag) a.y_flag[row] = (uint8_t)a.x_active;   // conservative
         float* pr = a.partials + (int64_t)lb * a.d;
 #pragma unroll
@@ -601,11 +549,11 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* r
 }
 
 // ONE launch of one problem (blk_begin = 0, blk_end = the grid).
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
-    spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(a, (int32_t)blockIdx.x, red_lds);
+    spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, (int32_t)blockIdx.x, red_lds);
 }
 
 // Up to LLMREC_SPMM_MAX_PROBLEMS independent problems of ONE kernel instance in one launch (llmrec_spmm_multi_f32): problem q owns the
@@ -622,16 +570,16 @@ __device__ __forceinline__ int spmm_multi_problem(const SpmmMulti& m, int32_t b)
     return (int)(b >= m.begin[1]) + (int)(b >= m.begin[2]) + (int)(b >= m.begin[3]);
 }
 
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool NT>
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
 __global__ __launch_bounds__(TPB) void spmm_multi_kernel(SpmmMulti m) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
     const int32_t b = blockIdx.x;
     switch (spmm_multi_problem(m, b)) {                                   // (block-uniform)
-    case 0: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[0], b, red_lds); break;
-    case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[1], b, red_lds); break;
-    case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[2], b, red_lds); break;
-    default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED, NT>(m.p[3], b, red_lds); break;
+    case 0: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[0], b, red_lds); break;
+    case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[1], b, red_lds); break;
+    case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[2], b, red_lds); break;
+    default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[3], b, red_lds); break;
     }
 }
 
@@ -711,7 +659,7 @@ __global__ __launch_bounds__(TPB) void spmm_rows_compact_kernel(SpmmArgs a, cons
     compact_pieces(e - s, per, n_pieces);
     if (p >= n_pieces) return;
     Vec<VEC> acc[NCHUNK];
-    if (block_range<LPR, NCHUNK, VEC, false, false, false>(a, 0, s + p * per, min(s + (p + 1) * per, e), red_lds, acc)) {
+    if (block_range<LPR, NCHUNK, VEC, false, false>(a, 0, s + p * per, min(s + (p + 1) * per, e), red_lds, acc)) {
         float* pr = partial + ((int64_t)j * LLMREC_SPMM_COMPACT_PARTS + p) * a.d;
 #pragma unroll
         for (int k = 0; k < NCHUNK; ++k) {
@@ -763,10 +711,10 @@ static int launch_rows_compact(SpmmArgs& a, const int32_t* row_list, const int32
     return LLMREC_OK;
 }
 
-// The compiled kernel family (LPR, NCHUNK, VEC) and variant (WEIGHTED, MASKED, NT) of a product: two products can share a grouped launch
-// only when both agree. The grouped kernels are compiled for the vector-load families (0..6) and the unmasked, default-cache-policy variants:
-// the latency-bound products of the step; masked products and the cache-policy split run in the HBM-bound or row-restricted paths.
-enum { SPMM_V_MASKED_W, SPMM_V_MASKED, SPMM_V_NT, SPMM_V_WEIGHTED, SPMM_V_PLAIN };
+// The compiled kernel family (LPR, NCHUNK, VEC) and variant (WEIGHTED, MASKED) of a product: two products can share a grouped launch
+// only when both agree. The grouped kernels are compiled for the vector-load families (0..6) and the unmasked variants: the latency-bound
+// products of the step; masked products run in the HBM-bound or row-restricted paths.
+enum { SPMM_V_MASKED_W, SPMM_V_MASKED, SPMM_V_WEIGHTED, SPMM_V_PLAIN };
 static const int kSpmmFamilyLpr[] = {4, 8, 16, 32, 64, 64, 64, 16, 64, 64};
 
 struct SpmmPrepared {
@@ -820,10 +768,6 @@ static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
         LLMREC_CHECK_ARG(e.op != LLMREC_SPMM_EPI_SOFTMAX_BWD || (e.S && e.lds >= d), "spmm: softmax backward needs S with ld >= d");
         a.epi_op = e.op; a.alpha = e.alpha; a.Z = e.Z; a.ldz = e.ldz; a.S = e.S; a.lds = e.lds; a.post_scale = e.post_scale;
         a.listed_only = e.rows_listed_only != 0;
-        LLMREC_CHECK_ARG(e.x_nt_from_row >= 0, "spmm: negative x_nt_from_row");
-        a.nt_from = e.x_nt_from_row;
-        a.xcd = e.xcd_contiguous != 0;
-        a.no_pipeline = e.no_pipeline != 0;
         if (e.y_row_needed) {
             LLMREC_CHECK_ARG(e.x_mask_active >= 1 && e.x_mask_active <= 255, "spmm: y_row_needed needs x_mask_active in 1..255");
             a.y_needed = e.y_row_needed; a.x_active = e.x_mask_active;
@@ -851,7 +795,6 @@ static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
     const bool weighted = a.val != nullptr || a.col_scale != nullptr;
     out.family = f;
     out.variant = a.x_mask ? (weighted ? SPMM_V_MASKED_W : SPMM_V_MASKED)
-                : (a.nt_from > 0 && !weighted) ? SPMM_V_NT                // cache-policy split (pattern-only operands: the propagation products)
                 : weighted ? SPMM_V_WEIGHTED : SPMM_V_PLAIN;
     out.bytes_x = X ? extent_bytes(n_cols, ldx, d) : 0;
     out.bytes_y = extent_bytes(n_rows, ldy, d);
@@ -863,13 +806,12 @@ static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
 
 // The block ranges of one problem whose blocks start at `first` (0 for a launch of its own); returns its block count, -1 past 32-bit ids.
 static int64_t spmm_layout(SpmmArgs& a, int lpr, int64_t first) {
-    const bool weighted = a.val != nullptr || a.col_scale != nullptr;
     const int64_t GPB = TPB / lpr;
     const int64_t S = a.n_slices;
     // unmasked products: the short rows' tasks as software pipelines (rows_body_pipe) - as many tasks per lane group as keep ~4 blocks per CU
     const int64_t short_tasks = a.listed_only ? 0 : (a.slot_row ? (int64_t)a.n_short_rows : a.n_rows) * S;
     int64_t pipe = 1;
-    if (!a.x_mask && !(a.nt_from > 0 && !weighted) && !a.no_pipeline) {
+    if (!a.x_mask) {
         pipe = short_tasks + GPB * 8192 < (1ll << 31) ? ceil_div(short_tasks, GPB * 1024) : 1;      // (32-bit task ids in the kernel)
         if (pipe > 8) pipe = 8;
         if (pipe < 1) pipe = 1;
@@ -895,11 +837,10 @@ static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipS
         if (n == 1) {
             const SpmmArgs& a = pp[0].a;
             switch (variant) {
-            case SPMM_V_MASKED_W: spmm_kernel<LPR, NCHUNK, VEC, true, true, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
-            case SPMM_V_MASKED: spmm_kernel<LPR, NCHUNK, VEC, false, true, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
-            case SPMM_V_NT: spmm_kernel<LPR, NCHUNK, VEC, false, false, true><<<(unsigned)total, TPB, 0, stream>>>(a); break;
-            case SPMM_V_WEIGHTED: spmm_kernel<LPR, NCHUNK, VEC, true, false, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
-            default: spmm_kernel<LPR, NCHUNK, VEC, false, false, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_MASKED_W: spmm_kernel<LPR, NCHUNK, VEC, true, true><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_MASKED: spmm_kernel<LPR, NCHUNK, VEC, false, true><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            case SPMM_V_WEIGHTED: spmm_kernel<LPR, NCHUNK, VEC, true, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
+            default: spmm_kernel<LPR, NCHUNK, VEC, false, false><<<(unsigned)total, TPB, 0, stream>>>(a); break;
             }
         } else if constexpr (VEC == 4) {                     // (spmm_run groups the vector-load families only)
             SpmmMulti m = {};
@@ -907,8 +848,8 @@ static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipS
                 if (q < n) { m.p[q] = pp[q].a; m.begin[q] = pp[q].a.blk_begin; }
                 else m.begin[q] = 0x7fffffff;
             }
-            if (variant == SPMM_V_WEIGHTED) spmm_multi_kernel<LPR, NCHUNK, VEC, true, false, false><<<(unsigned)total, TPB, 0, stream>>>(m);
-            else spmm_multi_kernel<LPR, NCHUNK, VEC, false, false, false><<<(unsigned)total, TPB, 0, stream>>>(m);
+            if (variant == SPMM_V_WEIGHTED) spmm_multi_kernel<LPR, NCHUNK, VEC, true, false><<<(unsigned)total, TPB, 0, stream>>>(m);
+            else spmm_multi_kernel<LPR, NCHUNK, VEC, false, false><<<(unsigned)total, TPB, 0, stream>>>(m);
         }
         LLMREC_LAUNCH_CHECK();
     }
@@ -961,7 +902,7 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
         }
     }
     if (m > 1 && !(pp[0].family <= 6 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED))) {
-        set_error("spmm_multi: grouped launches are compiled for the unmasked products with vector loads and the default cache policy only");
+        set_error("spmm_multi: grouped launches are compiled for the unmasked products with vector loads only");
         return LLMREC_EUNSUPPORTED;
     }
     // what one problem writes (Y, its partials) must not be read or written by another one: they run concurrently

@@ -71,8 +71,7 @@ class SpmmEpilogueC(_c.Structure):
     """llmrec_spmm_epilogue_t"""
     _fields_ = [("op", _c.c_int32), ("alpha", _c.c_float), ("Z", _c.c_void_p), ("ldz", _c.c_int64), ("S", _c.c_void_p), ("lds", _c.c_int64),
                 ("post_scale", _c.c_void_p), ("x_row_mask", _c.c_void_p), ("x_mask_active", _c.c_int32), ("y_row_flag", _c.c_void_p),
-                ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32),
-                ("x_nt_from_row", _c.c_int32), ("xcd_contiguous", _c.c_int32), ("no_pipeline", _c.c_int32)]
+                ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32)]
 
 
 class SpmmProblemC(_c.Structure):
@@ -167,10 +166,7 @@ class SpmmPlan:
     def by_length_class(rows: torch.Tensor, deg: torch.Tensor) -> torch.Tensor:
         """`rows` (ascending ids) reordered by descending length class - the power-of-two bucket of the row's nnz, empty rows last - and
         ascending id within a class (stable): rows that share a wavefront / a round of blocks then take (almost) equally long."""
-        if os.environ.get("LLMREC_SPMM_CLASS", "log2") == "exact":       # (experiment: one class per length)
-            cls = deg.to(torch.int64)
-        else:
-            cls = torch.where(deg > 0, torch.floor(torch.log2(deg.clamp(min=1).to(torch.float64))).to(torch.int64) + 1, torch.zeros_like(deg, dtype=torch.int64))
+        cls = torch.where(deg > 0, torch.floor(torch.log2(deg.clamp(min=1).to(torch.float64))).to(torch.int64) + 1, torch.zeros_like(deg, dtype=torch.int64))
         return rows[torch.sort(-cls, stable=True).indices].to(torch.int32).contiguous()
 
     @staticmethod
@@ -372,15 +368,13 @@ class BipartiteGraph:
 def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tensor] = None, S: Optional[torch.Tensor] = None,
                   post_scale: Optional[torch.Tensor] = None, x_row_mask: Optional[torch.Tensor] = None, x_mask_active: int = 0,
                   y_row_flag: Optional[torch.Tensor] = None, z_row_flag: Optional[torch.Tensor] = None,
-                  y_row_gate: Optional[torch.Tensor] = None, y_row_needed: Optional[torch.Tensor] = None, rows_listed_only: bool = False,
-                  x_nt_from_row: int = 0, xcd_contiguous: bool = False, no_pipeline: bool = False):
+                  y_row_gate: Optional[torch.Tensor] = None, y_row_needed: Optional[torch.Tensor] = None, rows_listed_only: bool = False):
     """llmrec_spmm_epilogue_t: Y = post_scale . op(alpha * Z + A X); S = forward softmax rows for EPI_SOFTMAX_BWD.
     x_row_mask (uint8 [n_cols]) / x_mask_active: X rows whose byte differs from the active value are promised all-zero and not read;
     y_row_flag (uint8 [n_rows]): receives the active value for rows whose result can be non-zero (z_row_flag: the non-zero rows of Z);
     y_row_gate (uint8 [n_rows]): rows without the active value are promised zero results and written as zeros unread;
     y_row_needed (uint8 [n_rows]): rows without the active value are neither computed nor written; rows_listed_only: compute the rows
-    in the plan's lists only (spmm_listed); x_nt_from_row > 0: X rows from that index on are gathered with non-temporal loads (cache hint);
-    xcd_contiguous: the workgroups of one XCD take a contiguous piece of the rows (same bits, another block -> row map)."""
+    in the plan's lists only (spmm_listed)."""
     for t in (x_row_mask, y_row_flag, z_row_flag, y_row_gate, y_row_needed):
         if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
             raise RuntimeError("spmm_epilogue: row masks / flags are contiguous uint8 tensors")
@@ -391,9 +385,7 @@ def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tens
                          y_row_flag.data_ptr() if y_row_flag is not None else None,
                          z_row_flag.data_ptr() if z_row_flag is not None else None,
                          y_row_gate.data_ptr() if y_row_gate is not None else None,
-                         y_row_needed.data_ptr() if y_row_needed is not None else None, 1 if rows_listed_only else 0, int(x_nt_from_row),
-                         1 if xcd_contiguous else 0,
-                         1 if no_pipeline else 0)
+                         y_row_needed.data_ptr() if y_row_needed is not None else None, 1 if rows_listed_only else 0)
 
 
 def listed_plan(a: Csr, rows: torch.Tensor, d: int, whole_row: bool = False) -> SpmmPlan:

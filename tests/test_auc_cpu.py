@@ -49,7 +49,7 @@ def test_signed_zeros_tie_and_one_class_and_non_finite_give_zero():
 
 def test_argument_errors_of_score_auc():
     lib = _lib.load()
-    assert _lib.CONST["LLMREC_ABI_VERSION"] == 7 and lib.llmrec_abi_version() == 7
+    assert _lib.CONST["LLMREC_ABI_VERSION"] == 8 and lib.llmrec_abi_version() == 8
     assert lib.llmrec_score_auc_workspace_bytes(-1, 10, 64) == -1
     assert lib.llmrec_score_auc_workspace_bytes(100, 0, 64) == -1
     assert lib.llmrec_score_auc_workspace_bytes(100, 10, 64) > 0

@@ -144,15 +144,14 @@ def test_spmm_row_buckets_split_rows_and_epilogues(ops):
         op.fwd.plans[key] = keep
         # round 6: the plan's PERMUTED CSR (rows stored by descending length class, slot -> row map, lists in slots): the same bits as the
         # operand's own CSR - with every bucket populated (lane-group rows incl. empty ones, wavefront, block and split rows), with the
-        # "+ Z" and softmax epilogues, with column slices, and with the XCD-contiguous block -> row map
+        # "+ Z" and softmax epilogues, and with column slices
         assert op.fwd.val is None and keep.slot_row is not None          # (the default plan of a pattern-only operand is the permuted one)
         for alt in (key, (32, 32, 64)):
             perm = ops.SpmmPlan.build(op.fwd.rowptr, *alt, colidx=op.fwd.colidx, order_rows=True)
             assert perm.slot_row is not None and sorted(perm.slot_row.tolist()) == list(range(n_rows))
             plain = ops.SpmmPlan.build(op.fwd.rowptr, *alt)
             for epi in (lambda: None, lambda: ops.spmm_epilogue(ops.EPI_NONE, 0.25, Z), lambda: ops.spmm_epilogue(ops.EPI_SOFTMAX),
-                        lambda: ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, 0.5, Z, torch.softmax(Z, dim=-1)),
-                        lambda: ops.spmm_epilogue(xcd_contiguous=True)):
+                        lambda: ops.spmm_epilogue(ops.EPI_SOFTMAX_BWD, 0.5, Z, torch.softmax(Z, dim=-1))):
                 op.fwd.plans[key] = plain
                 a_ = ops.spmm_raw(op.fwd, X, epilogue=epi())
                 op.fwd.plans[key] = perm
@@ -175,33 +174,6 @@ def test_spmm_row_buckets_split_rows_and_epilogues(ops):
     # the transposed operand (hub COLUMNS become many short rows gathering with col_scale)
     G_cpu = torch.tensor(rng.standard_normal((n_rows, 64)).astype(np.float32))
     assert rel_err(ops.spmm_raw(op.bwd, G_cpu.to(DEV)).cpu(), torch.sparse.mm(A_cpu.t(), G_cpu)) < 2e-6
-
-
-@pytest.mark.parametrize("d", [64, 128, 20])
-def test_spmm_nontemporal_policy_is_bit_identical(ops, d):
-    """llmrec_spmm_epilogue_t.x_nt_from_row (round-5 cache-policy experiment, profiles/experiments/r05_spmm_nt.md): gathered rows from that
-    index on are loaded non-temporally - a hint, so every row bucket (lane group, wavefront, block, split segments) must give the SAME
-    BITS as the default policy, whatever the threshold, with and without an init term."""
-    rng = np.random.default_rng(500 + d)
-    n_rows, n_cols = 600, 45000
-    degs = rng.integers(0, 40, size=n_rows)
-    for k, dg in enumerate([0, 1, 32, 33, 511, 512, 513, 4095, 4097, 16385, 20000]):
-        degs[(k * 13 + 1) % n_rows] = dg
-    rows, cols = rand_graph(rng, n_rows, n_cols, degs)
-    deg = np.bincount(rows, minlength=n_rows)
-    s = np.where(deg > 0, 1.0 / np.sqrt(np.maximum(deg, 1)), 0).astype(np.float32)
-    A = torch.sparse_coo_tensor(torch.tensor(np.vstack([rows, cols])), torch.tensor(s[rows]), (n_rows, n_cols)).to(DEV)
-    a = ops.operand_from_sparse_tensor(A).fwd
-    assert a.val is None                                                 # pattern-only: the products the policy applies to
-    X = torch.tensor(rng.standard_normal((n_cols, d)).astype(np.float32)).to(DEV)
-    Z = torch.tensor(rng.standard_normal((n_rows, d)).astype(np.float32)).to(DEV)
-    want = ops.spmm_raw(a, X)
-    want_z = ops.spmm_raw(a, X, epilogue=ops.spmm_epilogue(ops.EPI_NONE, 0.5, Z))
-    for H in (1, 100, 20000, n_cols, n_cols + 7):
-        got = ops.spmm_raw(a, X, epilogue=ops.spmm_epilogue(ops.EPI_NONE, x_nt_from_row=H))
-        assert torch.equal(got, want), H
-        got_z = ops.spmm_raw(a, X, epilogue=ops.spmm_epilogue(ops.EPI_NONE, 0.5, Z, x_nt_from_row=H))
-        assert torch.equal(got_z, want_z), H
 
 
 def test_spmm_general_values_and_strided_operands(ops):
@@ -580,9 +552,11 @@ def test_bpr_select_and_backward_in_one_launch(ops, drop, cap, valid, d):
 @pytest.mark.parametrize("d,weighted,n_rows", [(448, False, 30000), (448, True, 30000), (64, False, 150000), (192, True, 25000), (20, False, 70000)])
 def test_spmm_pipelined_short_rows_equal_one_task_per_lane_group(ops, d, weighted, n_rows):
     """Round 6: the lane-group bucket's tasks as software pipelines (a lane group takes up to 8 tasks and keeps the next task's indices and
-    the one after's row pointers in flight) against one task per lane group (epilogue.no_pipeline): the same bits - plain and with the
-    "+ Z" epilogue, pattern-only and weighted (col_scale: the transposed products of the step's backward), sliced and unsliced operands,
-    float4 and scalar rows (d = 20), with and without the plan's permuted CSR, empty rows and every long-row bucket included."""
+    the one after's row pointers in flight) against one task per lane group running the plain per-chunk loop: the same bits - plain and
+    with the "+ Z" epilogue, pattern-only and weighted (col_scale: the transposed products of the step's backward), sliced and unsliced
+    operands, float4 and scalar rows (d = 20), with and without the plan's permuted CSR, empty rows and every long-row bucket included.
+    The one-task side is the masked kernel under an all-active operand mask: a masked product never pipelines, and with every column active
+    it visits the same columns in the same ascending order with the same weights, pads with the same +0 terms and finishes rows alike."""
     rng = np.random.default_rng(d + int(weighted))
     n_cols = 5000
     degs = rng.integers(0, 34, size=n_rows)
@@ -601,12 +575,14 @@ def test_spmm_pipelined_short_rows_equal_one_task_per_lane_group(ops, d, weighte
     sw, pl = a.plan_for(d)
     assert pl.slot_row is not None and n_rows * (d // sw if sw else 1) > 2 * 32 * 1024         # enough tasks for several per lane group
     _, key = ops.spmm_shape(d, a.nnz)
+    stamp = 3
+    all_active = torch.full((n_cols,), stamp, dtype=torch.uint8, device=DEV)
     for plan in (pl, ops.SpmmPlan.build(rp, *key)):
         a.plans[key] = plan
         for z in (None, Z):
-            mk = lambda off: ops.spmm_epilogue(ops.EPI_NONE, 0.5 if z is not None else 0.0, z, no_pipeline=off)
-            y_pipe = ops.spmm_raw(a, X, epilogue=mk(False))
-            y_task = ops.spmm_raw(a, X, epilogue=mk(True))
+            mk = lambda **mask: ops.spmm_epilogue(ops.EPI_NONE, 0.5 if z is not None else 0.0, z, **mask)
+            y_pipe = ops.spmm_raw(a, X, epilogue=mk())
+            y_task = ops.spmm_raw(a, X, epilogue=mk(x_row_mask=all_active, x_mask_active=stamp))
             assert torch.equal(y_pipe.view(torch.int32), y_task.view(torch.int32)), (d, weighted, plan is pl, z is not None)
     A64 = torch.sparse_coo_tensor(torch.tensor(np.vstack([rows, cols])), torch.ones(len(rows), dtype=torch.float64), (n_rows, n_cols))
     want = torch.sparse.mm(A64, X.cpu().double() * (cs.cpu().double()[:, None] if weighted else 1.0)) * rs.cpu().double()[:, None]

@@ -29,7 +29,7 @@ def _tensors(n):
 def test_rows_group_entry_point_is_declared():
     protos = _lib.parse_header()
     assert "llmrec_step_rows_group_f32" in protos and len(protos["llmrec_step_rows_group_f32"][1]) == 21
-    assert _lib.CONST["LLMREC_ABI_VERSION"] == 7
+    assert _lib.CONST["LLMREC_ABI_VERSION"] == 8
     chunk = _lib.CONST["LLMREC_ADAMW_CHUNK"]
     assert chunk >= 1024 and chunk % 1024 == 0            # whole float4 rounds of a 256-thread block
 

@@ -22,7 +22,7 @@ def test_header_and_library_carry_the_wide_entry_points():
     assert "llmrec_topk_eval_sums_wide" not in protos           # the wide evaluation sums sit behind llmrec_topk_eval_sums
     assert CONST["LLMREC_TOPK_WIDE_MAX"] == 1024
     assert CONST["LLMREC_TOPK_MAX"] == 64 and CONST["LLMREC_TOPK_PREFILTER_MAX_K"] == 56
-    assert CONST["LLMREC_ABI_VERSION"] == 7
+    assert CONST["LLMREC_ABI_VERSION"] == 8
 
 
 def _wide(lib, n_query=4, q=0x1000, Eu=0x2000, Ei=0x3000, K=100, ws=None, ws_bytes=0, mode=0, train_nnz=0, d=64, n_items=500):

@@ -18,8 +18,7 @@ from llmrec_amd import ops, synth
 
 variant = sys.argv[1] if len(sys.argv) > 1 else "std"
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-# round 6: LLMREC_XCD=1 -> the XCD-contiguous block -> row map (llmrec_spmm_epilogue_t.xcd_contiguous), LLMREC_DIR=iu -> Y = A_iu X
-XCD = os.environ.get("LLMREC_XCD", "0") == "1"
+# LLMREC_DIR=iu -> Y = A_iu X
 DIR = os.environ.get("LLMREC_DIR", "ui")
 dev = torch.device("cuda")
 U, I, E, d = 2_000_000, 1_000_000, 40_000_000, 64
@@ -117,19 +116,13 @@ nnz = gr.ui.fwd.nnz
 del rows, cols
 a = gr.ui.fwd if DIR == "ui" else gr.iu.fwd
 X = torch.randn(a.n_cols, d, device=dev); Y = torch.empty(a.n_rows, d, device=dev)
-epi = ops.spmm_epilogue(xcd_contiguous=True) if XCD else None
-if XCD:                                                       # the other block -> row map: the same bits
-    Y0 = ops.spmm_raw(a, X)
-    ops.spmm_raw(a, X, out=Y, epilogue=epi)
-    assert torch.equal(Y0.view(torch.int32), Y.view(torch.int32)), "xcd_contiguous changed the result"
-    del Y0
-for _ in range(2): ops.spmm_raw(a, X, out=Y, epilogue=epi)
+for _ in range(2): ops.spmm_raw(a, X, out=Y)
 torch.cuda.synchronize()
 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 s.record()
-for _ in range(iters): ops.spmm_raw(a, X, out=Y, epilogue=epi)
+for _ in range(iters): ops.spmm_raw(a, X, out=Y)
 e.record(); torch.cuda.synchronize()
 ms = s.elapsed_time(e) / iters
 alg = 4.0 * nnz + 8.0 * a.n_rows + 4.0 * d * (a.n_cols + a.n_rows)
-print("LOCALITY %s dir %s xcd %d nnz %d ms %.4f Gedges/s %.2f frac_hbm_algorithmic %.3f gather_GBs %.0f alg_GB %.3f" % (
-    variant, DIR, int(XCD), nnz, ms, nnz / ms / 1e6, alg / ms / 1e6 / 8000.0, nnz * 4.0 * d / ms / 1e6, alg / 1e9))
+print("LOCALITY %s dir %s nnz %d ms %.4f Gedges/s %.2f frac_hbm_algorithmic %.3f gather_GBs %.0f alg_GB %.3f" % (
+    variant, DIR, nnz, ms, nnz / ms / 1e6, alg / ms / 1e6 / 8000.0, nnz * 4.0 * d / ms / 1e6, alg / 1e9))
