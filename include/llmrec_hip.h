@@ -369,6 +369,15 @@ int llmrec_fuse_fwd_multi_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_
  * llmrec_bpr_multi_losses_assemble_f32. Replaces the four llmrec_sumsq_f32 launches of a step. */
 int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_t* problems_host, int32_t d, int32_t n_sumsq_terms,
                                     float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host, llmrec_stream_t stream);
+/* The same launch with ONE more block in front, which does the second half of llmrec_batch_reach_rows: it turns the byte flags
+ * (n_users bytes, 16-byte aligned and readable up to n_users rounded up to 16) into the ascending row_list (n_users + 32 entries, the
+ * same padding entries), writes *n_rows and leaves the flags all-zero. The fusion's outputs and partial sums are those of
+ * llmrec_fuse_fwd_multi_sumsq_f32, bit for bit; the list's reader runs at the far end of the step, so the compaction hides behind the
+ * fusion's blocks. Only the float4 row family (d % 4 == 0, 16-byte aligned rows, d <= 512) is compiled: any other shape returns
+ * LLMREC_EUNSUPPORTED before anything is launched, and the caller issues the two separate calls. */
+int llmrec_fuse_fwd_multi_sumsq_compact_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_t* problems_host, int32_t d, int32_t n_sumsq_terms,
+                                            float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host,
+                                            int64_t n_users, uint8_t* flags, int32_t* row_list, int32_t* n_rows, llmrec_stream_t stream);
 typedef struct {
     int64_t rows; const float* dOut; int64_t lddo;
     int32_t n_norm; const float* const* norm_terms; const int64_t* norm_ld; const float* rates;
@@ -465,6 +474,15 @@ int llmrec_bpr_multi_fwd_sharded_f32(int32_t n_problems, const llmrec_bpr_proble
 #define LLMREC_BPR_PLAN_WORDS(B) (5 * (B))         /* 64-bit words of `plan`: 3 B keys + 3 B int32 run lengths */
 int llmrec_bpr_scatter_plan(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B_max, const int32_t* n_valid_dev,
                             uint64_t* plan, llmrec_stream_t stream);
+/* llmrec_bpr_scatter_plan AND the marking half of llmrec_batch_reach_rows in ONE launch: the plan's blocks come first, the marking
+ * blocks behind them. Both read the batch only and neither reads what the other writes; on one stream the flags then cost no launch of
+ * their own. The plan is llmrec_bpr_scatter_plan's; flags (n_users bytes, 16-byte aligned, all-zero on entry) are left as
+ * llmrec_batch_reach_rows' first launch leaves them: non-zero at the batch's users and at every user adjacent to one of its valid
+ * items. item_rowptr / item_colidx: the by-item CSR. The list is then made by llmrec_fuse_fwd_multi_sumsq_compact_f32 (or any compaction
+ * of the flags). B_max > LLMREC_BPR_MAX_B: LLMREC_EUNSUPPORTED, nothing launched. */
+int llmrec_bpr_scatter_plan_reach_mark(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B_max, const int32_t* n_valid_dev,
+                                       uint64_t* plan, int64_t n_users, int64_t n_items, const int32_t* item_rowptr,
+                                       const int32_t* item_colidx, uint8_t* flags, llmrec_stream_t stream);
 int llmrec_bpr_multi_bwd_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
                              const int64_t* users, const int64_t* pos, const int64_t* neg,
                              int32_t B_max, const int32_t* n_valid_dev, float decay, float batch_size_flag,
@@ -805,6 +823,16 @@ int llmrec_sample_batch(uint64_t seed, uint64_t* step_dev, int64_t n_exist_users
                         int32_t B_global, int32_t slice_begin, int32_t B, int32_t n_aug,
                         const int64_t* aug_pos, const int64_t* aug_neg,
                         int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_valid_dev, llmrec_stream_t stream);
+/* The same batch, counter and n_valid by ceil(B / 256) + 1 blocks on as many CUs: 256 BPR slots per block, and one block that draws the
+ * augmented triples on its own (it recomputes the users of its chosen slots instead of reading what the other blocks write). ticket:
+ * one int32 of device memory, ZERO before the first call; every block increments it after its last use of *step_dev and the block that
+ * draws the last ticket advances *step_dev and puts the ticket back to 0 (no block waits for another; graph replays need no host
+ * action). One ticket word per sampler: calls that share it must be ordered on a stream. */
+int llmrec_sample_batch_wide(uint64_t seed, uint64_t* step_dev, int64_t n_exist_users, const int64_t* exist_users,
+                             int64_t n_items, const int32_t* train_rowptr, const int32_t* train_colidx,
+                             int32_t B_global, int32_t slice_begin, int32_t B, int32_t n_aug,
+                             const int64_t* aug_pos, const int64_t* aug_neg,
+                             int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_valid_dev, int32_t* ticket, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`; nothing on the product path calls it). One single-lane launch that

@@ -4,6 +4,7 @@
 // Replaces nn.Softmax / torch.mean(torch.stack) / F.normalize + scaled adds (reference
 // Models.py:176-177,185-197), (x**2).sum() (main.py:151-156) and AdamW.step (main.py:100-104,278).
 #include "common.h"
+#include "reach.h"
 #include <type_traits>
 
 namespace llmrec {
@@ -235,10 +236,9 @@ struct FuseMulti {
     for (int64_t row = (int64_t)blk * ROWS_PER_BLOCK + threadIdx.x / RL; row < rows; row += row_stride)
 
 template <int VEC, int NCHUNK>
-__global__ __launch_bounds__(256) void fuse_fwd_multi_kernel(int d, FuseMulti m) {
-    __shared__ float ss_red[256];
+__device__ __forceinline__ void fuse_fwd_multi_block(int vb, int nvb, int d, const FuseMulti& m, float* ss_red) {
     float ss = 0.f;                                                     // this thread's share of sum ||x||^2 over the first n_sumsq terms
-    ROW_LOOP_MULTI(m, (int)blockIdx.x, (int)gridDim.x) {
+    ROW_LOOP_MULTI(m, vb, nvb) {
         RowReg<VEC, NCHUNK> acc, t;
         acc.fill(0.f);
         for (int i = 0; i < a.n_mean; ++i) {
@@ -272,8 +272,14 @@ __global__ __launch_bounds__(256) void fuse_fwd_multi_kernel(int d, FuseMulti m)
             if ((int)threadIdx.x < off) ss_red[threadIdx.x] += ss_red[threadIdx.x + off];
             __syncthreads();
         }
-        if (threadIdx.x == 0) m.sumsq_partial[blockIdx.x] = ss_red[0];
+        if (threadIdx.x == 0) m.sumsq_partial[vb] = ss_red[0];
     }
+}
+
+template <int VEC, int NCHUNK>
+__global__ __launch_bounds__(256) void fuse_fwd_multi_kernel(int d, FuseMulti m) {
+    __shared__ float ss_red[256];
+    fuse_fwd_multi_block<VEC, NCHUNK>((int)blockIdx.x, (int)gridDim.x, d, m, ss_red);
 }
 
 // (accumulate == 2 semantics of fuse_bwd_kernel: d_terms[t] = s_terms[t] (or 0) + the term's gradient)
@@ -690,26 +696,11 @@ __global__ __launch_bounds__(256) void mark_neighbours_kernel(int64_t n, const i
 // the byte flags into the ascending list (each thread owns a contiguous 16-aligned run of rows: count, block-wide exclusive scan,
 // write) and clears them again, so the scratch is all-zero between calls and nothing needs a stamp.
 // ---------------------------------------------------------------------------------------------
-constexpr int REACH_SPLIT = 8;                             // wavefronts per (sample, item): a hub item's adjacency list is walked in 8 interleaved parts
 __global__ __launch_bounds__(256) void batch_reach_mark_kernel(int B_cap, const int32_t* __restrict__ n_valid, const int64_t* __restrict__ users,
                                                                const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, int64_t n_users,
                                                                int64_t n_items, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                                                uint8_t* __restrict__ flags) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    int nv = n_valid ? *n_valid : B_cap;
-    nv = nv < B_cap ? nv : B_cap;
-    const int part = w % REACH_SPLIT, job = w / REACH_SPLIT;
-    const int b = job / 3, role = job - 3 * b;
-    if (b >= nv) return;
-    if (role == 0) {
-        const int64_t u = users[b];
-        if (part == 0 && lane == 0 && u >= 0 && u < n_users) flags[u] = 1;
-        return;
-    }
-    const int64_t it = role == 1 ? pos[b] : neg[b];
-    if (it < 0 || it >= n_items) return;
-    const int32_t s = rowptr[it], e = rowptr[it + 1];
-    for (int32_t k = s + part * 64 + lane; k < e; k += 64 * REACH_SPLIT) flags[colidx[k]] = 1;
+    batch_reach_mark_block((int)blockIdx.x, B_cap, n_valid, users, pos, neg, n_users, n_items, rowptr, colidx, flags);   // reach.h
 }
 
 // ONE block of 1024 threads: thread t owns the 16-aligned run of `per` rows starting at t * per; count, block-wide exclusive scan
@@ -749,6 +740,92 @@ __global__ __launch_bounds__(1024) void flags_compact_kernel(int64_t n, uint8_t*
     const int32_t pad_end = (total + 15) / 16 * 16 + 16;
     for (int32_t k = total + tid; k < pad_end; k += 1024) list[k] = 0;
     if (tid == 0) *n_out = total;
+}
+
+// flags_compact_kernel's work in ONE block of 256 threads that rides in front of the fusion's blocks (llmrec_fuse_fwd_multi_sumsq_compact_f32):
+// the flags are taken in tiles of 256 x wpt 16-byte words (wpt <= COMPACT_WPT, thread t owns wpt consecutive words of the tile), and a
+// thread keeps its words IN REGISTERS from the counting pass: the ids are written from them and the flags are cleared with 16-byte
+// stores - no byte-wise second pass over the flags interleaved with stores into them. Tiles ascend and so do the threads' runs in a
+// tile: the list is the ascending one, the padding behind it and the count are flags_compact_kernel's.
+constexpr int COMPACT_WPT = 8;
+__device__ __forceinline__ void flags_compact_block256(int64_t n, uint8_t* __restrict__ flags, int32_t* __restrict__ list, int32_t* __restrict__ n_out,
+                                                       int32_t* wave_total /* 4 ints of LDS */) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n_words = (n + 15) / 16;
+    int64_t wpt64 = (n_words + 255) / 256;
+    const int wpt = wpt64 > COMPACT_WPT ? COMPACT_WPT : (int)wpt64;
+    int32_t done = 0;                                                   // ids written by the tiles before this one (block-uniform)
+    for (int64_t w0 = 0; w0 < n_words; w0 += 256 * (int64_t)wpt) {      // block-uniform trip count
+        uint4 v[COMPACT_WPT];
+        const int64_t mine = w0 + (int64_t)tid * wpt;
+        int32_t c = 0;
+#pragma unroll
+        for (int j = 0; j < COMPACT_WPT; ++j) {
+            v[j] = uint4{0u, 0u, 0u, 0u};
+            const int64_t wd_i = mine + j;
+            if (j < wpt && wd_i < n_words) {
+                v[j] = *reinterpret_cast<const uint4*>(flags + 16 * wd_i);   // (the allocation is readable up to n rounded up to 16 bytes)
+                const int64_t left = n - 16 * wd_i;                       // the tail word: bytes past n do not count
+                uint32_t wd[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+                if (left < 16) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int bb = 0; bb < 4; ++bb)
+                            if (4 * q + bb >= left) wd[q] &= ~(0xffu << (8 * bb));
+                    v[j] = uint4{wd[0], wd[1], wd[2], wd[3]};
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int bb = 0; bb < 4; ++bb) c += ((wd[q] >> (8 * bb)) & 0xffu) != 0u;
+            }
+        }
+        int32_t incl = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) wave_total[wave] = incl;
+        __syncthreads();
+        int32_t base = 0, total = 0;
+#pragma unroll
+        for (int w2 = 0; w2 < 4; ++w2) { const int32_t t = wave_total[w2]; if (w2 < wave) base += t; total += t; }
+        __syncthreads();                                                 // wave_total is free for the next tile
+        int32_t o = done + base + incl - c;
+        if (c) {
+#pragma unroll
+            for (int j = 0; j < COMPACT_WPT; ++j) {
+                const uint32_t wd[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+                if ((wd[0] | wd[1] | wd[2] | wd[3]) == 0u) continue;
+                const int64_t r = 16 * (mine + j);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int bb = 0; bb < 4; ++bb)
+                        if ((wd[q] >> (8 * bb)) & 0xffu) list[o++] = (int32_t)(r + 4 * q + bb);
+                // clear: bytes past n in the tail word were masked out of v[j] above and are written back as they were read
+                const int64_t left = n - r;
+                if (left >= 16) *reinterpret_cast<uint4*>(flags + r) = uint4{0u, 0u, 0u, 0u};
+                else for (int64_t bb = 0; bb < left; ++bb) flags[r + bb] = 0;
+            }
+        }
+        done += total;
+    }
+    const int32_t pad_end = (done + 15) / 16 * 16 + 16;                  // the entries a 16-wide tile past the end may fetch: defined values
+    for (int32_t k = done + tid; k < pad_end; k += 256) list[k] = 0;
+    if (tid == 0) *n_out = done;
+}
+
+// Block 0: the reach flags -> the ascending row list (and the flags cleared); blocks 1 ...: the fusion's blocks, as fuse_fwd_multi_kernel
+// numbers them. The list's reader (the row-listed weight gradient) runs at the far end of the step.
+template <int VEC, int NCHUNK>
+__global__ __launch_bounds__(256) void fuse_fwd_multi_compact_kernel(int d, FuseMulti m, int64_t n_flags, uint8_t* __restrict__ flags,
+                                                                     int32_t* __restrict__ list, int32_t* __restrict__ n_out) {
+    __shared__ float ss_red[256];
+    if (blockIdx.x == 0) { flags_compact_block256(n_flags, flags, list, n_out, reinterpret_cast<int32_t*>(ss_red)); return; }
+    fuse_fwd_multi_block<VEC, NCHUNK>((int)blockIdx.x - 1, (int)gridDim.x - 1, d, m, ss_red);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -945,9 +1022,10 @@ int llmrec_fuse_fwd_multi_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_
     return llmrec_fuse_fwd_multi_sumsq_f32(n_problems, p, d, 0, nullptr, 0, nullptr, stream_);
 }
 
-int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_t* p, int32_t d, int32_t n_sumsq_terms,
-                                    float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host, llmrec_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// flags != NULL: the launch carries the reach flags' compaction as its block 0 (llmrec_fuse_fwd_multi_sumsq_compact_f32)
+static int fuse_fwd_multi_launch(int32_t n_problems, const llmrec_fuse_fwd_problem_t* p, int32_t d, int32_t n_sumsq_terms,
+                                 float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host,
+                                 int64_t n_flags, uint8_t* flags, int32_t* row_list, int32_t* n_rows, hipStream_t stream) {
     LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= FUSE_MAX_PROBLEMS && p && d > 0, "fuse_fwd_multi: 1..%d problems", FUSE_MAX_PROBLEMS);
     LLMREC_CHECK_ARG(n_sumsq_terms >= 0 && (n_sumsq_terms == 0 || (sumsq_partial && n_partial_host)), "fuse_fwd_multi: sum of squares without a partial buffer");
     FuseMulti m = {};
@@ -982,6 +1060,14 @@ int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_pr
         *n_partial_host = grid;
         m.n_sumsq = n_sumsq_terms; m.sumsq_partial = sumsq_partial;
     }
+    if (flags) {                                                        // block 0 compacts; a shape outside the float4 family is refused before the launch
+        int rc = dispatch_rows(d, vec4,
+            [&](auto nc) { fuse_fwd_multi_compact_kernel<4, decltype(nc)::value><<<grid + 1, 256, 0, stream>>>(d, m, n_flags, flags, row_list, n_rows); return 0; },
+            [&](auto) { set_error("fuse_fwd_multi_sumsq_compact: d = %d with rows that are not 16-byte aligned", d); return (int)LLMREC_EUNSUPPORTED; });
+        if (rc) return rc;
+        LLMREC_LAUNCH_CHECK();
+        return LLMREC_OK;
+    }
     if (grid == 0) return LLMREC_OK;
     int rc = dispatch_rows(d, vec4,
         [&](auto nc) { fuse_fwd_multi_kernel<4, decltype(nc)::value><<<grid, 256, 0, stream>>>(d, m); return 0; },
@@ -989,6 +1075,22 @@ int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_pr
     if (rc) return rc;
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
+}
+
+int llmrec_fuse_fwd_multi_sumsq_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_t* p, int32_t d, int32_t n_sumsq_terms,
+                                    float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host, llmrec_stream_t stream_) {
+    return fuse_fwd_multi_launch(n_problems, p, d, n_sumsq_terms, sumsq_partial, partial_capacity, n_partial_host, 0, nullptr, nullptr, nullptr,
+                                 (hipStream_t)stream_);
+}
+
+int llmrec_fuse_fwd_multi_sumsq_compact_f32(int32_t n_problems, const llmrec_fuse_fwd_problem_t* p, int32_t d, int32_t n_sumsq_terms,
+                                            float* sumsq_partial, int32_t partial_capacity, int32_t* n_partial_host,
+                                            int64_t n_users, uint8_t* flags, int32_t* row_list, int32_t* n_rows, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(n_users > 0 && n_users < 0x7fffffffll, "fuse_fwd_multi_sumsq_compact: bad sizes");
+    LLMREC_CHECK_ARG(flags && row_list && n_rows, "fuse_fwd_multi_sumsq_compact: null pointer");
+    LLMREC_CHECK_ARG((uintptr_t)flags % 16 == 0, "fuse_fwd_multi_sumsq_compact: flags must be 16-byte aligned (and readable up to n_users rounded up to 16 bytes)");
+    return fuse_fwd_multi_launch(n_problems, p, d, n_sumsq_terms, sumsq_partial, partial_capacity, n_partial_host, n_users, flags, row_list, n_rows,
+                                 (hipStream_t)stream_);
 }
 
 // the argument block of the paired fusion backward: m, whether every pointer / ld allows 16-byte accesses, and the block count
@@ -1238,7 +1340,7 @@ int llmrec_batch_reach_rows(int64_t n_users, int64_t n_items, const int64_t* use
     LLMREC_CHECK_ARG((uintptr_t)flags % 16 == 0, "batch_reach_rows: flags must be 16-byte aligned (and readable up to n_users rounded up to 16 bytes)");
     hipStream_t stream = (hipStream_t)stream_;
     if (B_cap > 0) {
-        batch_reach_mark_kernel<<<(unsigned)ceil_div(3 * (int64_t)B_cap * REACH_SPLIT, 4), 256, 0, stream>>>(B_cap, n_valid, users, pos, neg, n_users, n_items,
+        batch_reach_mark_kernel<<<(unsigned)reach_mark_blocks(B_cap), 256, 0, stream>>>(B_cap, n_valid, users, pos, neg, n_users, n_items,
                                                                                                 item_rowptr, item_colidx, flags);
         LLMREC_LAUNCH_CHECK();
     }

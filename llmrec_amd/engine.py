@@ -94,9 +94,14 @@ class DeviceBatcher:
         self.seed = seed
         self.capacity = self.B + self.n_aug
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=exist_users.device)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=exist_users.device)   # llmrec_sample_batch_wide's block count-off (left at 0)
 
     def fill(self, users, pos, neg, n_valid):
         """Sample the next step's batch into the given buffers (capacity entries each); advances the device counter."""
+        if self.world == 1:                                  # several blocks on as many CUs (the replicas' slices keep the one-block launch)
+            ops.sample_batch_wide(self.seed, self.step_dev, self.exist_users, self.n_items, self.train, self.B, 0, self.B, self.n_aug,
+                                  self.aug_pos, self.aug_neg, users, pos, neg, n_valid, self.ticket)
+            return
         ops.sample_batch(self.seed, self.step_dev, self.exist_users, self.n_items, self.train, self.B * self.world,
                          self.rank * self.B, self.B, self.n_aug, self.aug_pos, self.aug_neg, users, pos, neg, n_valid)
 

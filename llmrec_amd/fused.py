@@ -217,6 +217,7 @@ class FusedStep:
             self.ss_partial = torch.zeros(self.ss_cap, dtype=torch.float32, device=dev)
             self.ss_n = 0
         self._ev_plan = self._ev_reach = None                 # four streams: the scatter plan / the row list are ready (step_eager)
+        self._reach_pending = None                            # one stream: the batch whose reach flags are marked and wait for the fusion launch
         self._zero_in_forward = False                         # set by step_eager: forward() alone (evaluation) must not advance AdamW
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
@@ -432,7 +433,15 @@ class FusedStep:
         problem(arr[1], self.E_u, m.user_id_embedding.weight, self.Ul, self.U_cat, self.prof_u)
         if self.fold and self._zero_in_forward:                          # + the regulariser's sum of squares over the image / text streams (terms 0, 1)
             n_part = _c.c_int32(0)
-            _call("llmrec_fuse_fwd_multi_sumsq_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part))
+            pending, self._reach_pending = self._reach_pending, None
+            if pending is not None and _lib.call_unless_unsupported(         # + the reach flags' compaction as the launch's first block
+                    "llmrec_fuse_fwd_multi_sumsq_compact_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part),
+                    self.iu.fwd.n_cols, _p(self.act_flags), _p(self.act_rows), _p(self.act_n), ops._stream()):
+                pending = None
+            else:
+                _call("llmrec_fuse_fwd_multi_sumsq_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part))
+            if pending is not None:                                      # refused: the list by its own two launches (marking again changes nothing)
+                ops.batch_reach_rows(*pending, self.iu.fwd, self.act_flags, self.act_rows, self.act_n)
             self.ss_n = int(n_part.value)
         else:
             _call("llmrec_fuse_fwd_multi_f32", 2, arr, d)
@@ -843,6 +852,17 @@ class FusedStep:
             # event, the loss launches for the plan's (self._ev_plan), the weight gradient for the list's (self._ev_reach). Round 6, one
             # box, 300 steps twice: 0.4539 / 0.4539 ms per step with both ahead of the SpMMs, 0.4470 / 0.4481 behind them
             # (profiles/experiments/r06_step_chain.md).
+            # One stream, a reach list and a device sampler in the step: the marking half of llmrec_batch_reach_rows rides behind the plan's
+            # blocks (llmrec_bpr_scatter_plan_reach_mark) and the compaction in front of the fusion's (forward()): two launches fewer on
+            # the stream. A refused shape launches nothing and today's calls run.
+            if self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream:
+                if users.numel() > self.b_max:
+                    raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (users.numel(), self.b_max))
+                if _lib.call_unless_unsupported("llmrec_bpr_scatter_plan_reach_mark", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid),
+                                                _p(self.bpr_plan), self.iu.fwd.n_cols, self.iu.fwd.n_rows, _p(self.iu.fwd.rowptr),
+                                                _p(self.iu.fwd.colidx), _p(self.act_flags), ops._stream()):
+                    self._reach_pending = (users, pos, neg, n_valid)
+                    return
             self.build_scatter_plan(users, pos, neg, n_valid)
             self._ev_plan = self._mark()
             if self.wgrad_rows:
@@ -869,6 +889,9 @@ class FusedStep:
         except Exception:
             if not torch.cuda.is_current_stream_capturing():   # the invariant of LLMREC_SPARSE_ZERO may be broken: restore it
                 try:
+                    if self._reach_pending is not None:        # marked, not yet compacted: the flags' all-zero invariant too
+                        self._reach_pending = None
+                        self.act_flags.zero_()
                     self.reset_scatter_targets()
                 except Exception:
                     pass

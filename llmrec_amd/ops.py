@@ -1268,6 +1268,18 @@ def sample_batch(seed: int, step_dev: torch.Tensor, exist_users: torch.Tensor, n
               B_global, slice_begin, B, n_aug, _p(aug_pos), _p(aug_neg), _p(users), _p(pos), _p(neg), _p(n_valid), _stream())
 
 
+def sample_batch_wide(seed: int, step_dev: torch.Tensor, exist_users: torch.Tensor, n_items: int, train: Csr, B_global: int,
+                      slice_begin: int, B: int, n_aug: int, aug_pos: Optional[torch.Tensor], aug_neg: Optional[torch.Tensor],
+                      users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_valid: torch.Tensor, ticket: torch.Tensor):
+    """llmrec_sample_batch_wide: sample_batch's outputs by several blocks; ticket (int32[1], device, zero before the first call) is the
+    word the blocks count themselves off on - the launch leaves it at zero."""
+    _need_gpu(step_dev, exist_users, users, pos, neg, n_valid, ticket)
+    if users.numel() < B + n_aug or step_dev.dtype != torch.int64 or n_valid.dtype != torch.int32 or ticket.dtype != torch.int32:
+        raise RuntimeError("sample_batch_wide: buffers of B + n_aug int64 entries, int64 step counter, int32 n_valid and ticket expected")
+    _lib.call("llmrec_sample_batch_wide", seed, _p(step_dev), exist_users.numel(), _p(exist_users), n_items, _p(train.rowptr), _p(train.colidx),
+              B_global, slice_begin, B, n_aug, _p(aug_pos), _p(aug_neg), _p(users), _p(pos), _p(neg), _p(n_valid), _p(ticket), _stream())
+
+
 def topk_metrics(idx: torch.Tensor, hits: torch.Tensor, query_users: torch.Tensor, test_rowptr: torch.Tensor, Ks) -> torch.Tensor:
     """Per-user [n, 4, len(Ks)] float64 (precision, recall, ndcg, hit_ratio) on the device (llmrec_topk_metrics)."""
     _need_gpu(idx, hits, query_users, test_rowptr)

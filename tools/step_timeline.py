@@ -11,7 +11,7 @@ rows = c.execute(sel).fetchall()
 # a step = the launches from one in-graph sampler launch up to the next one; inside a graph of several steps the projection and the
 # sampler are both first (either may start a few us ahead of the other): a projection launched within 40 us before the sampler
 # belongs to the sampler's step
-starts = [i for i, r in enumerate(rows) if "sample_batch_kernel" in r[0]]
+starts = [i for i, r in enumerate(rows) if "sample_batch_kernel" in r[0] or "sample_batch_wide_kernel" in r[0]]
 for k, i in enumerate(starts):
     j = i - 1
     while j >= 0 and rows[i][1] - rows[j][1] < 40000:
