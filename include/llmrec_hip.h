@@ -215,6 +215,47 @@ typedef struct {
 } llmrec_spmm_problem_t;
 int llmrec_spmm_multi_f32(int32_t n, const llmrec_spmm_problem_t* problems, llmrec_stream_t stream);
 
+/* llmrec_spmm_multi_f32 with a GUEST: one short, independent launch of the step whose blocks run as the FIRST blocks of the grouped
+ * SpMM launch (they start first; the problems' block ranges follow, shifted by the guest's block count) instead of holding the stream
+ * alone while most CUs idle. The guest descriptor is tagged and carries exactly the arguments of the guest's stand-alone entry point,
+ * which are checked as that entry point checks them:
+ *   LLMREC_SPMM_GUEST_SAMPLER     llmrec_sample_batch_wide               (512-thread blocks: ceil(B / 512) + 1)
+ *   LLMREC_SPMM_GUEST_PLAN_REACH  llmrec_bpr_scatter_plan_reach_mark     (32 keys / 8 marking wavefronts per block; 16 B_max B of LDS)
+ *   LLMREC_SPMM_GUEST_LOSSES      llmrec_bpr_multi_losses_assemble_f32   (one block: 8 wavefronts take two of the trees each)
+ * Every SpMM result and every guest output is bit for bit that of the separate calls: a row's, key's, slot's or tree's work and its order
+ * of additions do not depend on the block that holds it. No block waits for another one. The caller guarantees what it guarantees for
+ * two launches that may overlap: the guest reads nothing a problem writes and writes nothing a problem reads or writes.
+ * Compiled for the step's instance only - 16 lanes per row, float4, d (or the slice width) in 33..64, unmasked, unweighted or weighted.
+ * Returns LLMREC_EUNSUPPORTED, BEFORE anything is launched, for every other group (also one llmrec_spmm_multi_f32 would refuse, or
+ * without a non-empty problem), for a guest its body cannot take (B_max > LLMREC_BPR_MAX_B, an empty capacity) and for a plan whose LDS
+ * would cost the launch its occupancy (B_max > LLMREC_SPMM_GUEST_MAX_PLAN_B): the caller then issues the separate calls. n = 1 hosts the
+ * guest in a single product. Problems with split rows keep their finalize launch, without guest blocks. */
+#define LLMREC_SPMM_GUEST_SAMPLER 1
+#define LLMREC_SPMM_GUEST_PLAN_REACH 2
+#define LLMREC_SPMM_GUEST_LOSSES 3
+#define LLMREC_SPMM_GUEST_MAX_PLAN_B 3072
+typedef struct {                                   /* llmrec_sample_batch_wide */
+    uint64_t seed; uint64_t* step_dev; int64_t n_exist_users; const int64_t* exist_users;
+    int64_t n_items; const int32_t* train_rowptr; const int32_t* train_colidx;
+    int32_t B_global; int32_t slice_begin; int32_t B; int32_t n_aug;
+    const int64_t* aug_pos; const int64_t* aug_neg;
+    int64_t* users; int64_t* pos; int64_t* neg; int32_t* n_valid_dev; int32_t* ticket;
+} llmrec_guest_sampler_t;
+typedef struct {                                   /* llmrec_bpr_scatter_plan_reach_mark */
+    const int64_t* users; const int64_t* pos; const int64_t* neg; int32_t B_max; const int32_t* n_valid_dev;
+    uint64_t* plan; int64_t n_users; int64_t n_items; const int32_t* item_rowptr; const int32_t* item_colidx; uint8_t* flags;
+} llmrec_guest_plan_reach_t;
+typedef struct {                                   /* llmrec_bpr_multi_losses_assemble_f32 */
+    int32_t n_problems; int32_t B_max; const int32_t* n_valid_dev; double remember_rate; float decay; float batch_size_flag;
+    float* out; float* saved; const float* w_mf_host; const float* sumsq_partial; int32_t n_partial; float feat_reg_coef;
+    float* scal4; double* running_sums3;
+} llmrec_guest_losses_t;
+typedef struct {
+    int32_t kind;                                  /* LLMREC_SPMM_GUEST_* */
+    union { llmrec_guest_sampler_t sampler; llmrec_guest_plan_reach_t plan_reach; llmrec_guest_losses_t losses; } u;
+} llmrec_spmm_guest_t;
+int llmrec_spmm_multi_guest_f32(int32_t n, const llmrec_spmm_problem_t* problems, const llmrec_spmm_guest_t* guest, llmrec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * R4  side-feature projection            replaces nn.Linear forward / weight-grad
  *                                        (reference Models.py:30-37,145-150; aten::addmm, aten::mm)

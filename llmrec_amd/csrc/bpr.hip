@@ -4,7 +4,7 @@
 // (utility/load_data.py:157-195). One launch, no host synchronisation: the reference pays a
 // device->host->device round trip per bpr_loss call (8 per step, main.py:159).
 #include "common.h"
-#include "reach.h"
+#include "guests.h"
 
 namespace llmrec {
 
@@ -40,11 +40,6 @@ struct BprTables {
     float g_mf[LLMREC_BPR_MAX_PROBLEMS];
     float g_emb[LLMREC_BPR_MAX_PROBLEMS];
 };
-
-__device__ __forceinline__ int bpr_batch(const int32_t* n_valid_dev, int B_max) {
-    int B = n_valid_dev ? n_valid_dev[0] : B_max;
-    return B > B_max ? B_max : (B < 0 ? 0 : B);
-}
 
 // what "a new step begins" means on the device (one thread of the scores launch): a new row stamp and, when given, AdamW's step
 // counter / bias corrections (adamw_advance_kernel's arithmetic, rowops.hip)
@@ -224,89 +219,10 @@ __global__ __launch_bounds__(BPR_THREADS) void bpr_reduce_kernel(int B_max, cons
     bpr_reduce_problem(blockIdx.x, B_max, n_valid_dev, remember_rate, decay, bsz, out_all, saved_all, saved_stride, ga, red);
 }
 
-// The logged scalars of a fused step in ONE single-block launch (llmrec_bpr_multi_losses_assemble_f32): the loss values of every
-// problem, the feature regulariser from the fusion launch's per-block partial sums, and the assembly of llmrec_loss_assemble_f32
-// mode 0. Every sum is bpr_reduce_kernel's / block_tree_sum's: slot v of 1024 is the sum over b = v, v + 1024, ... in ascending order
-// from 0.f, then the pairwise tree red[i] += red[i + off], off = 512 ... 1. Here ONE WAVEFRONT owns a tree: lane l holds slots
-// l, l + 64, ..., l + 960 in 16 registers, levels 512 ... 64 are register adds r[j] += r[j + off / 64], levels 32 ... 1 are
-// __shfl_down adds (only lanes below `off` matter; lane 0 ends with red[0]) - the same additions on the same operands, so the bits of
-// out / saved / scal are those of the 1024-slot LDS tree, without its block barriers and its 32 KB of LDS. A round's 16 loads of a lane
-// are issued together: the LDS version, and this one while its loads sat in per-slot loops, waited for every load on its own (22 us
-// and 21 us on the step's stream against 8.6 us). The 4 n_prob + 1 trees are dealt to the block's 16 wavefronts.
-struct LossW { float w[LLMREC_BPR_MAX_PROBLEMS]; };
-constexpr int LA_WAVES = BPR_THREADS / 64;
-constexpr int LA_TREES = 4 * LLMREC_BPR_MAX_PROBLEMS + 1;
-__device__ __forceinline__ float wave_tree_sum_1024(const float* __restrict__ src, int n, int lane) {
-    float r[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) r[j] = 0.f;
-    for (int base = 0; base < n; base += BPR_THREADS) {                 // wavefront-uniform; a round's 16 loads are issued together
-        float x[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { const int b = base + lane + 64 * j; x[j] = b < n ? src[b] : 0.f; }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { const int b = base + lane + 64 * j; if (b < n) r[j] += x[j]; }   // (ascending b per slot, from 0.f)
-    }
-#pragma unroll
-    for (int h = 8; h > 0; h >>= 1) {
-#pragma unroll
-        for (int j = 0; j < h; ++j) r[j] += r[j + h];
-    }
-    float x = r[0];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
-__global__ __launch_bounds__(BPR_THREADS) void bpr_losses_assemble_kernel(int n_prob, int B_max, const int32_t* __restrict__ n_valid_dev,
-                                                                          double remember_rate, float decay, float bsz,
-                                                                          float* __restrict__ out_all, float* __restrict__ saved_all, int saved_stride,
-                                                                          LossW w, const float* __restrict__ partial, int n_partial, float reg_coef,
-                                                                          float* __restrict__ scal, double* __restrict__ running) {
-    __shared__ float tot_s[LA_TREES];                                   // [4 prob + col]: kept, Su, Sp, Sq; [4 n_prob]: the partials' sum
-    const int B = bpr_batch(n_valid_dev, B_max);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int n_trees = 4 * n_prob + (partial ? 1 : 0);
-    for (int tr = wv; tr < n_trees; tr += LA_WAVES) {                   // wavefront-uniform
-        const int tree = partial ? (tr == 0 ? 4 * n_prob : tr - 1) : tr;   // the partials' tree (the longest) is dealt first
-        float x;
-        if (tree == 4 * n_prob) {
-            x = wave_tree_sum_1024(partial, n_partial, lane);
-        } else {
-            const int prob = tree >> 2, col = tree & 3;                   // slots 1 (kept m_b), 2, 3, 4 (squared norms) of `saved`
-            x = wave_tree_sum_1024(saved_all + (int64_t)prob * saved_stride + B_max + 4 + (int64_t)(col + 1) * B_max, B, lane);
-        }
-        if (lane == 0) tot_s[tree] = x;
-    }
-    __syncthreads();                                                    // the one barrier: every tree's total is in LDS
-    if (wv != 0) return;
-    float mf = 0.f, emb = 0.f;
-    if (lane < n_prob) {
-        const int prob = lane;
-        float* saved = saved_all + (int64_t)prob * saved_stride;
-        float tot[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) tot[c] = tot_s[4 * prob + c];
-        const int k = (int)(remember_rate * (double)B);
-        mf = -(tot[0] / (float)k);                                       // k == 0 -> nan, as torch's empty mean
-        const float reg = 1.0f / (2.0f * tot[1] + 1e-8f) + 1.0f / (2.0f * tot[2] + 1e-8f) + 1.0f / (2.0f * tot[3] + 1e-8f);
-        emb = decay * (reg / bsz);
-        out_all[prob * 2 + 0] = mf; out_all[prob * 2 + 1] = emb;
-        saved[B_max + 0] = tot[1]; saved[B_max + 1] = tot[2]; saved[B_max + 2] = tot[3]; saved[B_max + 3] = (float)k;
-    }
-    float outs[LLMREC_BPR_MAX_PROBLEMS][2];
-#pragma unroll
-    for (int p = 0; p < LLMREC_BPR_MAX_PROBLEMS; ++p) { outs[p][0] = __shfl(mf, p, 64); outs[p][1] = __shfl(emb, p, 64); }
-    if (lane != 0) return;
-    float feat = scal[0];                                              // no partial sums: whatever llmrec_sumsq_f32 left there
-    if (partial) feat = reg_coef * tot_s[4 * n_prob];
-    float s = 0.f;
-#pragma unroll
-    for (int p = 0; p < LLMREC_BPR_MAX_PROBLEMS; ++p) if (p < n_prob) s += outs[p][0] * w.w[p];
-    scal[0] = feat;
-    scal[2] = outs[0][0]; scal[3] = outs[0][1];
-    scal[1] = s + outs[0][1] + feat;
-    if (running) { running[0] += (double)scal[1]; running[1] += (double)scal[2]; running[2] += (double)scal[3]; }
+// The logged scalars of a fused step in ONE single-block launch (llmrec_bpr_multi_losses_assemble_f32): guests.h's body, its
+// 4 n_prob + 1 trees dealt to the block's 16 wavefronts.
+__global__ __launch_bounds__(BPR_THREADS) void bpr_losses_assemble_kernel(LossesArgs a) {
+    guest_block<BPR_THREADS>(a, 0, nullptr);
 }
 
 // pass 1 of the batch-sharded forward: this rank's block of the gathered layout
@@ -351,63 +267,20 @@ __global__ __launch_bounds__(256) void bpr_pack_kernel(int n_prob, int B_max, co
 //                        compacted into LDS records, and the group then streams the records' rows four at a time.
 // Targets of different problems must be identical (same pointer, same leading dimension) or disjoint.
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t PLAN_NO_ID = 0xffffffffu;
-// vb: the block's index among the plan's ceil(B_max / 16) + ceil(2 B_max / 16) blocks; k: 2 B_max keys of LDS
-__device__ __forceinline__ void bpr_plan_block(int vb, uint64_t* k, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
-                                               const int64_t* __restrict__ neg, int B_max,
-                                               const int32_t* __restrict__ n_valid_dev, uint64_t* __restrict__ plan) {
-    const int B = bpr_batch(n_valid_dev, B_max);
-    const int nbu = (B_max + 15) / 16;
-    const bool items = vb >= nbu;
-    const int n = items ? 2 * B_max : B_max;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int b = (items && i >= B_max) ? i - B_max : i;
-        uint64_t id = PLAN_NO_ID;
-        if (b < B) id = (uint64_t)(items ? (i >= B_max ? neg[b] : pos[b]) : users[b]);
-        k[i] = (id << 32) | (uint64_t)(uint32_t)i;
-    }
-    __syncthreads();
-    const int gl = threadIdx.x & 15;
-    const int i = (vb - (items ? nbu : 0)) * 16 + (threadIdx.x >> 4);
-    if (i >= n) return;
-    const uint64_t me = k[i];
-    const uint32_t id = (uint32_t)(me >> 32);
-    int below = 0, lower_id = 0, same_id = 0;
-    for (int j = gl; j < n; j += 16) {
-        const uint64_t kj = k[j];
-        const uint32_t idj = (uint32_t)(kj >> 32);
-        below += kj < me; lower_id += idj < id; same_id += idj == id;
-    }
-    below = (int)group_sum<16>((float)below); lower_id = (int)group_sum<16>((float)lower_id); same_id = (int)group_sum<16>((float)same_id);   // < 2^24: exact
-    if (gl == 0) {
-        const int base = items ? B_max : 0;
-        plan[base + below] = me;
-        int32_t* runlen = reinterpret_cast<int32_t*>(plan + 3 * (int64_t)B_max);
-        runlen[base + below] = (below == lower_id && id != PLAN_NO_ID) ? same_id : 0;
-    }
-}
-
+// (bpr_plan_block and the plan + reach-mark body: guests.h)
 __global__ __launch_bounds__(256) void bpr_plan_kernel(const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
                                                        const int64_t* __restrict__ neg, int B_max,
                                                        const int32_t* __restrict__ n_valid_dev, uint64_t* __restrict__ plan) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    bpr_plan_block((int)blockIdx.x, reinterpret_cast<uint64_t*>(smem), users, pos, neg, B_max, n_valid_dev, plan);
+    bpr_plan_block<256>((int)blockIdx.x, reinterpret_cast<uint64_t*>(smem), users, pos, neg, B_max, n_valid_dev, plan);
 }
 
 // The scatter plan and the reach flags of one batch in ONE launch (llmrec_bpr_scatter_plan_reach_mark): blocks [0, plan_blocks) run
 // the plan's body, the blocks behind them llmrec_batch_reach_rows' marking body (reach.h). Both read the sampled batch only and
 // neither reads what the other writes, so the flags no longer cost a launch of their own on the step's one stream.
-__global__ __launch_bounds__(256) void bpr_plan_reach_mark_kernel(const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
-                                                                  const int64_t* __restrict__ neg, int B_max,
-                                                                  const int32_t* __restrict__ n_valid_dev, uint64_t* __restrict__ plan,
-                                                                  int plan_blocks, int64_t n_users, int64_t n_items,
-                                                                  const int32_t* __restrict__ item_rowptr, const int32_t* __restrict__ item_colidx,
-                                                                  uint8_t* __restrict__ flags) {
+__global__ __launch_bounds__(256) void bpr_plan_reach_mark_kernel(PlanReachArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < plan_blocks)                                   // block-uniform
-        bpr_plan_block((int)blockIdx.x, reinterpret_cast<uint64_t*>(smem), users, pos, neg, B_max, n_valid_dev, plan);
-    else
-        batch_reach_mark_block((int)blockIdx.x - plan_blocks, B_max, n_valid_dev, users, pos, neg, n_users, n_items, item_rowptr, item_colidx, flags);
+    guest_block<256>(a, (int)blockIdx.x, smem);
 }
 
 constexpr int RUN_MAX_SHARE = LLMREC_BPR_MAX_PROBLEMS;
@@ -693,88 +566,7 @@ __global__ __launch_bounds__(256) void bpr_bwd_rows_kernel(const float* __restri
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Philox4x32-10 counter-based generator (Salmon et al., SC'11)
-// ---------------------------------------------------------------------------------------------
-struct Philox {
-    uint32_t key[2];
-    __device__ Philox(uint64_t seed) { key[0] = (uint32_t)seed; key[1] = (uint32_t)(seed >> 32); }
-    __device__ void operator()(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out[4]) const {
-        uint32_t k0 = key[0], k1 = key[1];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-            k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-        }
-        out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-    }
-};
-
-__device__ __forceinline__ uint32_t bounded(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
-
-// Keyed bijection of [0, n): 4-round Feistel on 2h bits (2^(2h) >= n) with cycle walking.
-__device__ uint64_t keyed_perm(uint64_t x, uint64_t n, int half_bits, const Philox& ph, uint32_t step_lo, uint32_t step_hi) {
-    const uint64_t mask = (1ull << half_bits) - 1;
-    do {
-        uint64_t L = x >> half_bits, R = x & mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            uint32_t o[4];
-            ph((uint32_t)R, (uint32_t)(R >> 32) ^ (0xA5A50000u + r), step_lo, step_hi, o);
-            const uint64_t f = (((uint64_t)o[1] << 32) | o[0]) & mask;
-            const uint64_t nL = R, nR = L ^ f;
-            L = nL; R = nR;
-        }
-        x = (L << half_bits) | R;
-    } while (x >= n);
-    return x;
-}
-
-// one BPR triple of the global batch: user slot b of B (without replacement while B <= n_exist), a uniform
-// train item of that user, a uniform non-train item by rejection (binary search in the sorted row)
-__device__ __forceinline__ int64_t sample_user(const Philox& ph, uint32_t slo, uint32_t shi, int b, int B, int half_bits,
-                                               int64_t n_exist, const int64_t* __restrict__ exist_users) {
-    // users: without replacement while B <= n_exist (rd.sample), with replacement otherwise (rd.choice)
-    uint64_t slot;
-    if ((int64_t)B <= n_exist) {
-        slot = keyed_perm((uint64_t)b, (uint64_t)n_exist, half_bits, ph, slo, shi);
-    } else {
-        uint32_t o[4];
-        ph((uint32_t)b, 0x55AA0001u, slo, shi, o);
-        slot = ((((uint64_t)o[1] << 32) | o[0]) % (uint64_t)n_exist);
-    }
-    return exist_users[slot];
-}
-
-__device__ __forceinline__ void sample_one(const Philox& ph, uint32_t slo, uint32_t shi, int b, int B, int half_bits,
-                                           int64_t n_exist, const int64_t* __restrict__ exist_users, int64_t n_items,
-                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-                                           int64_t& u_out, int64_t& p_out, int64_t& q_out) {
-    const int64_t u = sample_user(ph, slo, shi, b, B, half_bits, n_exist, exist_users);
-    const int32_t s = rowptr[u], e = rowptr[u + 1];
-    uint32_t o[4];
-    ph((uint32_t)b, 0x55AA0002u, slo, shi, o);
-    const int64_t p = colidx[s + (int32_t)bounded(o[0], (uint32_t)(e - s))];
-    int64_t q = 0;
-    uint32_t ctr = 0;
-    int have = 4;
-    for (int tries = 0; tries < 4096; ++tries) {
-        if (have == 4) { ph((uint32_t)b, 0x55AA0003u + ctr, slo, shi, o); ++ctr; have = 0; }
-        const uint32_t r = o[have++];
-        q = n_items <= 0xffffffffll ? (int64_t)bounded(r, (uint32_t)n_items) : (int64_t)(r % (uint64_t)n_items);
-        int32_t lo = s, hi = e;                                         // binary search in the sorted row
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) >> 1;
-            if (colidx[mid] < q) lo = mid + 1; else hi = mid;
-        }
-        if (!(lo < e && colidx[lo] == q)) break;                        // not a train item: accept
-    }
-    u_out = u; p_out = p; q_out = q;
-}
-
+// (Philox4x32-10, the keyed permutation and sample_one: guests.h)
 __global__ void sample_bpr_kernel(uint64_t seed, uint64_t step, int64_t n_exist, const int64_t* __restrict__ exist_users,
                                   int64_t n_items, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                   int B, int half_bits, int64_t* __restrict__ users, int64_t* __restrict__ pos,
@@ -840,72 +632,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_batch_kernel(
     if (threadIdx.x == 0) { n_valid_dev[0] = B + kept; *step_dev = step + 1ull; }
 }
 
-// The same batch by SEVERAL blocks (llmrec_sample_batch_wide): the BPR slots go to 256-thread blocks - at B = 1024 no SIMD holds more
-// than one sampling wavefront, where the single block stacks four of them on one CU - and ONE further block draws the augmented triples
-// on its own: it recomputes the user of each chosen slot (the same keyed permutation / with-replacement draw that wrote users[slot], so
-// the same value) instead of waiting for the other blocks, compacts in draw order, pads and writes n_valid. Every block reads the step
-// first; after its last use it takes a ticket (device-scope atomic increment), and the block that draws the last one advances the
-// counter and puts the ticket word back to 0 - nobody waits for anybody, and a graph replay needs no host action.
+// The same batch by SEVERAL blocks (llmrec_sample_batch_wide): guests.h's body in 256-thread blocks.
 constexpr int SAMPLE_WIDE_THREADS = 256;
-__global__ __launch_bounds__(SAMPLE_WIDE_THREADS) void sample_batch_wide_kernel(
-    uint64_t seed, unsigned long long* step_dev, int64_t n_exist, const int64_t* __restrict__ exist_users,
-    int64_t n_items, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-    int B_global, int half_bits_users, int slice_begin, int B, int n_aug, int half_bits_batch,
-    const int64_t* __restrict__ aug_pos, const int64_t* __restrict__ aug_neg,
-    int64_t* __restrict__ users, int64_t* __restrict__ pos, int64_t* __restrict__ neg, int32_t* __restrict__ n_valid_dev,
-    int32_t* ticket, int n_blocks) {
-    __shared__ int wave_tot[SAMPLE_WIDE_THREADS / 64];
-    __shared__ int base_s;
-    const unsigned long long step = *step_dev;
-    const uint32_t slo = (uint32_t)step, shi = (uint32_t)(step >> 32);
-    const Philox ph(seed);
-    if ((int)blockIdx.x + 1 < n_blocks) {                               // block-uniform: 256 BPR slots
-        const int b = blockIdx.x * SAMPLE_WIDE_THREADS + threadIdx.x;
-        if (b < B)
-            sample_one(ph, slo, shi, slice_begin + b, B_global, half_bits_users, n_exist, exist_users, n_items, rowptr, colidx,
-                       users[b], pos[b], neg[b]);
-    } else {                                                            // the last block: the augmented triples
-        if (threadIdx.x == 0) base_s = 0;
-        __syncthreads();
-        const Philox pa(seed ^ 0x9E3779B97F4A7C15ull);
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        for (int a0 = 0; a0 < n_aug; a0 += SAMPLE_WIDE_THREADS) {       // block-uniform
-            const int a = a0 + threadIdx.x;
-            int64_t u = 0, ap = 0, an = 0;
-            bool ok = false;
-            if (a < n_aug) {
-                const uint64_t slot = keyed_perm((uint64_t)a, (uint64_t)B, half_bits_batch, pa, slo, shi);   // distinct slots of the slice
-                u = sample_user(ph, slo, shi, slice_begin + (int)slot, B_global, half_bits_users, n_exist, exist_users);   // = users[slot]
-                ap = aug_pos[u]; an = aug_neg[u];
-                ok = ap >= 0 && an >= 0 && ap < n_items && an < n_items;
-            }
-            const unsigned long long bal = __ballot(ok);
-            const int before = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_tot[wv] = __popcll(bal);
-            __syncthreads();
-            int wave_base = 0, chunk_tot = 0;
-            for (int k = 0; k < SAMPLE_WIDE_THREADS / 64; ++k) { const int t = wave_tot[k]; if (k < wv) wave_base += t; chunk_tot += t; }
-            const int base = base_s;
-            if (a < n_aug && ok) {
-                const int o = B + base + wave_base + before;
-                users[o] = u; pos[o] = ap; neg[o] = an;
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) base_s = base + chunk_tot;
-            __syncthreads();
-        }
-        const int kept = base_s;
-        for (int o = B + kept + threadIdx.x; o < B + n_aug; o += SAMPLE_WIDE_THREADS) { users[o] = 0; pos[o] = 0; neg[o] = 0; }   // padding (never read: beyond n_valid)
-        if (threadIdx.x == 0) n_valid_dev[0] = B + kept;
-    }
-    __syncthreads();                                                    // every thread of this block is done with the step's value
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(ticket, 1) == n_blocks - 1) {                     // the last block: every block has read the counter
-            *step_dev = step + 1ull;
-            atomicExch(ticket, 0);
-        }
-    }
+__global__ __launch_bounds__(SAMPLE_WIDE_THREADS) void sample_batch_wide_kernel(SamplerArgs a) {
+    guest_block<SAMPLE_WIDE_THREADS>(a, (int)blockIdx.x, nullptr);
 }
 
 }  // namespace llmrec
@@ -1037,7 +767,7 @@ int llmrec_bpr_scatter_plan(const int64_t* users, const int64_t* pos, const int6
     if (B_max > LLMREC_BPR_MAX_B) { set_error("bpr_scatter_plan: B_max %d > %d", B_max, LLMREC_BPR_MAX_B); return LLMREC_EUNSUPPORTED; }
     if (B_max == 0) return LLMREC_OK;
     LLMREC_CHECK_ARG(users && pos && neg && plan, "bpr_scatter_plan: null pointer");
-    const unsigned blocks = (unsigned)(ceil_div(B_max, 16) + ceil_div(2 * (int64_t)B_max, 16));
+    const unsigned blocks = (unsigned)plan_blocks_for(B_max, 256);
     bpr_plan_kernel<<<blocks, 256, sizeof(uint64_t) * 2 * (size_t)B_max, (hipStream_t)stream_>>>(users, pos, neg, B_max, n_valid_dev, plan);   // <= 64 KB of LDS
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
@@ -1046,15 +776,13 @@ int llmrec_bpr_scatter_plan(const int64_t* users, const int64_t* pos, const int6
 int llmrec_bpr_scatter_plan_reach_mark(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B_max, const int32_t* n_valid_dev,
                                        uint64_t* plan, int64_t n_users, int64_t n_items, const int32_t* item_rowptr,
                                        const int32_t* item_colidx, uint8_t* flags, llmrec_stream_t stream_) {
-    LLMREC_CHECK_ARG(B_max >= 0 && n_users > 0 && n_users < 0x7fffffffll && n_items > 0, "bpr_scatter_plan_reach_mark: bad sizes");
-    LLMREC_CHECK_ARG(item_rowptr && item_colidx && flags, "bpr_scatter_plan_reach_mark: null pointer");
-    if (B_max > LLMREC_BPR_MAX_B) { set_error("bpr_scatter_plan_reach_mark: B_max %d > %d", B_max, LLMREC_BPR_MAX_B); return LLMREC_EUNSUPPORTED; }
-    if (B_max == 0) return LLMREC_OK;
-    LLMREC_CHECK_ARG(users && pos && neg && plan, "bpr_scatter_plan_reach_mark: null pointer");
-    const int plan_blocks = (int)(ceil_div(B_max, 16) + ceil_div(2 * (int64_t)B_max, 16));
-    const unsigned blocks = (unsigned)(plan_blocks + reach_mark_blocks(B_max));
-    bpr_plan_reach_mark_kernel<<<blocks, 256, sizeof(uint64_t) * 2 * (size_t)B_max, (hipStream_t)stream_>>>(   // <= 64 KB of LDS
-        users, pos, neg, B_max, n_valid_dev, plan, plan_blocks, n_users, n_items, item_rowptr, item_colidx, flags);
+    const llmrec_guest_plan_reach_t g = {users, pos, neg, B_max, n_valid_dev, plan, n_users, n_items, item_rowptr, item_colidx, flags};
+    PlanReachArgs a;
+    int64_t blocks;
+    size_t shmem;
+    const int rc = guest_prepare(g, 256, "bpr_scatter_plan_reach_mark", a, blocks, shmem);
+    if (rc != LLMREC_OK || blocks == 0) return rc;
+    bpr_plan_reach_mark_kernel<<<(unsigned)blocks, 256, shmem, (hipStream_t)stream_>>>(a);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }
@@ -1151,15 +879,14 @@ int llmrec_bpr_multi_losses_assemble_f32(int32_t n_problems, int32_t B_max, cons
                                          float batch_size_flag, float* out, float* saved, const float* w_mf_host,
                                          const float* sumsq_partial, int32_t n_partial, float feat_reg_coef,
                                          float* scal4, double* running_sums3, llmrec_stream_t stream_) {
-    LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= LLMREC_BPR_MAX_PROBLEMS && B_max >= 0 && out && saved && w_mf_host && scal4,
-                     "bpr_multi_losses_assemble: bad argument");
-    LLMREC_CHECK_ARG(n_partial >= 0 && (n_partial == 0 || sumsq_partial), "bpr_multi_losses_assemble: partial sums without a buffer");
-    if (B_max > LLMREC_BPR_MAX_B) { set_error("bpr_multi_losses_assemble: B_max %d > %d", B_max, LLMREC_BPR_MAX_B); return LLMREC_EUNSUPPORTED; }
-    LossW w = {};
-    for (int i = 0; i < n_problems; ++i) w.w[i] = w_mf_host[i];
-    bpr_losses_assemble_kernel<<<1, BPR_THREADS, 0, (hipStream_t)stream_>>>(n_problems, B_max, n_valid_dev, remember_rate, decay, batch_size_flag, out, saved,
-                                                                           LLMREC_BPR_SAVED_FLOATS(B_max), w, n_partial > 0 ? sumsq_partial : nullptr,
-                                                                           n_partial, feat_reg_coef, scal4, running_sums3);
+    const llmrec_guest_losses_t g = {n_problems, B_max, n_valid_dev, remember_rate, decay, batch_size_flag, out, saved, w_mf_host, sumsq_partial,
+                                     n_partial, feat_reg_coef, scal4, running_sums3};
+    LossesArgs a;
+    int64_t blocks;
+    size_t shmem;
+    const int rc = guest_prepare(g, BPR_THREADS, "bpr_multi_losses_assemble", a, blocks, shmem);
+    if (rc != LLMREC_OK) return rc;
+    bpr_losses_assemble_kernel<<<1, BPR_THREADS, 0, (hipStream_t)stream_>>>(a);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }
@@ -1250,18 +977,14 @@ int llmrec_sample_batch_wide(uint64_t seed, uint64_t* step_dev, int64_t n_exist_
                              int32_t B_global, int32_t slice_begin, int32_t B, int32_t n_aug,
                              const int64_t* aug_pos, const int64_t* aug_neg,
                              int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_valid_dev, int32_t* ticket, llmrec_stream_t stream_) {
-    LLMREC_CHECK_ARG(B >= 1 && B_global >= B && slice_begin >= 0 && slice_begin + B <= B_global && n_aug >= 0 && n_aug <= B &&
-                     n_exist_users > 0 && n_items > 0, "sample_batch_wide: bad sizes");
-    LLMREC_CHECK_ARG(step_dev && exist_users && train_rowptr && train_colidx && users && pos && neg && n_valid_dev && ticket,
-                     "sample_batch_wide: null pointer");
-    LLMREC_CHECK_ARG(n_aug == 0 || (aug_pos && aug_neg), "sample_batch_wide: augmented pairs missing");
-    int hb_users = 1, hb_batch = 1;
-    while ((1ull << (2 * hb_users)) < (uint64_t)n_exist_users) ++hb_users;
-    while ((1ull << (2 * hb_batch)) < (uint64_t)B) ++hb_batch;
-    const int n_blocks = (int)ceil_div(B, SAMPLE_WIDE_THREADS) + 1;
-    sample_batch_wide_kernel<<<n_blocks, SAMPLE_WIDE_THREADS, 0, (hipStream_t)stream_>>>(
-        seed, (unsigned long long*)step_dev, n_exist_users, exist_users, n_items, train_rowptr, train_colidx, B_global, hb_users,
-        slice_begin, B, n_aug, hb_batch, aug_pos, aug_neg, users, pos, neg, n_valid_dev, ticket, n_blocks);
+    const llmrec_guest_sampler_t g = {seed, step_dev, n_exist_users, exist_users, n_items, train_rowptr, train_colidx, B_global, slice_begin, B,
+                                      n_aug, aug_pos, aug_neg, users, pos, neg, n_valid_dev, ticket};
+    SamplerArgs a;
+    int64_t blocks;
+    size_t shmem;
+    const int rc = guest_prepare(g, SAMPLE_WIDE_THREADS, "sample_batch_wide", a, blocks, shmem);
+    if (rc != LLMREC_OK) return rc;
+    sample_batch_wide_kernel<<<(unsigned)blocks, SAMPLE_WIDE_THREADS, 0, (hipStream_t)stream_>>>(a);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }

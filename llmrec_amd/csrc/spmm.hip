@@ -28,6 +28,7 @@
 // ~7.4 TB/s of 128-B lines from the Infinity Cache or HBM alike, plus ~25 TB/s for the L2 hits; a constant-degree
 // graph without any imbalance reaches 35 G gathers/s on the synthetic graphs' popularity - this kernel's ceiling.
 #include "common.h"
+#include "guests.h"
 
 namespace llmrec {
 
@@ -583,6 +584,38 @@ __global__ __launch_bounds__(TPB) void spmm_multi_kernel(SpmmMulti m) {
     }
 }
 
+// The grouped launch with a GUEST (llmrec_spmm_multi_guest_f32): blocks [0, guest_blocks) run the guest's body (guests.h: the sampler,
+// the scatter plan + reach marks, or the loss values, in their 512-thread forms), the problems' ranges follow (begin[0] = guest_blocks).
+// The guest depends on nothing this launch computes and nothing here waits for it: its short blocks, which a launch of their own would
+// run on a few CUs of an otherwise idle chip, start first and the latency-bound products fill the rest. Only the step's instance is
+// compiled (16 lanes per row, float4, one chunk); one kernel per guest kind, so each keeps the registers of its own body only.
+template <class G>
+struct SpmmMultiGuest {
+    SpmmMulti m;
+    int32_t guest_blocks;
+    G g;
+};
+
+// Each instance is held to its host spmm_kernel's waves per SIMD (7 unweighted, 5 weighted): inlined, the sampler's Philox rounds would
+// otherwise cost the unweighted host two registers and with them the seventh wave (73 VGPRs against 71).
+template <bool WEIGHTED, class G>
+__global__ __launch_bounds__(TPB, WEIGHTED ? 5 : 7) void spmm_multi_guest_kernel(SpmmMultiGuest<G> m) {
+    constexpr int LPR = 16, NCHUNK = 1, VEC = 4, ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    extern __shared__ __attribute__((aligned(16))) char guest_lds[];
+    const int32_t b = blockIdx.x;
+    if (b < m.guest_blocks) {                                             // (block-uniform)
+        guest_block<TPB>(m.g, b, guest_lds);
+        return;
+    }
+    switch (spmm_multi_problem(m.m, b)) {                                 // (block-uniform)
+    case 0: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[0], b, red_lds); break;
+    case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[1], b, red_lds); break;
+    case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[2], b, red_lds); break;
+    default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[3], b, red_lds); break;
+    }
+}
+
 // one block per (split row, slice): the 256/LPR lane groups each add every (256/LPR)-th segment partial (ascending),
 // then the groups are combined through LDS in group order - a fixed summation tree; then the row's epilogue
 template <int LPR, int NCHUNK, int VEC>
@@ -831,10 +864,37 @@ static int64_t spmm_layout(SpmmArgs& a, int lpr, int64_t first) {
 
 // One launch of n >= 1 laid-out problems of one family / variant (n == 1: the single-problem kernels), then the finalize launch of the
 // problems with split rows.
+// The guest of a grouped launch, checked and laid out (spmm_run): the kernel arguments of its kind, its blocks and its dynamic LDS.
+struct GuestLaunch {
+    int kind;
+    SamplerArgs sampler;
+    PlanReachArgs plan_reach;
+    LossesArgs losses;
+    int64_t blocks;
+    size_t shmem;
+};
+
+template <class G>
+static void launch_spmm_guest(int n, const SpmmPrepared* pp, int variant, int64_t total, const G& g, const GuestLaunch& gl, hipStream_t stream) {
+    SpmmMultiGuest<G> m = {};
+    for (int q = 0; q < LLMREC_SPMM_MAX_PROBLEMS; ++q) {
+        if (q < n) { m.m.p[q] = pp[q].a; m.m.begin[q] = pp[q].a.blk_begin; }
+        else m.m.begin[q] = 0x7fffffff;
+    }
+    m.guest_blocks = (int32_t)gl.blocks;
+    m.g = g;
+    if (variant == SPMM_V_WEIGHTED) spmm_multi_guest_kernel<true, G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);
+    else spmm_multi_guest_kernel<false, G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);
+}
+
 template <int LPR, int NCHUNK, int VEC>
-static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipStream_t stream) {
+static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipStream_t stream, const GuestLaunch* guest = nullptr) {
     if (total > 0) {
-        if (n == 1) {
+        if (guest) {                                         // (spmm_run: family 2, unmasked; total counts the guest's blocks)
+            if (guest->kind == LLMREC_SPMM_GUEST_SAMPLER) launch_spmm_guest(n, pp, variant, total, guest->sampler, *guest, stream);
+            else if (guest->kind == LLMREC_SPMM_GUEST_PLAN_REACH) launch_spmm_guest(n, pp, variant, total, guest->plan_reach, *guest, stream);
+            else launch_spmm_guest(n, pp, variant, total, guest->losses, *guest, stream);
+        } else if (n == 1) {
             const SpmmArgs& a = pp[0].a;
             switch (variant) {
             case SPMM_V_MASKED_W: spmm_kernel<LPR, NCHUNK, VEC, true, true><<<(unsigned)total, TPB, 0, stream>>>(a); break;
@@ -884,7 +944,7 @@ static bool bytes_overlap(const void* p, int64_t np, const void* q, int64_t nq) 
 }
 
 // Checks every problem, lays the non-empty ones out back to back (in the caller's order) and launches them together.
-static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_t stream) {
+static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_t stream, const llmrec_spmm_guest_t* guest = nullptr) {
     LLMREC_CHECK_ARG(n >= 0 && n <= LLMREC_SPMM_MAX_PROBLEMS && (n == 0 || problems), "spmm_multi: n = %d outside 0..%d", n, LLMREC_SPMM_MAX_PROBLEMS);
     SpmmPrepared pp[LLMREC_SPMM_MAX_PROBLEMS];
     int m = 0;
@@ -892,6 +952,29 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
         const int rc = spmm_prepare(problems[q], pp[m]);
         if (rc != LLMREC_OK) return rc;
         if (!pp[m].empty) ++m;
+    }
+    GuestLaunch gl = {};
+    if (guest) {                                                         // every check of the guest too, before anything is launched
+        int rc;
+        gl.kind = guest->kind;
+        if (guest->kind == LLMREC_SPMM_GUEST_SAMPLER) rc = guest_prepare(guest->u.sampler, TPB, "spmm_multi_guest (sampler)", gl.sampler, gl.blocks, gl.shmem);
+        else if (guest->kind == LLMREC_SPMM_GUEST_PLAN_REACH) rc = guest_prepare(guest->u.plan_reach, TPB, "spmm_multi_guest (plan + reach marks)", gl.plan_reach, gl.blocks, gl.shmem);
+        else if (guest->kind == LLMREC_SPMM_GUEST_LOSSES) rc = guest_prepare(guest->u.losses, TPB, "spmm_multi_guest (loss values)", gl.losses, gl.blocks, gl.shmem);
+        else { set_error("spmm_multi_guest: unknown guest kind %d", guest->kind); return LLMREC_EINVAL; }
+        if (rc != LLMREC_OK) return rc;
+        if (gl.blocks == 0 || m == 0) {
+            set_error("spmm_multi_guest: an empty guest or no non-empty problem to host it");
+            return LLMREC_EUNSUPPORTED;
+        }
+        // the plan's keys are dynamic LDS of EVERY block of the launch: three 512-thread blocks (7 waves/SIMD) must still fit a CU's 160 KB
+        if (guest->kind == LLMREC_SPMM_GUEST_PLAN_REACH && guest->u.plan_reach.B_max > LLMREC_SPMM_GUEST_MAX_PLAN_B) {
+            set_error("spmm_multi_guest: a plan of B_max %d > %d would cost the launch its occupancy", guest->u.plan_reach.B_max, LLMREC_SPMM_GUEST_MAX_PLAN_B);
+            return LLMREC_EUNSUPPORTED;
+        }
+        if (!(pp[0].family == 2 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED))) {
+            set_error("spmm_multi_guest: compiled for the unmasked float4 products of 33..64 columns only (family %d, variant %d)", pp[0].family, pp[0].variant);
+            return LLMREC_EUNSUPPORTED;
+        }
     }
     if (m == 0) return LLMREC_OK;
     for (int q = 1; q < m; ++q) {
@@ -920,7 +1003,7 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
         }
     }
     const int lpr = kSpmmFamilyLpr[pp[0].family];
-    int64_t total = 0;
+    int64_t total = gl.blocks;                                           // (0 without a guest: its blocks come first)
     for (int q = 0; q < m; ++q) {
         const int64_t t = spmm_layout(pp[q].a, lpr, total);
         if (t < 0) { set_error("spmm: too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
@@ -930,7 +1013,7 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
     switch (pp[0].family) {
     case 0: return launch_spmm<4, 1, 4>(m, pp, v, total, stream);
     case 1: return launch_spmm<8, 1, 4>(m, pp, v, total, stream);
-    case 2: return launch_spmm<16, 1, 4>(m, pp, v, total, stream);
+    case 2: return launch_spmm<16, 1, 4>(m, pp, v, total, stream, guest ? &gl : nullptr);
     case 3: return launch_spmm<32, 1, 4>(m, pp, v, total, stream);
     case 4: return launch_spmm<64, 1, 4>(m, pp, v, total, stream);
     case 5: return launch_spmm<64, 2, 4>(m, pp, v, total, stream);
@@ -958,6 +1041,11 @@ extern "C" int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
 
 extern "C" int llmrec_spmm_multi_f32(int32_t n, const llmrec_spmm_problem_t* problems, llmrec_stream_t stream_) {
     return spmm_run(n, problems, (hipStream_t)stream_);
+}
+
+extern "C" int llmrec_spmm_multi_guest_f32(int32_t n, const llmrec_spmm_problem_t* problems, const llmrec_spmm_guest_t* guest, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(guest, "spmm_multi_guest: no guest (llmrec_spmm_multi_f32 is the call without one)");
+    return spmm_run(n, problems, (hipStream_t)stream_, guest);
 }
 
 extern "C" int64_t llmrec_spmm_rows_compact_workspace_bytes(int64_t capacity, int32_t d) {

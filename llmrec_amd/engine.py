@@ -105,6 +105,14 @@ class DeviceBatcher:
         ops.sample_batch(self.seed, self.step_dev, self.exist_users, self.n_items, self.train, self.B * self.world,
                          self.rank * self.B, self.B, self.n_aug, self.aug_pos, self.aug_neg, users, pos, neg, n_valid)
 
+    def guest(self, users, pos, neg, n_valid):
+        """fill()'s launch as the guest descriptor of a grouped SpMM launch (ops.spmm_multi_guest); None where fill() is not the wide
+        sampler (the replicas' slices)."""
+        if self.world != 1:
+            return None
+        return ops.guest_sampler(self.seed, self.step_dev, self.exist_users, self.n_items, self.train, self.B, 0, self.B, self.n_aug,
+                                 self.aug_pos, self.aug_neg, users, pos, neg, n_valid, self.ticket)
+
     def next(self, step: Optional[int] = None):
         """(users, pos, neg, n_valid) in fresh buffers; step = None continues the device counter."""
         dev = self.exist_users.device

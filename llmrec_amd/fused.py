@@ -1,4 +1,4 @@
-"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of 24 HIP launches (30 on four streams)
+"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of 17 HIP launches (30 on four streams)
 over preallocated buffers, with the backward pass written out by hand (no autograd graph), captured into one
 HIP graph; likewise an evaluation (forward + scoring + masked top-K).
 
@@ -218,6 +218,8 @@ class FusedStep:
             self.ss_n = 0
         self._ev_plan = self._ev_reach = None                 # four streams: the scatter plan / the row list are ready (step_eager)
         self._reach_pending = None                            # one stream: the batch whose reach flags are marked and wait for the fusion launch
+        self._ride_guests = False                             # this step's sampler, plan and loss values ride SpMM launches (step_eager)
+        self._refuse_guests = False                           # tests: treat every guest launch as refused (the separate calls run)
         self._zero_in_forward = False                         # set by step_eager: forward() alone (evaluation) must not advance AdamW
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
@@ -301,14 +303,37 @@ class FusedStep:
         for a, X, Y, kw in jobs:
             self._spmm(a, X, Y, **kw)
 
-    def _spmm_group(self, jobs):
+    def _spmm_group(self, jobs, guest=None, fallback=None):
         """Independent products [(a, X, Y, kwargs of _spmm)] in ONE llmrec_spmm_multi_f32 launch, longest first (one stream: each of these
         latency-bound products alone leaves most CUs idle). Separate launches when the group has one product, when a graph is in the
         HBM-bound regime (nnz >= ops.SPMM_LATENCY_NNZ: one product fills the chip) or when the library refuses the group. Bit-identical
-        either way: a row's summation tree does not depend on the launch it runs in."""
+        either way: a row's summation tree does not depend on the launch it runs in.
+        guest (ops.SpmmGuestC): a short launch that depends on nothing the chip is busy with rides as the first blocks of this group's
+        launch (llmrec_spmm_multi_guest_f32; a group of one product too). Returns True if it did; otherwise `fallback` - the guest's own
+        entry point - has run right ahead of the group's usual launches."""
         jobs = [j for j in jobs if j is not None]
+        if guest is not None and jobs and not (self._refuse_guests or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs)):
+            probs, keep = self._spmm_problems(jobs)
+            if ops.spmm_multi_guest(probs, guest):
+                for a, X, _, _ in jobs:
+                    self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
+                return True
+        if fallback is not None:
+            fallback()
+        self._spmm_group_plain(jobs)
+        return False
+
+    def _spmm_group_plain(self, jobs):
         if len(jobs) == 1 or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs):
             return self._spmm_jobs(jobs)
+        probs, keep = self._spmm_problems(jobs)
+        if not ops.spmm_multi(probs):
+            return self._spmm_jobs(jobs)
+        for a, X, _, _ in jobs:
+            self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
+
+    def _spmm_problems(self, jobs):
+        """(the llmrec_spmm_problem_t of each job, longest first; what they point into)"""
         order = sorted(jobs, key=lambda j: -j[0].nnz * j[1].shape[1])             # (stable)
         probs, keep = [], []
         for a, X, Y, kw in order:
@@ -319,10 +344,7 @@ class FusedStep:
             probs.append(ops.SpmmProblemC(a.n_rows, a.n_cols, rp.data_ptr(), ci.data_ptr(), ops._ptr(a.val), ops._ptr(a.row_scale),
                                           ops._ptr(a.col_scale), X.data_ptr(), _ld(X), Y.data_ptr(), _ld(Y), X.shape[1], sw,
                                           _c.addressof(pc), ops._ptr(partials), _c.addressof(epi) if epi is not None else None))
-        if not ops.spmm_multi(probs):
-            return self._spmm_jobs(jobs)
-        for a, X, _, _ in jobs:
-            self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
+        return probs, keep
 
     def _linear(self, X, lin, out):
         _call("llmrec_linear_fwd_f32", X.shape[0], self.d, X.shape[1], _p(X), _ld(X), _p(lin.weight), _ld(lin.weight), _p(lin.bias),
@@ -459,12 +481,23 @@ class FusedStep:
     def _forward_one_stream(self, sampler, after_chain):
         """The forward's products on ONE stream, as dependency groups of grouped SpMM launches: the k-th product of the ID chain, of the
         side chain and of the profile chain share a launch (_spmm_group). The chain runs behind the projection so that its first two layers
-        pair with the side and profile products."""
-        if sampler is not None:
+        pair with the side and profile products.
+        Round 10 (step_eager's guest path only): the sampler rides the FIRST group's launch and after_chain - the scatter plan and the reach
+        marks - the chain's third product, which runs alone (sampler.guest / after_chain.guest build the descriptors). Read / write sets:
+          sampler   reads its tables (users with interactions, the train CSR, the augmented pairs) and the step counter; writes users / pos /
+                    neg / n_valid, the counter and its ticket. The first group reads the ID tables, the projections P_cat / U_cat and P_usr
+                    and writes U_1, I_cat, prof_i: disjoint. The batch's last reader of the previous step, the item table's clean-up launch,
+                    precedes this launch in stream order; its first reader is the plan, two launches later.
+          plan + marks   read the batch and the by-item CSR; write the plan buffer and the reach flags. Their host reads I_1 and writes U_2;
+                    the flags are consumed by the fusion launch's compaction block, two launches later, the plan by the loss backward."""
+        ride = self._ride_guests
+        sg = getattr(sampler, "guest", None) if ride else None
+        pg = getattr(after_chain, "guest", None) if ride else None
+        if sampler is not None and sg is None:
             sampler()
         if self._zero_in_forward and not self.fold:
             self.opt.advance()
-        if after_chain is not None:                                      # (reads the batch only)
+        if after_chain is not None and pg is None:                       # (reads the batch only)
             after_chain()
         self._stamp(1)
         self._project_all()
@@ -473,8 +506,19 @@ class FusedStep:
         side.append((self.iu.fwd, self.U_cat, self.I_cat, {}))
         prof = [(self.iu.fwd, self.P_usr, self.prof_i, dict(tag=1)), (self.ui.fwd, self.prof_i, self.prof_u, dict(tag=1))]
         chain = self._chain_fwd_jobs()
-        for k in range(max(len(chain), len(side), len(prof))):
-            self._spmm_group([c[k] if k < len(c) else None for c in (chain, side, prof)])
+        n_groups = max(len(chain), len(side), len(prof))
+        k_plan = min(2, n_groups - 1)                                    # behind the sampler's launch; the chain's third product where there is one
+        for k in range(n_groups):
+            jobs = [c[k] if k < len(c) else None for c in (chain, side, prof)]
+            if k == 0 and sg is not None:
+                self._spmm_group(jobs, sg(), sampler)
+                if k_plan == 0 and pg is not None:                       # (a single group: the plan by its own launch, behind the batch)
+                    after_chain()
+            elif k == k_plan and pg is not None:
+                if self._spmm_group(jobs, pg(), after_chain):
+                    self._reach_pending = after_chain.batch
+            else:
+                self._spmm_group(jobs)
         if self._zero_in_forward and not self.fold:
             self._feat_reg()
 
@@ -573,6 +617,10 @@ class FusedStep:
                   _p(self.out), _p(self.saved))
             self._join(self.s3)                  # the regulariser's value (s3, during the forward)
             self._assemble_loss(0)               # loss = sum_p w_mf[p] * mf_p + emb_0 + feat_reg
+        if self.fold:                            # the same launch as a guest of the backward's first SpMM group (_backward_one_stream)
+            side.guest = lambda: ops.guest_losses(self.n_prob, B, n_valid, remember, float(hp.decay), float(hp.batch_size), self.out, self.saved,
+                                                  self.w_mf, self.ss_partial, self.ss_n, float(hp.feat_reg_decay * 0.5 / self.I), self.scal,
+                                                  self.epoch_sums)
         self._backward(probs, users, pos, neg, n_valid, side_work=side, bpr_bwd_done=True)
         if not self.fold:
             self._join(self.s3)
@@ -726,13 +774,22 @@ class FusedStep:
 
     def _backward_one_stream(self, probs, batch, fuse, side_work):
         """The backward up to the weight gradients on ONE stream: the k-th product of the ID chain, of the side chain and of the profile
-        chain share a launch (_spmm_group); folded, the fusion backward shares the chain head's."""
+        chain share a launch (_spmm_group); folded, the fusion backward shares the chain head's.
+        Round 10 (step_eager's guest path only): side_work's loss-value launch rides the FIRST group's launch instead of running in the chain
+        head. It reads `saved` (the scores and selection launches), the fusion launch's partial sums and n_valid; it writes out, the four
+        totals of each problem in `saved`, scal and the epoch sums - read by the host after the step. Its host reads tmpI, dE_u, U_L, dI_cat
+        and dprof_u and writes tmpU, dU_cat and dprof_i: disjoint."""
         if not self.fold:
             _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
-        self._chain_head(side_work, fuse if self.fold else None)
+        lg = getattr(side_work, "guest", None) if self._ride_guests else None
+        self._chain_head(side_work if lg is None else None, fuse if self.fold else None)
         chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs()
         for k in range(max(len(chain), len(side), len(prof))):
-            self._spmm_group([c[k] if k < len(c) else None for c in (chain, side, prof)])
+            jobs = [c[k] if k < len(c) else None for c in (chain, side, prof)]
+            if k == 0 and lg is not None:
+                self._spmm_group(jobs, lg(), side_work)
+            else:
+                self._spmm_group(jobs)
         if self.gemm != "bf16x3":                                        # (bf16x3: user_trans' gradient is in the multi-target launch)
             self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
         self._chain_tail(probs, batch)
@@ -868,11 +925,20 @@ class FusedStep:
             if self.wgrad_rows:
                 ops.batch_reach_rows(users, pos, neg, n_valid, self.iu.fwd, self.act_flags, self.act_rows, self.act_n)
                 self._ev_reach = self._mark()
+        # Round 10, where the riders above apply: the sampler, the plan + marks and the loss values ride SpMM launches (_forward_one_stream,
+        # _backward_one_stream) - three launches fewer on the stream. A refused guest runs by its own entry point right ahead of its host.
+        self._ride_guests = bool(self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream)
+        if self._ride_guests:
+            if users.numel() > self.b_max:
+                raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (users.numel(), self.b_max))
+            batch_lists.batch = (users, pos, neg, n_valid)
+            batch_lists.guest = lambda: ops.guest_plan_reach(users, pos, neg, users.numel(), n_valid, self.bpr_plan, self.iu.fwd.n_cols,
+                                                             self.iu.fwd.n_rows, self.iu.fwd.rowptr, self.iu.fwd.colidx, self.act_flags)
         self.spmm_edge_units = 0.0
         calls0 = _lib.n_calls
         try:
             self._stamp(0)
-            if self.multi_stream:                                # the sampler rides beside the projection (forward())
+            if self.multi_stream or self._ride_guests:           # the sampler rides beside the projection (forward()) / in an SpMM launch
                 self._train_forward(sampler, batch_lists)
             else:
                 if sampler is not None:
@@ -896,6 +962,8 @@ class FusedStep:
                 except Exception:
                     pass
             raise
+        finally:
+            self._ride_guests = False
         return self.scal[1], self.scal[2], self.scal[3]
 
     def _size_wgrad_for_rows(self):
@@ -1029,6 +1097,17 @@ class FusedStep:
         self.static = {"users": blk[0:b], "pos": blk[b:2 * b], "neg": blk[2 * b:3 * b], "n_valid": blk[3 * b:3 * b + 1].view(torch.int32)[:1]}
         return self.static
 
+    @staticmethod
+    def sampler_of(batcher, st):
+        """step_eager's `sampler` for a DeviceBatcher filling the buffers st (users / pos / neg / n_valid): the call, and as its `guest`
+        attribute the same call as the guest descriptor of an SpMM launch."""
+        if batcher is None:
+            return None
+        fill = lambda: batcher.fill(st["users"], st["pos"], st["neg"], st["n_valid"])
+        if hasattr(batcher, "guest"):
+            fill.guest = lambda: batcher.guest(st["users"], st["pos"], st["neg"], st["n_valid"])
+        return fill
+
     def capture(self, warm_users=None, warm_pos=None, warm_neg=None, warm_n_valid=None, batcher=None, unroll: int = 1, warm: bool = True):
         """Capture one step (fixed batch capacity b_max, actual size on the device in n_valid).
         With `batcher` (engine.DeviceBatcher, capacity == b_max) the sampler is part of the graph: a
@@ -1045,8 +1124,7 @@ class FusedStep:
             self._load(warm_users, warm_pos, warm_neg, warm_n_valid)
 
         def one_step():
-            fill = (lambda: batcher.fill(st["users"], st["pos"], st["neg"], st["n_valid"])) if batcher is not None else None
-            self.step_eager(st["users"], st["pos"], st["neg"], st["n_valid"], sampler=fill)
+            self.step_eager(st["users"], st["pos"], st["neg"], st["n_valid"], sampler=self.sampler_of(batcher, st))
         self.reset_scatter_targets()                           # (re)capture starts from the invariant, whatever ran before
         if warm:
             s = torch.cuda.Stream()

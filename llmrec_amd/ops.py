@@ -82,6 +82,40 @@ class SpmmProblemC(_c.Structure):
                 ("epilogue", _c.c_void_p)]
 
 
+class GuestSamplerC(_c.Structure):
+    """llmrec_guest_sampler_t: the arguments of llmrec_sample_batch_wide"""
+    _fields_ = [("seed", _c.c_uint64), ("step_dev", _c.c_void_p), ("n_exist_users", _c.c_int64), ("exist_users", _c.c_void_p),
+                ("n_items", _c.c_int64), ("train_rowptr", _c.c_void_p), ("train_colidx", _c.c_void_p), ("B_global", _c.c_int32),
+                ("slice_begin", _c.c_int32), ("B", _c.c_int32), ("n_aug", _c.c_int32), ("aug_pos", _c.c_void_p), ("aug_neg", _c.c_void_p),
+                ("users", _c.c_void_p), ("pos", _c.c_void_p), ("neg", _c.c_void_p), ("n_valid_dev", _c.c_void_p), ("ticket", _c.c_void_p)]
+
+
+class GuestPlanReachC(_c.Structure):
+    """llmrec_guest_plan_reach_t: the arguments of llmrec_bpr_scatter_plan_reach_mark"""
+    _fields_ = [("users", _c.c_void_p), ("pos", _c.c_void_p), ("neg", _c.c_void_p), ("B_max", _c.c_int32), ("n_valid_dev", _c.c_void_p),
+                ("plan", _c.c_void_p), ("n_users", _c.c_int64), ("n_items", _c.c_int64), ("item_rowptr", _c.c_void_p),
+                ("item_colidx", _c.c_void_p), ("flags", _c.c_void_p)]
+
+
+class GuestLossesC(_c.Structure):
+    """llmrec_guest_losses_t: the arguments of llmrec_bpr_multi_losses_assemble_f32"""
+    _fields_ = [("n_problems", _c.c_int32), ("B_max", _c.c_int32), ("n_valid_dev", _c.c_void_p), ("remember_rate", _c.c_double),
+                ("decay", _c.c_float), ("batch_size_flag", _c.c_float), ("out", _c.c_void_p), ("saved", _c.c_void_p),
+                ("w_mf_host", _c.c_void_p), ("sumsq_partial", _c.c_void_p), ("n_partial", _c.c_int32), ("feat_reg_coef", _c.c_float),
+                ("scal4", _c.c_void_p), ("running_sums3", _c.c_void_p)]
+
+
+class _SpmmGuestU(_c.Union):
+    _fields_ = [("sampler", GuestSamplerC), ("plan_reach", GuestPlanReachC), ("losses", GuestLossesC)]
+
+
+class SpmmGuestC(_c.Structure):
+    """llmrec_spmm_guest_t: the tagged guest of llmrec_spmm_multi_guest_f32. keep: host arrays the descriptor points into."""
+    _fields_ = [("kind", _c.c_int32), ("u", _SpmmGuestU)]
+    keep = None
+
+
+GUEST_SAMPLER, GUEST_PLAN_REACH, GUEST_LOSSES = 1, 2, 3
 EPI_NONE, EPI_SOFTMAX, EPI_SOFTMAX_BWD = 0, 1, 2
 SPMM_LATENCY_NNZ = 4_000_000      # below: the graph is L2-resident and a step is launch-bound (Netflix scale)
 
@@ -498,6 +532,46 @@ def spmm_multi(problems: Sequence[SpmmProblemC]) -> bool:
     kernel instances), nothing was launched and the caller issues the products one by one."""
     arr = (SpmmProblemC * len(problems))(*problems)
     return _lib.call_unless_unsupported("llmrec_spmm_multi_f32", len(problems), arr, _stream())
+
+
+def spmm_multi_guest(problems: Sequence[SpmmProblemC], guest: SpmmGuestC) -> bool:
+    """spmm_multi with a guest (llmrec_spmm_multi_guest_f32): the guest's blocks lead the grouped launch; every result is bit-identical
+    to the separate calls. False: refused (LLMREC_EUNSUPPORTED), nothing was launched - the caller issues the guest's own entry point
+    and the products as before."""
+    arr = (SpmmProblemC * len(problems))(*problems)
+    return _lib.call_unless_unsupported("llmrec_spmm_multi_guest_f32", len(problems), arr, _c.byref(guest), _stream())
+
+
+def guest_sampler(seed: int, step_dev: torch.Tensor, exist_users: torch.Tensor, n_items: int, train: Csr, B_global: int,
+                  slice_begin: int, B: int, n_aug: int, aug_pos: Optional[torch.Tensor], aug_neg: Optional[torch.Tensor],
+                  users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, n_valid: torch.Tensor, ticket: torch.Tensor) -> SpmmGuestC:
+    """sample_batch_wide's call as a guest descriptor (the same buffer checks)."""
+    _need_gpu(step_dev, exist_users, users, pos, neg, n_valid, ticket)
+    if users.numel() < B + n_aug or step_dev.dtype != torch.int64 or n_valid.dtype != torch.int32 or ticket.dtype != torch.int32:
+        raise RuntimeError("sample_batch_wide: buffers of B + n_aug int64 entries, int64 step counter, int32 n_valid and ticket expected")
+    g = SpmmGuestC(kind=GUEST_SAMPLER)
+    g.u.sampler = GuestSamplerC(seed, _ptr(step_dev), exist_users.numel(), _ptr(exist_users), n_items, _ptr(train.rowptr), _ptr(train.colidx),
+                                B_global, slice_begin, B, n_aug, _ptr(aug_pos), _ptr(aug_neg), _ptr(users), _ptr(pos), _ptr(neg),
+                                _ptr(n_valid), _ptr(ticket))
+    return g
+
+
+def guest_plan_reach(users, pos, neg, B_max: int, n_valid, plan, n_users: int, n_items: int, item_rowptr, item_colidx, flags) -> SpmmGuestC:
+    """llmrec_bpr_scatter_plan_reach_mark's call as a guest descriptor."""
+    g = SpmmGuestC(kind=GUEST_PLAN_REACH)
+    g.u.plan_reach = GuestPlanReachC(_ptr(users), _ptr(pos), _ptr(neg), B_max, _ptr(n_valid), _ptr(plan), n_users, n_items, _ptr(item_rowptr),
+                                     _ptr(item_colidx), _ptr(flags))
+    return g
+
+
+def guest_losses(n_problems: int, B_max: int, n_valid, remember_rate: float, decay: float, batch_size_flag: float, out, saved, w_mf,
+                 sumsq_partial, n_partial: int, feat_reg_coef: float, scal4, running_sums3) -> SpmmGuestC:
+    """llmrec_bpr_multi_losses_assemble_f32's call as a guest descriptor; w_mf: the host weights (kept alive by the descriptor)."""
+    g = SpmmGuestC(kind=GUEST_LOSSES)
+    g.keep = w = (_c.c_float * n_problems)(*w_mf)
+    g.u.losses = GuestLossesC(n_problems, B_max, _ptr(n_valid), remember_rate, decay, batch_size_flag, _ptr(out), _ptr(saved),
+                              _c.cast(w, _c.c_void_p), _ptr(sumsq_partial), n_partial, feat_reg_coef, _ptr(scal4), _ptr(running_sums3))
+    return g
 
 
 class _SpMM(torch.autograd.Function):

@@ -1,5 +1,6 @@
 """One steady-state training step as a kernel timeline (from a rocprofv3 rocpd database of bench.py).
-python tools/step_timeline.py <results.db> <out.txt>  - picks a steady-state step (delimited by the in-graph sampler launch)."""
+python tools/step_timeline.py <results.db> <out.txt>  - picks a steady-state step (delimited by the in-graph sampler launch, or by the
+projection where the sampler has no launch of its own)."""
 import sqlite3, sys
 db, out = sys.argv[1], sys.argv[2]
 c = sqlite3.connect(db)
@@ -12,6 +13,8 @@ rows = c.execute(sel).fetchall()
 # sampler are both first (either may start a few us ahead of the other): a projection launched within 40 us before the sampler
 # belongs to the sampler's step
 starts = [i for i, r in enumerate(rows) if "sample_batch_kernel" in r[0] or "sample_batch_wide_kernel" in r[0]]
+if not starts:                                                   # the sampler rides an SpMM launch: the projection is the step's first launch
+    starts = [i for i, r in enumerate(rows) if "linear_fwd_grouped" in r[0]]
 for k, i in enumerate(starts):
     j = i - 1
     while j >= 0 and rows[i][1] - rows[j][1] < 40000:
