@@ -178,10 +178,10 @@ class DataParallelStep(FusedStep):
         if self.graphs is None:
             return self.step_eager(users, pos, neg, n_valid)
         if users is not None:
-            if getattr(self, "batcher", None) is not None:
+            if self.batcher is not None:
                 raise RuntimeError("DataParallelStep.step: this graph samples its own batch; call step() without arguments")
             self._load(users, pos, neg, n_valid)
-        elif getattr(self, "batcher", None) is None:
+        elif self.batcher is None:
             raise RuntimeError("DataParallelStep.step: a batch is needed (the graphs were captured without a sampler)")
         ga, gb, gc, ga_upd = self.graphs
         if self.lazy_update:

@@ -1,30 +1,37 @@
-"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of 17 HIP launches (30 on four streams)
-over preallocated buffers, with the backward pass written out by hand (no autograd graph), captured into one
-HIP graph; likewise an evaluation (forward + scoring + masked top-K).
+"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of HIP launches over preallocated buffers (17 at
+the benchmark's shape on one stream, FusedStep.entry_point_calls_per_step; more on four streams, where nothing is grouped), with the
+backward pass written out by hand (no autograd graph), captured into one HIP graph; likewise an evaluation (forward + scoring + top-K).
 
-Same arithmetic as the modular path (Models.MM_Model.forward + llmrec_amd.engine.train_step,
-i.e. reference Models.py:127-199 + main.py:228-278); what changes is the organisation:
-  * the seven item-side streams (image, text, 5 attributes) travel as ONE [rows, 7d] operand, so
-    the 16 side-feature SpMMs of the reference (Models.py:152-167) become 4 (+4 in backward) - 2 + 2 when the constant
-    products A_ui F_k are pre-propagated at set-up - and the adjacency indices are read once per direction instead of seven times;
+Same arithmetic as the modular path (Models.MM_Model.forward + llmrec_amd.engine.train_step, i.e. reference Models.py:127-199 +
+main.py:228-278); what changes is the organisation:
+  * the seven item-side streams (image, text, 5 attributes) travel as ONE [rows, 7d] operand, so the 16 side-feature SpMMs of the
+    reference (Models.py:152-167) become 4 (+4 in backward) - 2 + 2 when the constant products A_ui F_k are pre-propagated at set-up -
+    and the adjacency indices are read once per direction instead of seven times;
   * the 8 BPR + prune losses (main.py:232-254) are two launches on the critical path (scores - which also begin the step on the device:
     row stamp, AdamW's counter - and selection + gradient rows) and one beside it (the loss values, the feature regulariser from the
     fusion launch's partial sums, the logged scalars);
-  * projections and weight gradients of the constant feature matrices are grouped launches (8 projections in
-    one; all four Linears' gradients, row-listed, in one, with their AdamW in the reduction launch) in split-precision bf16x3
-    arithmetic (LLMREC_GEMM=f32: exact fp32);
-  * independent chains run on four HIP streams (fork/join = graph edges);
+  * projections and weight gradients of the constant feature matrices are grouped launches (8 projections in one; all four Linears'
+    gradients, row-listed, in one, with their AdamW in the reduction launch) in split-precision bf16x3 arithmetic (LLMREC_GEMM=f32: exact);
+  * independent products share grouped SpMM launches on ONE stream - the sampler, the scatter plan with the reach marks and the loss
+    values ride three of them as guests (_Rider) - or run as chains on four HIP streams (LLMREC_STREAMS=1: fork/join = graph edges);
   * the embedding tables' AdamW reads its gradient where it is formed (the user table's is inv * dE_u) and the row-wise clean-up of the
     scatter targets rides in the item table's AdamW launch;
-  * nothing allocates or synchronises, so the step can be replayed from a HIP graph
-    (``capture()``), removing the per-launch host cost that dominates at Netflix scale.
+  * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
 Falls outside its scope (use the modular path): dropout > 0 and the --mask branch.
+Schedule switches that remain: LLMREC_STREAMS=1 (four streams) and LLMREC_FOLD=0 (the separate small launches) are the A/B references of
+the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
+FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
+gradients before AdamW).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import os
-from typing import List, Optional
+from collections import namedtuple
+from itertools import zip_longest
+from typing import Callable, Optional
 
 import torch
 
@@ -38,38 +45,56 @@ def _call(name, *a):
     _lib.call(name, *a, ops._stream())
 
 
-class _capture_without_gc:
+def _raw(args):
+    """An argument tuple as an entry point takes it: tensors (and None) as pointers. The same tuple builds the guest descriptor (ops.guest_*)."""
+    return [_p(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+
+
+@contextlib.contextmanager
+def _capture_without_gc(graph, multi_branch: bool):
     """torch.cuda.graph(g) with Python's cyclic garbage collector held off for the duration of the capture. torch.cuda.graph collects
     garbage once, on entry; the body of a captured step then creates tens of thousands of container objects (ctypes argument arrays,
     tuples), so generation-0/1/2 collections run INSIDE the capture and may finalise whatever cyclic garbage exists by then - a
     previously imported drop-in module with its device tensors, an older step object with its graph executables - i.e. free device
     memory and destroy executables in the middle of a stream capture. Hygiene, not a fix for anything observed: the host fault round 4
     chased through the GPU suite turned out to be hipGraphLaunch's own (llmrec_amd/__init__.py)."""
+    from . import require_graph_replay
+    require_graph_replay("llmrec_amd: stream capture", multi_branch)   # single-branch graphs only (llmrec_amd/__init__.py)
+    capture = torch.cuda.graph(graph, capture_error_mode="thread_local")   # other threads (the RCCL watchdog) may touch the runtime
+    was_enabled = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        with capture:
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
-    def __init__(self, graph, multi_branch: bool):
-        from . import require_graph_replay
-        require_graph_replay("llmrec_amd: stream capture", multi_branch)   # single-branch graphs only (llmrec_amd/__init__.py)
-        self.ctx = torch.cuda.graph(graph, capture_error_mode="thread_local")   # other threads (the RCCL watchdog) may touch the runtime
 
-    def __enter__(self):
-        import gc
-        self.was_enabled = gc.isenabled()
-        gc.collect()
-        gc.disable()
-        try:
-            return self.ctx.__enter__()
-        except BaseException:
-            if self.was_enabled:
-                gc.enable()
-            raise
+class _Rider:
+    """A launch of the step that may ride in a grouped SpMM launch. run(): the launch by its own entry point(s), on the current stream;
+    guest: None, or a callable returning the same launch as a guest descriptor (ops.SpmmGuestC); rode: called when the guest launch was
+    accepted. FusedStep._spmm_group(jobs, rider) decides: the guest launch, or - refused, or no guest - run() right ahead of the
+    group's usual launches. Calling a rider runs it."""
+    def __init__(self, run: Callable, guest: Optional[Callable] = None, rode: Optional[Callable] = None):
+        self.run, self.guest, self.rode = run, guest, rode
 
-    def __exit__(self, *exc):
-        import gc
-        try:
-            return self.ctx.__exit__(*exc)
-        finally:
-            if self.was_enabled:
-                gc.enable()
+    def __call__(self):
+        self.run()
+
+
+class _TrainStep:
+    """What ONE training step hands from its forward to its backward, created by step_eager() and passed down as an argument: an
+    evaluation's forward() has none, so it cannot advance AdamW, emit the regulariser's partial sums or consume reach marks.
+    ride: the step's sampler, plan and loss values ride SpMM launches; ev_plan / ev_reach: four streams - the scatter plan / the weight
+    gradient's row list are ready; reach_pending: the batch whose reach flags are marked and wait for the fusion launch's compaction."""
+    def __init__(self, ride: bool = False):
+        self.ride, self.ev_plan, self.ev_reach, self.reach_pending = ride, None, None, None
+
+
+# one captured evaluation: the graph and everything it reads or writes (sums / auc_sum: pinned, None without a held-out set / auc=True)
+_EvalGraph = namedtuple("_EvalGraph", "graph idx scores q train ws sums sums_ws held auc_sum auc_ws")
 
 
 class FusedStep:
@@ -78,6 +103,7 @@ class FusedStep:
     # 81 us beside it and 12 us alone and, once the row list had shortened the GEMM, had become the step's tail. 224 blocks leave 32 CUs
     # to the other streams: 256 / 240 / 224 / 208 / 192 blocks -> 0.474 / 0.459 / 0.454 / 0.456 / 0.469 ms per step on one box.
     wgrad_blocks = 224
+    WGRAD_ROWS = INLINE_ADAMW = FOLD = True      # schedule switches of the class: DataParallelStep (llmrec_amd/dp.py) turns all three off
 
     def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
@@ -139,9 +165,9 @@ class FusedStep:
         self.ws_wgrad_b, self.ws_wgrad_c, self.ws_wgrad_d = wsq(model.user_feats), wsq(model.text_feats), wsq(model.image_feats)
         self.ws_wgrad_multi = None                           # sized at the first backward (needs the gradient tensors)
         self._partials = {}
-        # Independent chains (7-stream side features / LLM profile / ID embeddings / the two fusion halves / the logged scalars)
-        # can run on five HIP streams in forward and in backward (LLMREC_STREAMS=1), so that the latency-bound Netflix-scale SpMMs overlap
-        # the GEMMs in eager launches. The default is ONE stream: a captured step must be a single-branch graph (llmrec_amd/__init__.py).
+        # Independent chains (7-stream side features / LLM profile / ID embeddings / the logged scalars) can run on four HIP streams in forward
+        # and in backward (LLMREC_STREAMS=1), so that the latency-bound Netflix-scale SpMMs overlap the GEMMs in eager launches. The default
+        # is ONE stream: a captured step must be a single-branch graph (llmrec_amd/__init__.py).
         self.multi_stream = os.environ.get("LLMREC_STREAMS", "0") == "1"
         self.s1, self.s2, self.s3 = (torch.cuda.Stream(device=dev) for _ in range(3))
         for p in model.parameters():
@@ -153,10 +179,11 @@ class FusedStep:
         self.n_prob = 1 + S
         if self.n_prob > _lib.CONST["LLMREC_BPR_MAX_PROBLEMS"]:
             raise RuntimeError("FusedStep: %d BPR problems exceed LLMREC_BPR_MAX_PROBLEMS" % self.n_prob)
-        self.w_mf_dev = torch.tensor(self.w_mf, dtype=torch.float32, device=dev)
         self.graph_exec = None
-        self.static = None
-        self._eval_graphs = {}
+        self.graph_multi, self.graph_unroll = None, 0        # capture(batcher=, unroll=): a graph of `unroll` steps
+        self.batcher = self._capture_args = None             # capture()'s in-graph sampler and its arguments (check_wgrad_geometry re-captures)
+        self.static = self._last_eval = None
+        self._eval_graphs = {}                               # key -> _EvalGraph (_last_eval: the one replayed last)
         # measurement only (bench.py `roofline`): a uint64 tensor of STAMP_SLOTS device timestamps written by llmrec_timestamp launches around
         # the step, the projection launch and the weight-gradient launches - the durations INSIDE a replayed graph, which cannot carry events
         self.stamps = None
@@ -180,7 +207,7 @@ class FusedStep:
         self.preprop = d <= 64 and (want == "1" or (want not in ("0", "1") and U <= I))
         if not self.preprop:
             self.P_cat, self.dP_cat = f(I, S * d), f(I, S * d)        # the projected features and their gradient (reference order)
-        if self.preprop:
+        else:
             item_feats = [model.image_feats, model.text_feats] + [model.item_feats[k] for k in self.keys]
             self.AX = [self._propagate_constant(self.ui.fwd, x) for x in item_feats]
             self.a_rowsum = ops.spmm_raw(self.ui.fwd, torch.ones(I, 4, dtype=torch.float32, device=dev))[:, 0].contiguous()   # A_ui 1
@@ -189,11 +216,11 @@ class FusedStep:
         # streams' projected features is EXACTLY ZERO outside the rows the batch reaches: an attribute stream meets the loss in the fused
         # embeddings and BPR terms of the batch's rows only (Models.py:160-163,188-197; main.py:249-254), so dU_cat[:, attribute columns] is
         # non-zero in the batch's users (fusion backward) and in the users adjacent to the batch's items (A_iu^T of the items' rows) - 43 %
-        # of the users at the Netflix shape. llmrec_batch_reach_rows lists those rows (two small launches beside the forward) and the
+        # of the users at the Netflix shape. llmrec_batch_reach_rows lists those rows (beside the forward: _plan_reach_rider) and the
         # weight-gradient launch streams the listed rows of dU_cat and A_ui F_k only (llmrec_wgrad_problem_t.row_list): the same sums
         # without the terms that are zero. The image / text streams stay dense (the feature regulariser reads every row, main.py:151-156),
         # and so does user_trans (its gradient is two hops wide: 66 % of the rows).
-        self.wgrad_rows = (getattr(type(self), "WGRAD_ROWS", True) and os.environ.get("LLMREC_WGRAD_ROWS", "1") == "1" and self.preprop
+        self.wgrad_rows = (self.WGRAD_ROWS and os.environ.get("LLMREC_WGRAD_ROWS", "1") == "1" and self.preprop
                            and len(self.keys) > 0 and self.gemm == "bf16x3")     # (the exact-fp32 launches ignore the list: do not build it)
         if self.wgrad_rows:
             self.act_flags = torch.zeros(U + 16, dtype=torch.uint8, device=dev)[:U]   # all-zero between calls (readable in 16-byte words)
@@ -204,29 +231,24 @@ class FusedStep:
         # gradients (beside the weight-gradient GEMM), the four Linears right after the slab reduction of that GEMM - the
         # step's tail is then one small launch instead of reduction -> cross-stream join -> a 1.96 M-parameter update.
         # (Batch-sharded replicas all-reduce the gradients first and update afterwards: llmrec_amd/dp.py sets this to False.)
-        self.inline_adamw = getattr(type(self), "INLINE_ADAMW", True)
-        # FOLDED launches (round 5; LLMREC_FOLD=0 restores the 36-launch step): AdamW's counter advances inside the scores
+        self.inline_adamw = self.INLINE_ADAMW
+        # FOLDED launches (round 5; LLMREC_FOLD=0 restores the separate launches): AdamW's counter advances inside the scores
         # launch ("a new step begins": llmrec_bpr_multi_scores_step_f32), the feature regulariser's sum of squares comes out of the fusion launch
         # as per-block partials (llmrec_fuse_fwd_multi_sumsq_f32: it holds those rows anyway) and is reduced by the ONE launch that also forms
         # the loss values and assembles the logged scalars (llmrec_bpr_multi_losses_assemble_f32), the user table's AdamW reads inv * dE_u
         # directly and stores it as the table's .grad on the way (no axpy), and the row-wise clean-up of the scatter targets rides in the item
-        # table's AdamW launch (llmrec_adamw_multi_zero_rows_f32): 36 -> 28 launches, same arithmetic except the regulariser's summation tree.
-        self.fold = getattr(type(self), "FOLD", True) and os.environ.get("LLMREC_FOLD", "1") == "1" and self.inline_adamw
+        # table's AdamW launch (llmrec_adamw_multi_zero_rows_f32): eight launches fewer, same arithmetic except the regulariser's summation tree.
+        self.fold = self.FOLD and os.environ.get("LLMREC_FOLD", "1") == "1" and self.inline_adamw
         if self.fold:
             self.ss_cap = 2 * 2048                                # >= the fusion launch's grid (two problems, <= 2048 blocks each)
             self.ss_partial = torch.zeros(self.ss_cap, dtype=torch.float32, device=dev)
             self.ss_n = 0
-        self._ev_plan = self._ev_reach = None                 # four streams: the scatter plan / the row list are ready (step_eager)
-        self._reach_pending = None                            # one stream: the batch whose reach flags are marked and wait for the fusion launch
-        self._ride_guests = False                             # this step's sampler, plan and loss values ride SpMM launches (step_eager)
         self._refuse_guests = False                           # tests: treat every guest launch as refused (the separate calls run)
-        self._zero_in_forward = False                         # set by step_eager: forward() alone (evaluation) must not advance AdamW
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
-        # Launch (= capture) order at the fork points decides which branch the graph runs behind its parent without a cross-queue
-        # hand-off (~10 us). Measured one at a time in round 2 (profiles/README.md): the forward's side-feature SpMMs are
-        # captured before the profile chain, the BPR backward before the regulariser / loss assembly (-3.6 % together); the
-        # other fork points are neutral or lose.
+        # (Four streams: launch = capture order at the fork points decides which branch the graph runs behind its parent without a cross-queue
+        # hand-off, ~10 us. Measured one at a time in round 2, profiles/README.md: the forward's side-feature SpMMs are captured before the
+        # profile chain, the BPR backward before the regulariser / loss assembly, -3.6 % together; the other fork points are neutral or lose.)
 
     # -- raw kernel helpers -----------------------------------------------------------------------
     @staticmethod
@@ -303,31 +325,31 @@ class FusedStep:
         for a, X, Y, kw in jobs:
             self._spmm(a, X, Y, **kw)
 
-    def _spmm_group(self, jobs, guest=None, fallback=None):
+    def _check_batch(self, B: int):
+        if B > self.b_max:
+            raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (B, self.b_max))
+
+    def _spmm_group(self, jobs, rider: Optional[_Rider] = None):
         """Independent products [(a, X, Y, kwargs of _spmm)] in ONE llmrec_spmm_multi_f32 launch, longest first (one stream: each of these
         latency-bound products alone leaves most CUs idle). Separate launches when the group has one product, when a graph is in the
         HBM-bound regime (nnz >= ops.SPMM_LATENCY_NNZ: one product fills the chip) or when the library refuses the group. Bit-identical
         either way: a row's summation tree does not depend on the launch it runs in.
-        guest (ops.SpmmGuestC): a short launch that depends on nothing the chip is busy with rides as the first blocks of this group's
-        launch (llmrec_spmm_multi_guest_f32; a group of one product too). Returns True if it did; otherwise `fallback` - the guest's own
-        entry point - has run right ahead of the group's usual launches."""
+        rider: a short launch that depends on nothing the chip is busy with. With a guest descriptor it rides as the first blocks of this
+        group's launch (llmrec_spmm_multi_guest_f32; a group of one product too); refused, or without one, it runs by its own entry
+        point right ahead of the group's usual launches."""
         jobs = [j for j in jobs if j is not None]
-        if guest is not None and jobs and not (self._refuse_guests or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs)):
-            probs, keep = self._spmm_problems(jobs)
-            if ops.spmm_multi_guest(probs, guest):
-                for a, X, _, _ in jobs:
-                    self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
-                return True
-        if fallback is not None:
-            fallback()
-        self._spmm_group_plain(jobs)
-        return False
-
-    def _spmm_group_plain(self, jobs):
-        if len(jobs) == 1 or self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs):
-            return self._spmm_jobs(jobs)
-        probs, keep = self._spmm_problems(jobs)
-        if not ops.spmm_multi(probs):
+        groupable = not (self.multi_stream or any(a.nnz >= ops.SPMM_LATENCY_NNZ for a, _, _, _ in jobs))
+        as_guest = rider is not None and rider.guest is not None and groupable and not self._refuse_guests
+        probs, keep = self._spmm_problems(jobs) if as_guest or (groupable and len(jobs) > 1) else (None, None)
+        guest = rider.guest() if as_guest else None                      # (None: no guest form after all - the replicas' sampler)
+        launched = guest is not None and ops.spmm_multi_guest(probs, guest)
+        if launched and rider.rode is not None:
+            rider.rode()
+        if rider is not None and not launched:
+            rider()
+        if not launched and groupable and len(jobs) > 1:
+            launched = ops.spmm_multi(probs)
+        if not launched:
             return self._spmm_jobs(jobs)
         for a, X, _, _ in jobs:
             self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
@@ -401,9 +423,6 @@ class FusedStep:
         ops.linear_wgrad_grouped([(dY, X)], lin.weight.grad, lin.bias.grad, accumulate, self.ws_wgrad if ws is None else ws,
                                  precision=self.gemm)
 
-    def _softmax(self, Z, Y):
-        _call("llmrec_softmax_rows_fwd_f32", Z.shape[0], self.d, _p(Z), _ld(Z), _p(Y), _ld(Y))
-
     def _softmax_bwd(self, Y, dY, dZ, alpha: float = 1.0):
         _call("llmrec_softmax_rows_bwd_scaled_f32", Y.shape[0], self.d, float(alpha), _p(Y), _ld(Y), _p(dY), _ld(dY), _p(dZ), _ld(dZ))
 
@@ -428,14 +447,23 @@ class FusedStep:
         return (_c.c_float * len(r))(*r)
 
     # -- forward ----------------------------------------------------------------------------------
-    def forward(self, sampler=None, after_chain=None, profile_on_main: bool = False):
-        """sampler / after_chain: launches for the ID chain's stream, ahead of / behind its SpMMs (the batch and what is derived from it);
-        profile_on_main: the profile chain stays on the current stream (the evaluation's graph, see eval_topk)."""
+    def forward(self, profile_on_main: bool = False):
+        """The evaluation's forward (no training step: it advances and consumes nothing). profile_on_main: the profile chain stays on the
+        current stream (the evaluation's graph, see eval_topk)."""
+        self._forward(None, profile_on_main=profile_on_main)
+
+    def _train_forward(self, sampler: Optional[_Rider] = None, after_chain: Optional[_Rider] = None, step: Optional[_TrainStep] = None):
+        """The forward of a training step (step_eager's riders and record; DataParallelStep, which runs its own backward, passes none)."""
+        self._forward(step if step is not None else _TrainStep(), sampler, after_chain)
+
+    def _forward(self, step: Optional[_TrainStep], sampler=None, after_chain=None, profile_on_main: bool = False):
+        """step: the training step this forward belongs to, None = evaluation. sampler / after_chain: launches for the ID chain's stream,
+        ahead of / behind its SpMMs (the batch and what is derived from it)."""
         m, d = self.m, self.d
         if self.multi_stream:
-            self._forward_streams(sampler, after_chain, profile_on_main)
+            self._forward_streams(step, sampler, after_chain, profile_on_main)
         else:
-            self._forward_one_stream(sampler, after_chain)
+            self._forward_one_stream(step, sampler, after_chain)
 
         # E_u and E_i (Models.py:185-197) in ONE launch: llmrec_fuse_fwd_multi_f32 (two independent row ranges)
         keep = []
@@ -453,9 +481,9 @@ class FusedStep:
         arr = (ops.FuseFwdProblem * 2)()
         problem(arr[0], self.E_i, m.item_id_embedding.weight, self.Il, self.I_cat, self.prof_i)
         problem(arr[1], self.E_u, m.user_id_embedding.weight, self.Ul, self.U_cat, self.prof_u)
-        if self.fold and self._zero_in_forward:                          # + the regulariser's sum of squares over the image / text streams (terms 0, 1)
+        if self.fold and step is not None:                               # + the regulariser's sum of squares over the image / text streams (terms 0, 1)
             n_part = _c.c_int32(0)
-            pending, self._reach_pending = self._reach_pending, None
+            pending, step.reach_pending = step.reach_pending, None
             if pending is not None and _lib.call_unless_unsupported(         # + the reach flags' compaction as the launch's first block
                     "llmrec_fuse_fwd_multi_sumsq_compact_f32", 2, arr, d, 2, _p(self.ss_partial), self.ss_cap, _c.byref(n_part),
                     self.iu.fwd.n_cols, _p(self.act_flags), _p(self.act_rows), _p(self.act_n), ops._stream()):
@@ -478,26 +506,24 @@ class FusedStep:
             i_prev = self.Il[l]
         return jobs
 
-    def _forward_one_stream(self, sampler, after_chain):
+    def _forward_one_stream(self, step, sampler, after_chain):
         """The forward's products on ONE stream, as dependency groups of grouped SpMM launches: the k-th product of the ID chain, of the
         side chain and of the profile chain share a launch (_spmm_group). The chain runs behind the projection so that its first two layers
         pair with the side and profile products.
-        Round 10 (step_eager's guest path only): the sampler rides the FIRST group's launch and after_chain - the scatter plan and the reach
-        marks - the chain's third product, which runs alone (sampler.guest / after_chain.guest build the descriptors). Read / write sets:
+        sampler / after_chain are step_eager's riders (given only where they ride: step.ride): the sampler rides the FIRST group's launch
+        and after_chain - the scatter plan and the reach marks - the chain's third product, which runs alone. A rider without a guest
+        descriptor runs ahead of the projection. Read / write sets:
           sampler   reads its tables (users with interactions, the train CSR, the augmented pairs) and the step counter; writes users / pos /
                     neg / n_valid, the counter and its ticket. The first group reads the ID tables, the projections P_cat / U_cat and P_usr
                     and writes U_1, I_cat, prof_i: disjoint. The batch's last reader of the previous step, the item table's clean-up launch,
                     precedes this launch in stream order; its first reader is the plan, two launches later.
           plan + marks   read the batch and the by-item CSR; write the plan buffer and the reach flags. Their host reads I_1 and writes U_2;
                     the flags are consumed by the fusion launch's compaction block, two launches later, the plan by the loss backward."""
-        ride = self._ride_guests
-        sg = getattr(sampler, "guest", None) if ride else None
-        pg = getattr(after_chain, "guest", None) if ride else None
-        if sampler is not None and sg is None:
+        if sampler is not None and sampler.guest is None:
             sampler()
-        if self._zero_in_forward and not self.fold:
+        if step is not None and not self.fold:
             self.opt.advance()
-        if after_chain is not None and pg is None:                       # (reads the batch only)
+        if after_chain is not None and after_chain.guest is None:        # (reads the batch only)
             after_chain()
         self._stamp(1)
         self._project_all()
@@ -506,29 +532,22 @@ class FusedStep:
         side.append((self.iu.fwd, self.U_cat, self.I_cat, {}))
         prof = [(self.iu.fwd, self.P_usr, self.prof_i, dict(tag=1)), (self.ui.fwd, self.prof_i, self.prof_u, dict(tag=1))]
         chain = self._chain_fwd_jobs()
-        n_groups = max(len(chain), len(side), len(prof))
-        k_plan = min(2, n_groups - 1)                                    # behind the sampler's launch; the chain's third product where there is one
-        for k in range(n_groups):
-            jobs = [c[k] if k < len(c) else None for c in (chain, side, prof)]
-            if k == 0 and sg is not None:
-                self._spmm_group(jobs, sg(), sampler)
-                if k_plan == 0 and pg is not None:                       # (a single group: the plan by its own launch, behind the batch)
-                    after_chain()
-            elif k == k_plan and pg is not None:
-                if self._spmm_group(jobs, pg(), after_chain):
-                    self._reach_pending = after_chain.batch
-            else:
-                self._spmm_group(jobs)
-        if self._zero_in_forward and not self.fold:
+        groups = list(zip_longest(chain, side, prof))                    # (two at least: the profile chain's)
+        # the riders' hosts: the sampler's is the first group, the plan's comes behind it - the chain's third product where there is one
+        hosts = {0: sampler, min(2, len(groups) - 1): after_chain}
+        for k, jobs in enumerate(groups):
+            rider = hosts.get(k)
+            self._spmm_group(jobs, rider if rider is not None and rider.guest is not None else None)
+        if step is not None and not self.fold:
             self._feat_reg()
 
-    def _forward_streams(self, sampler, after_chain, profile_on_main):
+    def _forward_streams(self, step, sampler, after_chain, profile_on_main):
         """The forward's products on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule)."""
         self._fork(self.s2)
         with self._on(self.s2):                                          # ID chain: needs no projection
             if sampler is not None:                                      # the batch is first read by the losses, after the join below:
                 sampler()                                                # sampling rides beside the projection instead of ahead of it
-            if self._zero_in_forward and not self.fold:
+            if step is not None and not self.fold:
                 self.opt.advance()                                       # AdamW's step counter / bias corrections, off the critical path
             self._spmm_jobs(self._chain_fwd_jobs())
             ev_chain = self._mark() if after_chain is not None else None     # the chain's SpMMs are done; what follows on this stream
@@ -549,7 +568,7 @@ class FusedStep:
             with self._on(self.s1):                                      # profile stream: items first
                 self._spmm(self.iu.fwd, self.P_usr, self.prof_i, tag=1)
                 self._spmm(self.ui.fwd, self.prof_i, self.prof_u, tag=1)
-        if self._zero_in_forward and not self.fold:                      # training: the feature regulariser's value needs only U_cat / I_cat -
+        if step is not None and not self.fold:                           # training: the feature regulariser's value needs only U_cat / I_cat -
             self._fork(self.s3)                                          # captured HERE it runs beside the fusion and the BPR launches (captured
             with self._on(self.s3):                                      # after the BPR backward, round 2, the graph ran it last: the step's tail)
                 self._feat_reg()
@@ -581,47 +600,44 @@ class FusedStep:
             arr[i].g_mf, arr[i].g_emb = self.w_mf[i], self.w_emb[i]
         return arr
 
-    def loss_backward(self, users, pos, neg, n_valid=None):
+    def loss_backward(self, users, pos, neg, n_valid=None, step: Optional[_TrainStep] = None):
+        """The 8 losses and the whole backward behind _train_forward(). step: step_eager's record (None: nothing to wait for, nothing rides)."""
+        step = step if step is not None else _TrainStep()
         B = users.numel()
-        if B > self.b_max:
-            raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (B, self.b_max))
+        self._check_batch(B)
         probs = self._problems()
         hp = self.hp
         remember = float(1 - hp.prune_loss_drop_rate)
-        # critical path: scores -> [selection + gradient rows] (two launches); the loss VALUES (one more launch) and their assembly for
-        # the log line ride on the ID chain's stream (a branch of their own right behind the BPR launches: the graph ran it as the step's tail)
+        # critical path: scores -> [selection + gradient rows] (two launches); the loss VALUES are beside it (below)
         self._check_scatter_targets()
-        if self._ev_plan is not None:                                    # (four streams: the plan was built behind the ID chain)
-            torch.cuda.current_stream().wait_event(self._ev_plan)
+        if step.ev_plan is not None:                                     # (four streams: the plan was built behind the ID chain)
+            torch.cuda.current_stream().wait_event(step.ev_plan)
         # the scores launch begins the step (row stamp; folded: AdamW's counter too), the selection stamps the batch's rows
+        scores = (self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved), _p(self.row_stamp))
         if self.fold:
             o = self.opt
             if o.dev_state is None:
                 o.dev_state = torch.zeros(3, dtype=torch.float32, device=self.E_u.device)
-            _call("llmrec_bpr_multi_scores_step_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved),
-                  _p(self.row_stamp), _p(o.dev_state), o.lr, o.betas[0], o.betas[1])
+            _call("llmrec_bpr_multi_scores_step_f32", *scores, _p(o.dev_state), o.lr, o.betas[0], o.betas[1])
         else:
-            _call("llmrec_bpr_multi_scores_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved),
-                  _p(self.row_stamp))
+            _call("llmrec_bpr_multi_scores_f32", *scores)
         _call("llmrec_bpr_multi_select_bwd_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), remember,
               float(hp.decay), float(hp.batch_size), _p(self.saved), _p(self.flag_u), _p(self.flag_i), _p(self.row_stamp), _p(self.bpr_plan))
+        # The loss values and the logged scalars, on the ID chain's stream (_backward places them: a branch of their own right behind the BPR
+        # launches - the graph ran it as the step's tail). Folded: ONE launch - loss values + regulariser (the fusion launch's partial sums) +
+        # assembly - and, where the step's riders apply, the same launch as a guest of the backward's first SpMM group (_backward_one_stream).
+        losses = (self.n_prob, B, n_valid, remember, float(hp.decay), float(hp.batch_size), self.out, self.saved)
+        reg = (self.ss_partial, self.ss_n, float(hp.feat_reg_decay * 0.5 / self.I), self.scal, self.epoch_sums) if self.fold else None
 
-        def side():                              # (runs on the ID chain's stream, _backward places it)
-            if self.fold:                        # loss values + regulariser (the fusion launch's partial sums) + assembly: one launch
-                w = (_c.c_float * self.n_prob)(*self.w_mf)
-                _call("llmrec_bpr_multi_losses_assemble_f32", self.n_prob, B, _p(n_valid), remember, float(hp.decay), float(hp.batch_size),
-                      _p(self.out), _p(self.saved), w, _p(self.ss_partial), self.ss_n, float(hp.feat_reg_decay * 0.5 / self.I),
-                      _p(self.scal), _p(self.epoch_sums))
-                return
-            _call("llmrec_bpr_multi_losses_f32", self.n_prob, B, _p(n_valid), remember, float(hp.decay), float(hp.batch_size),
-                  _p(self.out), _p(self.saved))
+        def folded():
+            _call("llmrec_bpr_multi_losses_assemble_f32", *_raw(losses), (_c.c_float * self.n_prob)(*self.w_mf), *_raw(reg))
+
+        def unfolded():
+            _call("llmrec_bpr_multi_losses_f32", *_raw(losses))
             self._join(self.s3)                  # the regulariser's value (s3, during the forward)
             self._assemble_loss(0)               # loss = sum_p w_mf[p] * mf_p + emb_0 + feat_reg
-        if self.fold:                            # the same launch as a guest of the backward's first SpMM group (_backward_one_stream)
-            side.guest = lambda: ops.guest_losses(self.n_prob, B, n_valid, remember, float(hp.decay), float(hp.batch_size), self.out, self.saved,
-                                                  self.w_mf, self.ss_partial, self.ss_n, float(hp.feat_reg_decay * 0.5 / self.I), self.scal,
-                                                  self.epoch_sums)
-        self._backward(probs, users, pos, neg, n_valid, side_work=side, bpr_bwd_done=True)
+        values = _Rider(folded, (lambda: ops.guest_losses(*losses, self.w_mf, *reg)) if step.ride else None) if self.fold else _Rider(unfolded)
+        self._backward(probs, users, pos, neg, n_valid, bpr_bwd_done=True, side_work=values, ev_reach=step.ev_reach)
         if not self.fold:
             self._join(self.s3)
 
@@ -645,11 +661,13 @@ class FusedStep:
             if dirty:
                 raise RuntimeError("FusedStep: scatter targets not all-zero before the loss backward: %s (an aborted step? call reset_scatter_targets())" % dirty)
 
-    def _backward(self, probs, users, pos, neg, n_valid, replicated_scale: float = 1.0, bpr_bwd_done: bool = False, side_work=None):
+    def _backward(self, probs, users, pos, neg, n_valid, replicated_scale: float = 1.0, bpr_bwd_done: bool = False, side_work=None,
+                  ev_reach=None):
         """Hand-written backward from the saved BPR state to the parameter gradients (and, with inline_adamw, the update).
         replicated_scale weights the batch-independent loss terms (1 / world on batch-sharded replicas, whose
         gradients are summed over ranks afterwards). bpr_bwd_done: the loss launch already scattered the gradient rows.
-        side_work: launches for the ID chain's stream, ahead of its last SpMM."""
+        side_work: launches for the ID chain's stream, ahead of its last SpMM (loss_backward's rider); ev_reach: four streams - the event
+        behind the weight gradient's row list."""
         hp = self.hp
         if not bpr_bwd_done:
             self._check_scatter_targets()
@@ -659,7 +677,7 @@ class FusedStep:
         fuse, keep = self._fuse_bwd_problems(hp.feat_reg_decay * 0.5 / self.I * replicated_scale, stamped=bpr_bwd_done)
         schedule = self._backward_streams if self.multi_stream else self._backward_one_stream
         schedule(probs, (users, pos, neg, n_valid), fuse, side_work)
-        self._weight_gradients()
+        self._weight_gradients(ev_reach)
         self._join(self.s2)
         if self.fold and side_work is not None:                          # (four streams: side_work ran on a stream of its own)
             self._join(self.s3)
@@ -775,21 +793,17 @@ class FusedStep:
     def _backward_one_stream(self, probs, batch, fuse, side_work):
         """The backward up to the weight gradients on ONE stream: the k-th product of the ID chain, of the side chain and of the profile
         chain share a launch (_spmm_group); folded, the fusion backward shares the chain head's.
-        Round 10 (step_eager's guest path only): side_work's loss-value launch rides the FIRST group's launch instead of running in the chain
-        head. It reads `saved` (the scores and selection launches), the fusion launch's partial sums and n_valid; it writes out, the four
-        totals of each problem in `saved`, scal and the epoch sums - read by the host after the step. Its host reads tmpI, dE_u, U_L, dI_cat
-        and dprof_u and writes tmpU, dU_cat and dprof_i: disjoint."""
+        Where side_work carries a guest descriptor (loss_backward's rider), its loss-value launch rides the FIRST group's launch instead of
+        running in the chain head. It reads `saved` (the scores and selection launches), the fusion launch's partial sums and n_valid; it
+        writes out, the four totals of each problem in `saved`, scal and the epoch sums - read by the host after the step. Its host reads
+        tmpI, dE_u, U_L, dI_cat and dprof_u and writes tmpU, dU_cat and dprof_i: disjoint."""
         if not self.fold:
             _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
-        lg = getattr(side_work, "guest", None) if self._ride_guests else None
-        self._chain_head(side_work if lg is None else None, fuse if self.fold else None)
+        rides = side_work is not None and side_work.guest is not None
+        self._chain_head(None if rides else side_work, fuse if self.fold else None)
         chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs()
-        for k in range(max(len(chain), len(side), len(prof))):
-            jobs = [c[k] if k < len(c) else None for c in (chain, side, prof)]
-            if k == 0 and lg is not None:
-                self._spmm_group(jobs, lg(), side_work)
-            else:
-                self._spmm_group(jobs)
+        for k, jobs in enumerate(zip_longest(chain, side, prof)):
+            self._spmm_group(jobs, side_work if k == 0 and rides else None)
         if self.gemm != "bf16x3":                                        # (bf16x3: user_trans' gradient is in the multi-target launch)
             self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
         self._chain_tail(probs, batch)
@@ -829,8 +843,9 @@ class FusedStep:
         if not main_first:
             self._spmm_jobs(side)
 
-    def _weight_gradients(self):
-        """The four Linears' gradients from dU_cat (pre-propagated; else dP_cat) and dP_usr, and - with inline_adamw - their update."""
+    def _weight_gradients(self, ev_reach=None):
+        """The four Linears' gradients from dU_cat (pre-propagated; else dP_cat) and dP_usr, and - with inline_adamw - their update.
+        ev_reach: four streams - the event behind the row list (step_eager's record)."""
         m, S, d = self.m, self.S, self.d
         dY_cat = self.dU_cat if self.preprop else self.dP_cat
         targets = self.wgrad_targets(dY_cat, self.dP_usr)
@@ -848,8 +863,8 @@ class FusedStep:
                 self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=dY_cat.device) if need >= 0 else False
             if self.ws_wgrad_multi is not False:
                 self._stamp(3)
-                if self._ev_reach is not None:                           # (four streams: the row list was built behind the ID chain)
-                    torch.cuda.current_stream().wait_event(self._ev_reach)
+                if ev_reach is not None:                                 # (four streams: the row list was built behind the ID chain)
+                    torch.cuda.current_stream().wait_event(ev_reach)
                 lins = (m.item_trans, m.user_trans, m.text_trans, m.image_trans)              # (wgrad_targets' order)
                 if self.inline_adamw:                                  # the four Linears' AdamW rides in the slab-reduction launch
                     ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, update=(self.opt, [(l.weight, l.bias) for l in lins]), block_budget=self.wgrad_blocks)
@@ -876,76 +891,69 @@ class FusedStep:
         if self.inline_adamw:                                            # whatever the reduction launch did not update (all four Linears on
             self.opt.step_params([p_ for p_ in self._lin_params if all(p_ is not q for q in updated)])   # the per-target fallback paths)
 
-    def _train_forward(self, sampler=None, after_chain=None):
-        """forward() of a training step: also advances AdamW's counters (and samples the batch) on a side stream."""
-        self._zero_in_forward = True
-        try:
-            self.forward(sampler, after_chain)
-        finally:
-            self._zero_in_forward = False
-
     def build_scatter_plan(self, users, pos, neg, n_valid=None):
         """llmrec_bpr_scatter_plan of this batch into the step's plan buffer (one launch; step_eager does it behind the sampler - callers
         that drive forward() / loss_backward() themselves call it once per batch, any time before the loss backward)."""
-        B = users.numel()
-        if B > self.b_max:
-            raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (B, self.b_max))
-        _call("llmrec_bpr_scatter_plan", _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.bpr_plan))
+        self._check_batch(users.numel())
+        _call("llmrec_bpr_scatter_plan", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid), _p(self.bpr_plan))
 
     def reset_scatter_targets(self):
-        """Dense clear of the buffers the sparse-zero scheme keeps all-zero between steps (set-up, (re)capture, and after a
-        step that raised between the loss backward's scatter and its row-wise clean-up)."""
+        """Dense clear of the scatter targets, which the step keeps all-zero between steps by clearing the rows it touched (set-up,
+        (re)capture, and after a step that raised between the loss backward's scatter and its row-wise clean-up)."""
         for t in (self.dE_u, self.dE_i, self.sc_U, self.sc_I, self.sc_prof):
             t.zero_()
 
-    def step_eager(self, users, pos, neg, n_valid=None, sampler=None):
-        """sampler: optional callable that fills (users, pos, neg, n_valid) on the current stream first (inside the same
-        graph when captured; running it on a side stream beside the forward measured no faster)."""
-        self._ev_plan = self._ev_reach = None
+    def _plan_reach_rider(self, step: _TrainStep, batch) -> _Rider:
+        """The scatter plan of the loss backward and the weight gradient's row list. Where the step's riders apply, a ladder - a refused
+        rung launches nothing and the next one runs:
+          1. plan + reach marks as the guest of an SpMM launch (_forward_one_stream names the host);
+          2. the same as ONE launch of their own: the marking half of llmrec_batch_reach_rows behind the plan's blocks. After 1 or 2 the
+             flags are marked and the compaction rides in front of the fusion launch's blocks (_forward): two launches fewer;
+          3. the separate launches: the plan, then llmrec_batch_reach_rows' two. (All there is where the riders do not apply.)
+        On four streams they run on the ID chain's stream BEHIND its SpMMs (the plan is needed ~200 us later, the list at the step's far
+        end): the fusion waits for the chain's event, the loss launches for ev_plan, the weight gradient for ev_reach. Round 6, one box,
+        300 steps twice: 0.4539 / 0.4539 ms per step ahead of the SpMMs, 0.4470 / 0.4481 behind them (profiles/experiments/r06_step_chain.md)."""
+        users, pos, neg, n_valid = batch
+        by_item = self.iu.fwd
+        plan_reach = (users, pos, neg, users.numel(), n_valid, self.bpr_plan, by_item.n_cols, by_item.n_rows, by_item.rowptr, by_item.colidx,
+                      self.act_flags) if step.ride else None   # the arguments of rungs 1 and 2
 
-        def batch_lists():
-            # the scatter plan of the loss backward and the weight gradient's row list. On four streams they ride on the ID chain's stream
-            # BEHIND its SpMMs (the plan is needed ~200 us later, the list at the far end of the step): the fusion waits for the chain's
-            # event, the loss launches for the plan's (self._ev_plan), the weight gradient for the list's (self._ev_reach). Round 6, one
-            # box, 300 steps twice: 0.4539 / 0.4539 ms per step with both ahead of the SpMMs, 0.4470 / 0.4481 behind them
-            # (profiles/experiments/r06_step_chain.md).
-            # One stream, a reach list and a device sampler in the step: the marking half of llmrec_batch_reach_rows rides behind the plan's
-            # blocks (llmrec_bpr_scatter_plan_reach_mark) and the compaction in front of the fusion's (forward()): two launches fewer on
-            # the stream. A refused shape launches nothing and today's calls run.
-            if self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream:
-                if users.numel() > self.b_max:
-                    raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (users.numel(), self.b_max))
-                if _lib.call_unless_unsupported("llmrec_bpr_scatter_plan_reach_mark", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid),
-                                                _p(self.bpr_plan), self.iu.fwd.n_cols, self.iu.fwd.n_rows, _p(self.iu.fwd.rowptr),
-                                                _p(self.iu.fwd.colidx), _p(self.act_flags), ops._stream()):
-                    self._reach_pending = (users, pos, neg, n_valid)
-                    return
-            self.build_scatter_plan(users, pos, neg, n_valid)
-            self._ev_plan = self._mark()
+        def marked():
+            step.reach_pending = batch
+
+        def alone():
+            if step.ride and _lib.call_unless_unsupported("llmrec_bpr_scatter_plan_reach_mark", *_raw(plan_reach), ops._stream()):   # rung 2
+                return marked()
+            self.build_scatter_plan(users, pos, neg, n_valid)                                                        # rung 3
+            step.ev_plan = self._mark()
             if self.wgrad_rows:
-                ops.batch_reach_rows(users, pos, neg, n_valid, self.iu.fwd, self.act_flags, self.act_rows, self.act_n)
-                self._ev_reach = self._mark()
-        # Round 10, where the riders above apply: the sampler, the plan + marks and the loss values ride SpMM launches (_forward_one_stream,
-        # _backward_one_stream) - three launches fewer on the stream. A refused guest runs by its own entry point right ahead of its host.
-        self._ride_guests = bool(self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream)
-        if self._ride_guests:
-            if users.numel() > self.b_max:
-                raise RuntimeError("FusedStep: batch of %d exceeds b_max %d" % (users.numel(), self.b_max))
-            batch_lists.batch = (users, pos, neg, n_valid)
-            batch_lists.guest = lambda: ops.guest_plan_reach(users, pos, neg, users.numel(), n_valid, self.bpr_plan, self.iu.fwd.n_cols,
-                                                             self.iu.fwd.n_rows, self.iu.fwd.rowptr, self.iu.fwd.colidx, self.act_flags)
+                ops.batch_reach_rows(users, pos, neg, n_valid, by_item, self.act_flags, self.act_rows, self.act_n)
+                step.ev_reach = self._mark()
+        return _Rider(alone, (lambda: ops.guest_plan_reach(*plan_reach)) if step.ride else None, marked)             # rung 1
+
+    def step_eager(self, users, pos, neg, n_valid=None, sampler=None):
+        """sampler: optional callable - a plain one or sampler_of()'s rider - that fills (users, pos, neg, n_valid) on the current stream
+        first (inside the same graph when captured; running it on a side stream beside the forward measured no faster)."""
+        if sampler is not None and not isinstance(sampler, _Rider):
+            sampler = _Rider(sampler)
+        # riders (the sampler, the plan + reach marks and the loss values in SpMM launches: three launches fewer) apply on one stream with a
+        # device sampler in the step, a reach list to build and the folded loss-value launch
+        step = _TrainStep(ride=bool(self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream))
+        if step.ride:
+            self._check_batch(users.numel())
+        batch_lists = self._plan_reach_rider(step, (users, pos, neg, n_valid))
         self.spmm_edge_units = 0.0
         calls0 = _lib.n_calls
         try:
             self._stamp(0)
-            if self.multi_stream or self._ride_guests:           # the sampler rides beside the projection (forward()) / in an SpMM launch
-                self._train_forward(sampler, batch_lists)
+            if self.multi_stream or step.ride:                   # the sampler rides beside the projection (_forward_streams) / in an SpMM launch
+                self._train_forward(sampler, batch_lists, step)
             else:
                 if sampler is not None:
                     sampler()
                 batch_lists()
-                self._train_forward()
-            self.loss_backward(users, pos, neg, n_valid)
+                self._train_forward(step=step)
+            self.loss_backward(users, pos, neg, n_valid, step)
             if not self.inline_adamw:
                 self.opt.step(advanced=True)
             self._stamp(5)
@@ -953,17 +961,12 @@ class FusedStep:
             if self.wgrad_rows and self.act_expected is None and not torch.cuda.is_current_stream_capturing():
                 self._size_wgrad_for_rows()                      # first step: one read-back of the list length
         except Exception:
-            if not torch.cuda.is_current_stream_capturing():   # the invariant of LLMREC_SPARSE_ZERO may be broken: restore it
-                try:
-                    if self._reach_pending is not None:        # marked, not yet compacted: the flags' all-zero invariant too
-                        self._reach_pending = None
+            if not torch.cuda.is_current_stream_capturing():   # the all-zero invariant of the scatter targets may be broken: restore it
+                with contextlib.suppress(Exception):
+                    if step.reach_pending is not None:         # marked, not yet compacted: the flags' all-zero invariant too
                         self.act_flags.zero_()
                     self.reset_scatter_targets()
-                except Exception:
-                    pass
             raise
-        finally:
-            self._ride_guests = False
         return self.scal[1], self.scal[2], self.scal[3]
 
     def _size_wgrad_for_rows(self):
@@ -988,7 +991,7 @@ class FusedStep:
         if self.act_expected / factor <= want <= self.act_expected * factor:
             return False
         self._size_wgrad_for_rows()
-        if self.graph_exec is not None and getattr(self, "_capture_args", None) is not None:
+        if self.graph_exec is not None and self._capture_args is not None:
             self.capture(warm=False, **self._capture_args)
         return True
 
@@ -1032,25 +1035,25 @@ class FusedStep:
                 auc_sum = torch.zeros(1, dtype=torch.float64).pin_memory()
                 auc_ws = ops.auc_workspace(n, self.I, q.device, self.d)
 
+            # what the three scoring launches share: the queries, both tables, the train rows to mask
+            scoring = (n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
+                       _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None)
+
             def run():
                 # the evaluation's graph has TWO branches (the ID chain beside the projection; the profile chain stays on the main stream):
                 # 0.572 ms per replay back to back / 0.599 one at a time, against 0.73 - 0.76 / 0.595 with the training forward's three
                 # side branches - successive launches of a many-branch graph pay for their cross-queue joins (tools/eval_probe.py, round 6)
                 self.forward(profile_on_main=True)
                 if wide:
-                    _call("llmrec_score_topk_wide_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
-                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-                          K, _p(idx), _p(sc), _p(ws), ws.numel(), ops.topk_wide_mode(None, self.I, self.d, K), nnz)
+                    _call("llmrec_score_topk_wide_f32", *scoring, K, _p(idx), _p(sc), _p(ws), ws.numel(), ops.topk_wide_mode(None, self.I, self.d, K), nnz)
                 else:
-                    _call("llmrec_score_topk_mode_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
-                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-                          K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, ops.topk_mode(None, self.I, self.d, K))
+                    _call("llmrec_score_topk_mode_f32", *scoring, K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0,
+                          ops.topk_mode(None, self.I, self.d, K))
                 if held is not None:
                     ops.topk_eval_sums(idx, q, held[0], held[1], Ks, out=sums, ws=sums_ws)
                 if auc:
-                    _call("llmrec_score_auc_f32", n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
-                          _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-                          _p(held[0]), _p(held[1]), None, None, _c.c_void_p(auc_sum.data_ptr()), _p(auc_ws), auc_ws.numel())
+                    _call("llmrec_score_auc_f32", *scoring, _p(held[0]), _p(held[1]), None, None, _c.c_void_p(auc_sum.data_ptr()), _p(auc_ws),
+                          auc_ws.numel())
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -1060,26 +1063,26 @@ class FusedStep:
             g = torch.cuda.CUDAGraph()
             with _capture_without_gc(g, self.multi_stream):
                 run()
-            ev = self._eval_graphs[key] = (g, idx, sc, q, train, ws, sums, sums_ws, held, auc_sum, auc_ws)     # keeps the captured operands alive
-        ev[0].replay()
+            ev = self._eval_graphs[key] = _EvalGraph(g, idx, sc, q, train, ws, sums, sums_ws, held, auc_sum, auc_ws)
+        ev.graph.replay()
         self._last_eval = ev
-        return ev[1], ev[2]
+        return ev.idx, ev.scores
 
     def eval_sums(self):
         """The pinned [4, len(Ks)] sums of the LAST eval_topk(..., held=...) replay; synchronises the current stream first."""
-        ev = getattr(self, "_last_eval", None)
-        if ev is None or ev[6] is None:
+        ev = self._last_eval
+        if ev is None or ev.sums is None:
             raise RuntimeError("FusedStep.eval_sums: the last evaluation was not captured with a held-out set")
         torch.cuda.current_stream().synchronize()
-        return ev[6]
+        return ev.sums
 
     def eval_auc_sum(self):
         """The pinned float64 [1] sum of the per-user AUCs of the LAST eval_topk(..., auc=True) replay; synchronises the current stream first."""
-        ev = getattr(self, "_last_eval", None)
-        if ev is None or ev[9] is None:
+        ev = self._last_eval
+        if ev is None or ev.auc_sum is None:
             raise RuntimeError("FusedStep.eval_auc_sum: the last evaluation was not captured with auc=True")
         torch.cuda.current_stream().synchronize()
-        return ev[9]
+        return ev.auc_sum
 
     def drop_eval_graph(self, query_users: torch.Tensor):
         """Release every captured evaluation (graph, result lists, top-K workspace) of this query tensor."""
@@ -1099,14 +1102,12 @@ class FusedStep:
 
     @staticmethod
     def sampler_of(batcher, st):
-        """step_eager's `sampler` for a DeviceBatcher filling the buffers st (users / pos / neg / n_valid): the call, and as its `guest`
-        attribute the same call as the guest descriptor of an SpMM launch."""
+        """step_eager's `sampler` for a DeviceBatcher filling the buffers st (users / pos / neg / n_valid): the rider whose run() is the
+        batcher's own launch and whose guest (where the batcher offers one) is the same call as the guest descriptor of an SpMM launch."""
         if batcher is None:
             return None
-        fill = lambda: batcher.fill(st["users"], st["pos"], st["neg"], st["n_valid"])
-        if hasattr(batcher, "guest"):
-            fill.guest = lambda: batcher.guest(st["users"], st["pos"], st["neg"], st["n_valid"])
-        return fill
+        args = (st["users"], st["pos"], st["neg"], st["n_valid"])
+        return _Rider(lambda: batcher.fill(*args), (lambda: batcher.guest(*args)) if hasattr(batcher, "guest") else None)
 
     def capture(self, warm_users=None, warm_pos=None, warm_neg=None, warm_n_valid=None, batcher=None, unroll: int = 1, warm: bool = True):
         """Capture one step (fixed batch capacity b_max, actual size on the device in n_valid).
@@ -1117,10 +1118,9 @@ class FusedStep:
         st = self._make_static() if (warm or self.static is None) else self.static
         self.batcher = batcher
         self._capture_args = {"batcher": batcher, "unroll": unroll}
-        if batcher is not None:
-            if batcher.capacity != self.b_max:
-                raise RuntimeError("FusedStep.capture: batcher capacity %d != b_max %d" % (batcher.capacity, self.b_max))
-        elif warm:
+        if batcher is not None and batcher.capacity != self.b_max:
+            raise RuntimeError("FusedStep.capture: batcher capacity %d != b_max %d" % (batcher.capacity, self.b_max))
+        if batcher is None and warm:
             self._load(warm_users, warm_pos, warm_neg, warm_n_valid)
 
         def one_step():
@@ -1150,7 +1150,7 @@ class FusedStep:
     def run_steps(self, n: int):
         """n training steps of the captured graph(s) (in-graph sampler only): as many replays of the `unroll`-step graph as fit, single
         steps for the remainder. Returns the logged scalars of the last step."""
-        if self.graph_exec is None or getattr(self, "batcher", None) is None:
+        if self.graph_exec is None or self.batcher is None:
             raise RuntimeError("FusedStep.run_steps: capture(batcher=...) first")
         k = self.graph_unroll if self.graph_multi is not None else 0
         while k and n >= k:
@@ -1178,7 +1178,7 @@ class FusedStep:
     def step_packed(self, host_block: torch.Tensor):
         """One training step from a host-sampled batch already laid out as packed_layout() says (pinned memory): ONE asynchronous H2D copy
         into the captured step's static buffers, then the graph replay - no per-tensor device copies (step(users, pos, neg) issues four)."""
-        if self.graph_exec is None or getattr(self, "batcher", None) is not None:
+        if self.graph_exec is None or self.batcher is not None:
             raise RuntimeError("FusedStep.step_packed: capture(users, pos, neg) first (a graph without an in-graph sampler)")
         self.static_block.copy_(host_block, non_blocking=True)
         self.graph_exec.replay()
@@ -1190,10 +1190,10 @@ class FusedStep:
         if self.graph_exec is None:
             return self.step_eager(users, pos, neg, n_valid)
         if users is not None:
-            if getattr(self, "batcher", None) is not None:
+            if self.batcher is not None:
                 raise RuntimeError("FusedStep.step: this graph samples its own batch; call step() without arguments")
             self._load(users, pos, neg, n_valid)
-        elif getattr(self, "batcher", None) is None:
+        elif self.batcher is None:
             raise RuntimeError("FusedStep.step: a batch is needed (the graph was captured without a sampler)")
         self.graph_exec.replay()
         return self.scal[1], self.scal[2], self.scal[3]

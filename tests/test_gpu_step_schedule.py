@@ -6,7 +6,8 @@ One eager training step is recorded as the ordered list of what the host issued:
   ["wait_event", stream, k]          torch.cuda.Stream.wait_event (k = the record it waits for; null = not recorded in this step),
   ["wait_stream", waiting, waited]   torch.cuda.Stream.wait_stream,
 with stream in main / s1 / s2 / s3 / other. Launches + synchronisation are the whole dependency structure of the eager step and with it
-the capture order of the step's graph. tests/step_schedule_expected.json holds the lists of the commit that introduced this test; a
+the capture order of the step's graph. tests/step_schedule_expected.json holds the lists of the commit that introduced this test (the two
+device_sampler variants: of the parent of the commit that added them, which then restructured FusedStep without moving a launch); a
 change of FusedStep's schedule shows up as an exact difference (LLMREC_STEP_SCHEDULE_WRITE=<file> writes the recorded lists there
 instead of comparing - for a change that MEANS to move the schedule)."""
 import json
@@ -23,7 +24,7 @@ from tests.conftest import GoldenCase
 
 EXPECTED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "step_schedule_expected.json")
 WRITE_TO = os.environ.get("LLMREC_STEP_SCHEDULE_WRITE")
-GROUPED = re.compile(r"llmrec_(spmm_multi_f32|fuse_\w+_multi\w*|bpr_multi_\w+|linear_\w+_(grouped|multi)\w*)$")
+GROUPED = re.compile(r"llmrec_(spmm_multi(_guest)?_f32|fuse_\w+_multi\w*|bpr_multi_\w+|linear_\w+_(grouped|multi)\w*)$")
 KNOBS = ("LLMREC_STREAMS", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM", "LLMREC_WGRAD_ROWS", "LLMREC_DEVICE_SAMPLER",
          "LLMREC_CHECK_ZERO")
 VARIANTS = {
@@ -35,6 +36,8 @@ VARIANTS = {
     "f32": {"LLMREC_GEMM": "f32"},
     "dense_wgrad": {"LLMREC_WGRAD_ROWS": "0"},
     "data_parallel": {},
+    "device_sampler": {"LLMREC_DEVICE_SAMPLER": "1"},                 # the sampler, the plan + reach marks and the loss values ride SpMM launches
+    "device_sampler_refused": {"LLMREC_DEVICE_SAMPLER": "1"},         # ... with every guest launch refused: the next rungs of the ladder
 }
 
 
@@ -111,6 +114,13 @@ def _record_second_step(golden, variant, monkeypatch):
         step = tr._fused_step()
         assert step, "the golden configuration runs the fused step"
         run = lambda s: tr.train_step(*_batch(golden, s))
+        if variant.startswith("device_sampler"):
+            # the step the benchmark times: the batch is sampled on the device, inside the step (tests/test_gpu_spmm_guests.py drives it so)
+            from llmrec_amd.fused import FusedStep
+            tr.model_mm.train()
+            batcher, st = tr._device_batcher(), step._make_static()
+            step._refuse_guests = variant == "device_sampler_refused"
+            run = lambda s: step.step_eager(st["users"], st["pos"], st["neg"], st["n_valid"], sampler=FusedStep.sampler_of(batcher, st))
     run(0)
     torch.cuda.synchronize()
     with monkeypatch.context() as mp:
