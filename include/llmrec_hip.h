@@ -142,6 +142,24 @@ typedef struct {
      *                 explicit row list this is "these rows of A X"; all other rows of Y keep their contents. */
     const uint8_t* x_row_mask; int32_t x_mask_active; uint8_t* y_row_flag; const uint8_t* z_row_flag; const uint8_t* y_row_gate;
     const uint8_t* y_row_needed; int32_t rows_listed_only;
+    /* SLICE-RANGED mask with a DEVICE stamp (the training step's in-place side product dU_cat += A_iu^T dI_cat: the attribute slices of
+     * dI_cat are zero outside the rows of the batch's items, which the loss launch stamps - llmrec_bpr_multi_select_bwd_f32).
+     *   x_mask_stamp  NULL = none of this. Else a device counter: the active byte of x_row_mask is LLMREC_ROW_STAMP(*x_mask_stamp), read
+     *                 by the kernel, so it may change between replays of a captured launch (x_mask_active is ignored);
+     *   mask_from_slice (0 .. d / slice_width; slice_width = 0 counts as one slice): in the (row, slice) tasks with slice >=
+     *                 mask_from_slice, rows of X whose x_row_mask byte differs from the stamp are PROMISED all-zero in that slice's columns
+     *                 and are not read there (they may hold anything); tasks of lower slices run exactly as without a mask.
+     * The result equals the unmasked product on the promised zeros bit for bit: the skipped addends are w * (+0) on an accumulator that
+     * starts at +0. IN-PLACE SKIP: when the product is the in-place accumulate (Z aliases Y with ldz = ldy, alpha = 1, op NONE, no
+     * post_scale), a masked task whose row has no active neighbour neither reads Z nor writes Y - the row keeps its bits (the unmasked
+     * product would turn a -0 of Z into +0, nothing else); rows of the block and split buckets are always computed and written.
+     * Excludes y_row_flag, z_row_flag, y_row_gate, y_row_needed, rows_listed_only and the softmax epilogues (LLMREC_EINVAL). Compiled for
+     * the pattern-only float4 products weighted by col_scale (val NULL) of 33..64 columns per slice (16 lanes per row) - alone, in
+     * llmrec_spmm_multi_f32 (whose other members run unmasked beside it; they must be products of the same family weighted by col_scale
+     * alone, without y_row_needed) and as the host of the LLMREC_SPMM_GUEST_LOSSES guest; any
+     * other shape, variant, company or guest returns LLMREC_EUNSUPPORTED before anything is launched and the caller issues the unmasked
+     * call (which is correct whenever the promised rows really hold zeros). */
+    const int32_t* x_mask_stamp; int32_t mask_from_slice;
 } llmrec_spmm_epilogue_t;
 /* Round 5 - "these rows of A X" with the row list AND its length in device memory (the row-restricted forward of the row-sharded step,
  * without a host read-back: llmrec_amd/dist_fused.py). Pattern-only operands (A = diag(row_scale) P).
@@ -225,7 +243,8 @@ int llmrec_spmm_multi_f32(int32_t n, const llmrec_spmm_problem_t* problems, llmr
  * Every SpMM result and every guest output is bit for bit that of the separate calls: a row's, key's, slot's or tree's work and its order
  * of additions do not depend on the block that holds it. No block waits for another one. The caller guarantees what it guarantees for
  * two launches that may overlap: the guest reads nothing a problem writes and writes nothing a problem reads or writes.
- * Compiled for the step's instance only - 16 lanes per row, float4, d (or the slice width) in 33..64, unmasked, unweighted or weighted.
+ * Compiled for the step's instance only - 16 lanes per row, float4, d (or the slice width) in 33..64, unmasked, unweighted or weighted
+ * (and, for the LOSSES guest, the slice-masked weighted product: llmrec_spmm_epilogue_t.x_mask_stamp).
  * Returns LLMREC_EUNSUPPORTED, BEFORE anything is launched, for every other group (also one llmrec_spmm_multi_f32 would refuse, or
  * without a non-empty problem), for a guest its body cannot take (B_max > LLMREC_BPR_MAX_B, an empty capacity) and for a plan whose LDS
  * would cost the launch its occupancy (B_max > LLMREC_SPMM_GUEST_MAX_PLAN_B): the caller then issues the separate calls. n = 1 hosts the
@@ -430,6 +449,9 @@ typedef struct {
                                    rows it touches): the kernel then writes the regulariser's term for the first n_reg_terms streams and zeros
                                    for the others without reading anything else - the same bits, ~half the traffic at 10 % touched rows */
     const int32_t* row_stamp;   /* device counter that defines ACTIVE, or NULL (active = non-zero flag) */
+    int32_t zero_skip_from_term; /* 0 = none. Else (>= n_reg_terms, needs row_flags): in a row that is not ACTIVE the terms at or beyond this index are
+                                   NOT WRITTEN (they would be zeros; the rows keep stale contents) - for terms whose only reader skips the
+                                   rows that are not ACTIVE by the same flags and stamp (llmrec_spmm_epilogue_t.x_mask_stamp) */
 } llmrec_fuse_bwd_problem_t;
 int llmrec_fuse_bwd_src_multi_f32(int32_t n_problems, const llmrec_fuse_bwd_problem_t* problems_host, int32_t d, llmrec_stream_t stream);
 

@@ -221,6 +221,7 @@ struct FuseMulti {
     const float* dOut[FUSE_MAX_PROBLEMS]; int64_t lddo[FUSE_MAX_PROBLEMS];    // backward
     const uint8_t* row_flags[FUSE_MAX_PROBLEMS];                              // backward: not active = dOut and the sources of this row are all-zero
     const int32_t* row_stamp[FUSE_MAX_PROBLEMS];                              // device counter defining "active" (NULL: non-zero)
+    int n_written[FUSE_MAX_PROBLEMS];                                         // backward: terms written in a row that is not active (zero_skip_from_term)
     int block_begin;                                                          // first block of problem 1
     int n_sumsq;                                                              // forward: the first n_sumsq norm terms' squared norms are summed
     float* sumsq_partial;                                                     // ... into one partial per block [gridDim.x]
@@ -290,7 +291,7 @@ __device__ __forceinline__ void fuse_bwd_src_multi_rows(int vb, int nvb, int d, 
         if (m.row_flags[prob] && !(m.row_stamp[prob] ? m.row_flags[prob][row] == LLMREC_ROW_STAMP(m.row_stamp[prob][0]) : m.row_flags[prob][row] != 0)) {
             // a row the batch did not touch: dOut = 0 and the sources are 0, so every stream's gradient is w (0 - x 0) = +0 and
             // what is left is the regulariser's reg2 * x on the first n_reg streams - the same bits as the general path below
-            for (int i = 0; i < a.n_norm; ++i) {
+            for (int i = 0; i < m.n_written[prob]; ++i) {                // (the terms beyond: zeros nobody reads - zero_skip_from_term)
                 o.fill(0.f);
                 if (i < a.n_reg) {
                     t.load(a.norm_terms[i] + row * a.norm_ld[i], gl, d);
@@ -1116,7 +1117,10 @@ static int fill_fuse_bwd_multi(int32_t n_problems, const llmrec_fuse_bwd_problem
             vec4 = vec4 && q.norm_ld[i] % 4 == 0 && q.d_ld[i] % 4 == 0 && aligned16(q.norm_terms[i]) && aligned16(q.d_terms[i]) &&
                    (!a.s_terms[i] || (a.s_ld[i] % 4 == 0 && aligned16(a.s_terms[i])));
         }
+        LLMREC_CHECK_ARG(q.zero_skip_from_term == 0 || (q.row_flags && q.zero_skip_from_term >= q.n_reg_terms),
+                         "fuse_bwd_src_multi: problem %d: zero_skip_from_term needs row_flags and must not skip a regularised term", k);
         m.rows[k] = q.rows; m.dOut[k] = q.dOut; m.lddo[k] = q.lddo; m.row_flags[k] = q.row_flags; m.row_stamp[k] = q.row_stamp;
+        m.n_written[k] = q.zero_skip_from_term > 0 && q.zero_skip_from_term < q.n_norm ? q.zero_skip_from_term : q.n_norm;
         blocks[k] = grid_for(q.rows, ROWS_PER_BLOCK);
     }
     m.block_begin = blocks[0];

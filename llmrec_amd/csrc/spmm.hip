@@ -29,6 +29,7 @@
 // graph without any imbalance reaches 35 G gathers/s on the synthetic graphs' popularity - this kernel's ceiling.
 #include "common.h"
 #include "guests.h"
+#include <type_traits>
 
 namespace llmrec {
 
@@ -103,6 +104,13 @@ struct SpmmArgs {
     const uint8_t* y_needed;     // rows whose byte != x_active are neither computed nor written (short-row range)
     int32_t listed_only;         // no short-row range at all: only the plan's row lists are computed
     int32_t pipe;                // > 1: tasks per lane group of the short-row range, run as a software pipeline (rows_body_pipe)
+    // slice-ranged mask with a device stamp (llmrec_spmm_epilogue_t.x_mask_stamp; the SMASK kernels only): in tasks whose first column is
+    // >= smask_col0, X rows whose smask byte differs from LLMREC_ROW_STAMP(*smask_stamp) are all-zero and are not read. smask NULL and
+    // smask_col0 = n_slices * d: a member of a grouped launch without a mask of its own
+    const uint8_t* smask;
+    const int32_t* smask_stamp;
+    int32_t smask_col0;
+    int32_t smask_inplace;       // Y += A X in place (Z = Y, alpha 1, no op, no post_scale): a masked task without an active neighbour leaves its row alone
     // plan
     const int32_t* slot_row;     // non-NULL: rowptr / colidx are the PERMUTED CSR of the plan - CSR row `slot` is output row slot_row[slot], the
     int32_t n_short_rows;        // first n_short_rows slots are the lane-group bucket, the plan's lists hold slots (llmrec_spmm_plan_t)
@@ -167,7 +175,8 @@ __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_
 }
 
 template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK], int& any) {
+__device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK], int& any,
+                                                 const uint8_t* xm, int xa) {
     if constexpr (!MASKED) {
         accumulate_range_plain<LPR, NCHUNK, VEC, WEIGHTED>(a, col0, s, e, gl, acc);
     } else {
@@ -182,7 +191,7 @@ __device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0
                     myw = a.val ? a.val[base + gl] : 1.0f;
                     if (a.col_scale) myw *= a.col_scale[myc];
                 }
-                myact = (int)a.x_mask[myc] == a.x_active; any |= myact;
+                myact = (int)xm[myc] == xa; any |= myact;
             }
             // only the ACTIVE columns of this chunk are visited (ascending, as in the dense loop: the skipped terms are exact zeros)
             const unsigned long long bal = __ballot(myact != 0);
@@ -323,9 +332,9 @@ __device__ __forceinline__ void rows_body(const SpmmArgs& a, int64_t block) {
         const unsigned long long gm = LPR >= 64 ? ~0ull : (((1ull << LPR) - 1ull) << g0);
         const bool any_g = (bal & gm) != 0ull;
         zero_row = write_row_flag(a, row, any_g, slice == 0 && gl == 0);
-        if (any_g) accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any);
+        if (any_g) accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any, a.x_mask, a.x_active);
     } else {
-        accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any);
+        accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, gl, acc, any, a.x_mask, a.x_active);
     }
     finish_row<LPR, NCHUNK, VEC>(a, col0, row, gl, acc, zero_row);
 }
@@ -424,16 +433,139 @@ __device__ __forceinline__ void rows_body_pipe(const SpmmArgs& a, int64_t block,
     }
 }
 
+// The pipelined short rows of the SLICE-MASKED product (SpmmArgs.smask: the step's in-place side product, whose attribute slices of X are
+// zero outside the rows the loss launch stamped). The mask bytes depend on the column indices, so the pipeline is one stage deeper than
+// rows_body_pipe: the row pointers of task i + 3, the indices of task i + 2 and the mask bytes of task i + 1 are in flight while the rows
+// of task i are gathered - still one round trip per task. An inactive column becomes index -1 and its gather is predicated off: the
+// value that enters the fma chain is the +0 the promised-zero row would have delivered, so the sums are the unmasked product's, bit for
+// bit. A masked task whose lane group sees no active column gathers nothing; in the in-place form it leaves its row untouched
+// (Y[r] + 0 = Y[r]). Tasks below smask_col0 run as in rows_body_pipe. Any task count per lane group (pipe >= 1). The weights are
+// col_scale (the host admits pattern-only operands weighted by it): a stage carries two words, and the kernel keeps its host's 5 waves.
+template <int LPR, int NCHUNK, int VEC>
+__device__ __forceinline__ void rows_body_pipe_smask(const SpmmArgs& a, int64_t block, int64_t n_blocks) {
+    constexpr int GPB = TPB / LPR;
+    constexpr int NI = (LLMREC_SPMM_LONG_ROW + LPR - 1) / LPR;
+    constexpr int NBITS = 6, NMAX = LLMREC_SPMM_LONG_ROW + 1;           // a task's (slice, min(nnz, NMAX)) in one register: slice << NBITS | nnz
+    static_assert(NMAX < (1 << NBITS), "rows_body_pipe_smask: the row length does not fit its bits");
+    const int gl = threadIdx.x & (LPR - 1);
+    const int g0 = (int)(threadIdx.x & 63) / LPR * LPR;
+    const int32_t n_list = (int32_t)(a.slot_row ? (int64_t)a.n_short_rows : a.n_rows);      // (32-bit task ids: checked by the host)
+    const int32_t n_tasks = n_list * a.n_slices, G = (int32_t)n_blocks * GPB;
+    const int32_t t0 = (int32_t)block * GPB + (int32_t)(threadIdx.x / LPR);
+    if (t0 >= n_tasks) return;
+    const int32_t stamp = a.smask ? (int32_t)LLMREC_ROW_STAMP(a.smask_stamp[0]) : 0;        // (uniform)
+    auto level1 = [&](int32_t t, int32_t& s_, int32_t& sn) {                                  // the row pointers
+        const int32_t slice = t / n_list, slot = t - slice * n_list;
+        s_ = a.rowptr[slot];
+        sn = slice << NBITS | min(a.rowptr[slot + 1] - s_, NMAX);
+    };
+    auto level2 = [&](int32_t s_, int32_t sn, int32_t (&c)[NI]) {                             // the row's column indices (<= LONG_ROW of them)
+        const int32_t n_ = sn & 63;
+#pragma unroll
+        for (int k = 0; k < NI; ++k) { const int j = k * LPR + gl; c[k] = (j < n_ && n_ <= LLMREC_SPMM_LONG_ROW) ? a.colidx[s_ + j] : 0; }
+    };
+    auto level3 = [&](int32_t sn, const int32_t (&c)[NI], int32_t (&m)[NI]) {                 // the columns' mask bytes (masked slices only)
+        const int32_t n_ = sn & 63;
+#pragma unroll
+        for (int k = 0; k < NI; ++k) {
+            const int j = k * LPR + gl;
+            m[k] = stamp;
+            if ((sn >> NBITS) * a.d >= a.smask_col0 && j < n_ && n_ <= LLMREC_SPMM_LONG_ROW) m[k] = (int32_t)a.smask[c[k]];
+        }
+    };
+    int32_t snD, cD[NI];                                                // task i: gathers (inactive columns: -1)
+    int32_t sC = 0, snC = 0, cC[NI], mC[NI];                            // task i + 1: mask bytes
+    int32_t sB = 0, snB = 0;                                            // task i + 2: indices
+#pragma unroll
+    for (int k = 0; k < NI; ++k) { cC[k] = 0; mC[k] = 0; }
+    int32_t t2 = t0 + 2 * G;
+    bool has1 = t0 + G < n_tasks, has2 = has1 && t2 < n_tasks;
+    int32_t sD;
+    level1(t0, sD, snD);                                                // prologue: the first task's three dependent levels, the second's two,
+    if (has1) level1(t0 + G, sC, snC);                                  // the third's one
+    if (has2) level1(t2, sB, snB);
+    level2(sD, snD, cD);
+    if (has1) level2(sC, snC, cC);
+    level3(snD, cD, mC);
+#pragma unroll
+    for (int k = 0; k < NI; ++k) cD[k] = mC[k] == stamp ? cD[k] : -1;
+    for (;;) {
+        int32_t sA = 0, snA = 0, cB[NI];
+        const int32_t t3 = t2 + G;
+        const bool has3 = has2 && t3 < n_tasks;
+#pragma unroll
+        for (int k = 0; k < NI; ++k) cB[k] = 0;
+        if (has2) level2(sB, snB, cB);                                  // in flight while task i's rows are gathered
+        if (has3) level1(t3, sA, snA);
+        if (has1) level3(snC, cC, mC);
+        const int32_t nD = snD & 63, sliceD = snD >> NBITS, colD = sliceD * a.d;
+        if (nD <= LLMREC_SPMM_LONG_ROW) {                               // (longer: a row of another bucket, plain plans only)
+            bool any = true;
+            if (colD >= a.smask_col0) {                                 // (uniform per lane group) a masked task: does the row have an active column?
+                bool act = false;
+#pragma unroll
+                for (int k = 0; k < NI; ++k) act |= k * LPR + gl < nD && cD[k] >= 0;
+                any = ((__ballot(act) >> g0) & ((1ull << LPR) - 1ull)) != 0ull;
+            }
+            if (any || !a.smask_inplace) {
+                const int32_t slotD = (t2 - 2 * G) - sliceD * n_list;
+                const int32_t rowD = a.slot_row ? a.slot_row[slotD] : slotD;       // (the output row: beside the gathers, read behind them)
+                float w0[NI];
+#pragma unroll
+                for (int k = 0; k < NI; ++k) w0[k] = (k * LPR + gl < nD && cD[k] >= 0) ? a.col_scale[cD[k]] : 0.f;
+                Vec<VEC> acc[NCHUNK];
+#pragma unroll
+                for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
+#pragma unroll
+                for (int ki = 0; ki < NI; ++ki) {
+                    const int nk = any ? min(LPR, nD - ki * LPR) : 0;   // (uniform per lane group)
+                    for (int t = 0; t < nk; t += UNROLL) {
+                        Vec<VEC> v[UNROLL][NCHUNK];
+                        float w[UNROLL];
+#pragma unroll
+                        for (int u = 0; u < UNROLL; ++u) {
+                            const int tt = t + u;
+                            const int32_t c = __shfl(cD[ki], tt & (LPR - 1), LPR);
+                            const float* xr = a.X + (int64_t)c * a.ldx + colD;
+#pragma unroll
+                            for (int k = 0; k < NCHUNK; ++k) {
+                                const int col = (k * LPR + gl) * VEC;
+                                if (tt < nk && c >= 0 && col < a.d) v[u][k].load(xr + col);
+                                else v[u][k].zero();
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < UNROLL; ++u) {
+                            w[u] = __shfl(w0[ki], (t + u) & (LPR - 1), LPR);
+#pragma unroll
+                            for (int k = 0; k < NCHUNK; ++k) acc[k].fma(w[u], v[u][k]);
+                        }
+                    }
+                }
+                finish_row<LPR, NCHUNK, VEC>(a, colD, rowD, gl, acc, false);
+            }
+        }
+        if (!has1) break;
+        snD = snC;
+#pragma unroll
+        for (int k = 0; k < NI; ++k) { cD[k] = mC[k] == stamp ? cC[k] : -1; cC[k] = cB[k]; }
+        sC = sB; snC = snB;
+        sB = sA; snB = snA;
+        t2 = t3; has1 = has2; has2 = has3;
+    }
+}
+
 // one wavefront over [s, e): the 64/LPR lane groups take contiguous parts, butterfly sum -> every group holds the total
 template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ void wave_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int lane, Vec<VEC> (&acc)[NCHUNK], int& any) {
+__device__ __forceinline__ void wave_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int lane, Vec<VEC> (&acc)[NCHUNK], int& any,
+                                           const uint8_t* xm, int xa) {
     constexpr int G = 64 / LPR;
     const int gl = lane & (LPR - 1), g = lane / LPR;
     const int32_t per = (((e - s) + G - 1) / G + LPR - 1) / LPR * LPR;      // multiple of LPR: aligned index loads
     const int32_t gs = min(s + g * per, e), ge = min(gs + per, e);
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
-    accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, gs, ge, gl, acc, any);
+    accumulate_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, gs, ge, gl, acc, any, xm, xa);
 #pragma unroll
     for (int off = LPR; off < 64; off <<= 1) {
 #pragma unroll
@@ -468,28 +600,58 @@ __device__ __forceinline__ void wave_rows_body(const SpmmArgs& a, int32_t block)
             if (base + lane < re) any |= (int)a.x_mask[a.colidx[base + lane]] == a.x_active;
         const bool any_w = __ballot(any != 0) != 0ull;
         zero_row = write_row_flag(a, row, any_w, col0 == 0 && lane == 0);
-        if (any_w) wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, rs, re, lane, acc, any);
+        if (any_w) wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, rs, re, lane, acc, any, a.x_mask, a.x_active);
         else {
 #pragma unroll
             for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
         }
     } else {
-        wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], lane, acc, any);
+        wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], lane, acc, any, a.x_mask, a.x_active);
     }
     if (lane < LPR) finish_row<LPR, NCHUNK, VEC>(a, col0, row, lane, acc, zero_row);
+}
+
+// wave_rows_body of the slice-masked product (SpmmArgs.smask): a task at or beyond smask_col0 scans its columns' mask bytes first and gathers
+// the active ones only (the masked loop: ascending, the skipped terms are exact +0); without an active column the in-place form leaves
+// the row untouched. Tasks of lower slices run the plain loop.
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED>
+__device__ __forceinline__ void wave_rows_body_smask(const SpmmArgs& a, int32_t block) {
+    const int lane = threadIdx.x & 63;
+    const int64_t task = (int64_t)block * (TPB / 64) + (threadIdx.x >> 6);
+    if (task >= (int64_t)a.n_wave_rows * a.n_slices) return;
+    int32_t crow, row, slot; int64_t col0;
+    list_task(a, a.wave_rows, a.n_wave_rows, task, crow, row, col0, slot);
+    const int32_t rs = a.rowptr[crow], re = a.rowptr[crow + 1];
+    Vec<VEC> acc[NCHUNK];
+    int any = 0;
+    if (col0 >= a.smask_col0) {                                          // (wave-uniform)
+        const int stamp = (int)LLMREC_ROW_STAMP(a.smask_stamp[0]);
+        for (int32_t base = rs; base < re; base += 64)
+            if (base + lane < re) any |= (int)a.smask[a.colidx[base + lane]] == stamp;
+        if (__ballot(any != 0) != 0ull) wave_range<LPR, NCHUNK, VEC, WEIGHTED, true>(a, col0, rs, re, lane, acc, any, a.smask, stamp);
+        else if (a.smask_inplace) return;
+        else {
+#pragma unroll
+            for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
+        }
+    } else {
+        wave_range<LPR, NCHUNK, VEC, WEIGHTED, false>(a, col0, rs, re, lane, acc, any, nullptr, 0);
+    }
+    if (lane < LPR) finish_row<LPR, NCHUNK, VEC>(a, col0, row, lane, acc, false);
 }
 
 // one block over [s, e): the 8 waves take contiguous parts, summed through LDS in wave order; the total ends up in the
 // first lane group of wave 0 (returns true there)
 template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK]) {
+__device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK],
+                                            const uint8_t* xm, int xa) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     constexpr int NW = TPB / 64;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int32_t per = (((e - s) + NW - 1) / NW + 63) / 64 * 64;
     const int32_t ws = min(s + w * per, e), we = min(ws + per, e);
     int any = 0;                                                         // (long rows: their output flag is set unconditionally)
-    wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, ws, we, lane, acc, any);
+    wave_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, ws, we, lane, acc, any, xm, xa);
     if (w > 0 && lane < LPR) {
 #pragma unroll
         for (int k = 0; k < NCHUNK; ++k) acc[k].store(lds + (w - 1) * ROWW + (k * LPR + lane) * VEC);
@@ -504,25 +666,40 @@ __device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int
     return true;
 }
 
+// block_range of the slice-masked product: the masked loop at or beyond smask_col0 (block-uniform), the plain one below
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED>
+__device__ __forceinline__ bool block_range_smask(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK]) {
+    if (col0 >= a.smask_col0)
+        return block_range<LPR, NCHUNK, VEC, WEIGHTED, true>(a, col0, s, e, lds, acc, a.smask, (int)LLMREC_ROW_STAMP(a.smask_stamp[0]));
+    return block_range<LPR, NCHUNK, VEC, WEIGHTED, false>(a, col0, s, e, lds, acc, nullptr, 0);
+}
+
 // One problem's block b (a global block id) of the ranges of SpmmArgs: the heavy blocks come first. The segment partials are indexed by
 // the problem-local block id, so a grouped launch addresses them exactly like a launch of its own.
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
+// SMASK (with MASKED = false): the slice-masked product - the run-time choice between the plain and the masked loops per task.
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool SMASK = false>
 __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* red_lds) {
+    static_assert(!SMASK || (WEIGHTED && !MASKED), "spmm_body: the slice-masked product is weighted and has no host-stamped mask");
     if (b >= a.blk_wave) {
         const int64_t lb = (int64_t)b - a.blk_wave;
-        if (!MASKED && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)a.blk_end - a.blk_wave);     // (block-uniform)
+        if constexpr (SMASK) rows_body_pipe_smask<LPR, NCHUNK, VEC>(a, lb, (int64_t)a.blk_end - a.blk_wave);
+        else if (!MASKED && a.pipe > 1) rows_body_pipe<LPR, NCHUNK, VEC, WEIGHTED>(a, lb, (int64_t)a.blk_end - a.blk_wave);     // (block-uniform)
         else rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, lb);
         return;
     }
     if (b >= a.blk_block) {
-        wave_rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, b - a.blk_block);
+        if constexpr (SMASK) wave_rows_body_smask<LPR, NCHUNK, VEC, WEIGHTED>(a, b - a.blk_block);
+        else wave_rows_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, b - a.blk_block);
         return;
     }
     Vec<VEC> acc[NCHUNK];
     int32_t crow, row, slot; int64_t col0;
     if (b >= a.blk_seg) {
         list_task(a, a.block_rows, a.n_block_rows, b - a.blk_seg, crow, row, col0, slot);
-        if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], red_lds, acc)) {
+        bool mine;                                                       // (long rows of the slice-masked product are always computed and written)
+        if constexpr (SMASK) mine = block_range_smask<LPR, NCHUNK, VEC, WEIGHTED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], red_lds, acc);
+        else mine = block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, a.rowptr[crow], a.rowptr[crow + 1], red_lds, acc, a.x_mask, a.x_active);
+        if (mine) {
             if (MASKED && col0 == 0 && threadIdx.x == 0 && a.y_flag) a.y_flag[row] = (uint8_t)a.x_active;   // conservative: "may be non-zero"
             finish_row<LPR, NCHUNK, VEC>(a, col0, row, threadIdx.x, acc);
         }
@@ -538,7 +715,10 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* r
     const int32_t re = a.rowptr[crow + 1];
     const int32_t s = a.rowptr[crow] + k_in_row * a.segment;
     const int32_t e = min(s + a.segment, re);
-    if (block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, red_lds, acc)) {
+    bool mine;
+    if constexpr (SMASK) mine = block_range_smask<LPR, NCHUNK, VEC, WEIGHTED>(a, col0, s, e, red_lds, acc);
+    else mine = block_range<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, col0, s, e, red_lds, acc, a.x_mask, a.x_active);
+    if (mine) {
         if (MASKED && col0 == 0 && k_in_row == 0 && threadIdx.x == 0 && a.y_flag) a.y_flag[row] = (uint8_t)a.x_active;   // conservative
         float* pr = a.partials + (int64_t)lb * a.d;
 #pragma unroll
@@ -555,6 +735,14 @@ __global__ __launch_bounds__(TPB) void spmm_kernel(SpmmArgs a) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
     spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(a, (int32_t)blockIdx.x, red_lds);
+}
+
+// The slice-masked product (SpmmArgs.smask), weighted: an instance of its own, so the kernels above keep their registers.
+template <int LPR, int NCHUNK, int VEC>
+__global__ __launch_bounds__(TPB, 5) void spmm_smask_kernel(SpmmArgs a) {
+    constexpr int ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    spmm_body<LPR, NCHUNK, VEC, true, false, true>(a, (int32_t)blockIdx.x, red_lds);
 }
 
 // Up to LLMREC_SPMM_MAX_PROBLEMS independent problems of ONE kernel instance in one launch (llmrec_spmm_multi_f32): problem q owns the
@@ -581,6 +769,20 @@ __global__ __launch_bounds__(TPB) void spmm_multi_kernel(SpmmMulti m) {
     case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[1], b, red_lds); break;
     case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[2], b, red_lds); break;
     default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, MASKED>(m.p[3], b, red_lds); break;
+    }
+}
+
+// the grouped launch of the slice-masked instance: members without a mask carry smask_col0 = their width and run the plain loops
+template <int LPR, int NCHUNK, int VEC>
+__global__ __launch_bounds__(TPB, 5) void spmm_smask_multi_kernel(SpmmMulti m) {
+    constexpr int ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    const int32_t b = blockIdx.x;
+    switch (spmm_multi_problem(m, b)) {                                   // (block-uniform)
+    case 0: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.p[0], b, red_lds); break;
+    case 1: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.p[1], b, red_lds); break;
+    case 2: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.p[2], b, red_lds); break;
+    default: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.p[3], b, red_lds); break;
     }
 }
 
@@ -613,6 +815,25 @@ __global__ __launch_bounds__(TPB, WEIGHTED ? 5 : 7) void spmm_multi_guest_kernel
     case 1: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[1], b, red_lds); break;
     case 2: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[2], b, red_lds); break;
     default: spmm_body<LPR, NCHUNK, VEC, WEIGHTED, false>(m.m.p[3], b, red_lds); break;
+    }
+}
+
+// the guest launch of the slice-masked instance (the backward's first group hosts the loss values: compiled for that guest only)
+template <class G>
+__global__ __launch_bounds__(TPB, 5) void spmm_smask_multi_guest_kernel(SpmmMultiGuest<G> m) {
+    constexpr int LPR = 16, NCHUNK = 1, VEC = 4, ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    extern __shared__ __attribute__((aligned(16))) char guest_lds[];
+    const int32_t b = blockIdx.x;
+    if (b < m.guest_blocks) {                                             // (block-uniform)
+        guest_block<TPB>(m.g, b, guest_lds);
+        return;
+    }
+    switch (spmm_multi_problem(m.m, b)) {                                 // (block-uniform)
+    case 0: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.m.p[0], b, red_lds); break;
+    case 1: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.m.p[1], b, red_lds); break;
+    case 2: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.m.p[2], b, red_lds); break;
+    default: spmm_body<LPR, NCHUNK, VEC, true, false, true>(m.m.p[3], b, red_lds); break;
     }
 }
 
@@ -692,7 +913,7 @@ __global__ __launch_bounds__(TPB) void spmm_rows_compact_kernel(SpmmArgs a, cons
     compact_pieces(e - s, per, n_pieces);
     if (p >= n_pieces) return;
     Vec<VEC> acc[NCHUNK];
-    if (block_range<LPR, NCHUNK, VEC, false, false>(a, 0, s + p * per, min(s + (p + 1) * per, e), red_lds, acc)) {
+    if (block_range<LPR, NCHUNK, VEC, false, false>(a, 0, s + p * per, min(s + (p + 1) * per, e), red_lds, acc, nullptr, 0)) {
         float* pr = partial + ((int64_t)j * LLMREC_SPMM_COMPACT_PARTS + p) * a.d;
 #pragma unroll
         for (int k = 0; k < NCHUNK; ++k) {
@@ -747,7 +968,8 @@ static int launch_rows_compact(SpmmArgs& a, const int32_t* row_list, const int32
 // The compiled kernel family (LPR, NCHUNK, VEC) and variant (WEIGHTED, MASKED) of a product: two products can share a grouped launch
 // only when both agree. The grouped kernels are compiled for the vector-load families (0..6) and the unmasked variants: the latency-bound
 // products of the step; masked products run in the HBM-bound or row-restricted paths.
-enum { SPMM_V_MASKED_W, SPMM_V_MASKED, SPMM_V_WEIGHTED, SPMM_V_PLAIN };
+// SPMM_V_SMASK_W: the slice-masked weighted product (x_mask_stamp) - family 2 only, single, grouped and as the loss values' host.
+enum { SPMM_V_MASKED_W, SPMM_V_MASKED, SPMM_V_WEIGHTED, SPMM_V_PLAIN, SPMM_V_SMASK_W };
 static const int kSpmmFamilyLpr[] = {4, 8, 16, 32, 64, 64, 64, 16, 64, 64};
 
 struct SpmmPrepared {
@@ -805,7 +1027,14 @@ static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
             LLMREC_CHECK_ARG(e.x_mask_active >= 1 && e.x_mask_active <= 255, "spmm: y_row_needed needs x_mask_active in 1..255");
             a.y_needed = e.y_row_needed; a.x_active = e.x_mask_active;
         }
-        if (e.x_row_mask) {
+        if (e.x_mask_stamp) {
+            // the slice-ranged mask with a device stamp: a kernel instance of its own, nothing of the host-stamped masks beside it
+            LLMREC_CHECK_ARG(e.x_row_mask && e.mask_from_slice >= 0 && e.mask_from_slice <= a.n_slices, "spmm: x_mask_stamp needs x_row_mask and mask_from_slice in 0..%d", a.n_slices);
+            LLMREC_CHECK_ARG(!e.y_row_flag && !e.z_row_flag && !e.y_row_gate && !e.y_row_needed && !e.rows_listed_only && e.op == LLMREC_SPMM_EPI_NONE,
+                             "spmm: x_mask_stamp excludes the row flags, gates, row lists and the softmax epilogues");
+            a.smask = e.x_row_mask; a.smask_stamp = e.x_mask_stamp; a.smask_col0 = e.mask_from_slice * a.d;
+            a.smask_inplace = e.Z == Y && e.ldz == ldy && e.alpha == 1.0f && !e.post_scale;
+        } else if (e.x_row_mask) {
             LLMREC_CHECK_ARG(e.x_mask_active >= 1 && e.x_mask_active <= 255, "spmm: x_mask_active must be a byte value 1..255");
             a.x_mask = e.x_row_mask; a.x_active = e.x_mask_active; a.y_flag = e.y_row_flag; a.z_flag = e.z_row_flag;
             LLMREC_CHECK_ARG(!e.y_row_gate || e.op != LLMREC_SPMM_EPI_SOFTMAX, "spmm: y_row_gate with the forward softmax (a zero row is not a zero output)");
@@ -829,6 +1058,16 @@ static int spmm_prepare(const llmrec_spmm_problem_t& pr, SpmmPrepared& out) {
     out.family = f;
     out.variant = a.x_mask ? (weighted ? SPMM_V_MASKED_W : SPMM_V_MASKED)
                 : weighted ? SPMM_V_WEIGHTED : SPMM_V_PLAIN;
+    if (a.smask) {
+        const int64_t tasks = (p.slot_row ? (int64_t)p.n_short_rows : n_rows) * a.n_slices;
+        const char* why = f != 2 ? "its slices are not float4 rows of 33..64 columns" : a.val ? "the operand has val" :
+                          !a.col_scale ? "the operand has no col_scale" : tasks + (TPB / 16) * 8192 >= (1ll << 31) ? "too many (row, slice) tasks" : nullptr;
+        if (why) {
+            set_error("spmm: the slice-masked product is compiled for the pattern-only float4 products of 33..64 columns per slice weighted by col_scale: %s (family %d)", why, f);
+            return LLMREC_EUNSUPPORTED;
+        }
+        out.variant = SPMM_V_SMASK_W;
+    }
     out.bytes_x = X ? extent_bytes(n_cols, ldx, d) : 0;
     out.bytes_y = extent_bytes(n_rows, ldy, d);
     out.bytes_z = a.Z ? extent_bytes(n_rows, a.ldz, d) : 0;
@@ -883,7 +1122,9 @@ static void launch_spmm_guest(int n, const SpmmPrepared* pp, int variant, int64_
     }
     m.guest_blocks = (int32_t)gl.blocks;
     m.g = g;
-    if (variant == SPMM_V_WEIGHTED) spmm_multi_guest_kernel<true, G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);
+    if (variant == SPMM_V_SMASK_W) {
+        if constexpr (std::is_same<G, LossesArgs>::value) spmm_smask_multi_guest_kernel<G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);   // (spmm_run: this guest only)
+    } else if (variant == SPMM_V_WEIGHTED) spmm_multi_guest_kernel<true, G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);
     else spmm_multi_guest_kernel<false, G><<<(unsigned)total, TPB, gl.shmem, stream>>>(m);
 }
 
@@ -894,6 +1135,18 @@ static int launch_spmm(int n, SpmmPrepared* pp, int variant, int64_t total, hipS
             if (guest->kind == LLMREC_SPMM_GUEST_SAMPLER) launch_spmm_guest(n, pp, variant, total, guest->sampler, *guest, stream);
             else if (guest->kind == LLMREC_SPMM_GUEST_PLAN_REACH) launch_spmm_guest(n, pp, variant, total, guest->plan_reach, *guest, stream);
             else launch_spmm_guest(n, pp, variant, total, guest->losses, *guest, stream);
+        } else if (variant == SPMM_V_SMASK_W) {              // (spmm_prepare: family 2 only)
+            if constexpr (LPR == 16 && NCHUNK == 1 && VEC == 4) {
+                if (n == 1) spmm_smask_kernel<LPR, NCHUNK, VEC><<<(unsigned)total, TPB, 0, stream>>>(pp[0].a);
+                else {
+                    SpmmMulti m = {};
+                    for (int q = 0; q < LLMREC_SPMM_MAX_PROBLEMS; ++q) {
+                        if (q < n) { m.p[q] = pp[q].a; m.begin[q] = pp[q].a.blk_begin; }
+                        else m.begin[q] = 0x7fffffff;
+                    }
+                    spmm_smask_multi_kernel<LPR, NCHUNK, VEC><<<(unsigned)total, TPB, 0, stream>>>(m);
+                }
+            }
         } else if (n == 1) {
             const SpmmArgs& a = pp[0].a;
             switch (variant) {
@@ -953,6 +1206,17 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
         if (rc != LLMREC_OK) return rc;
         if (!pp[m].empty) ++m;
     }
+    // a slice-masked product takes along the members of its group that its instance can run - the same family, weighted by col_scale
+    // alone (rows_body_pipe_smask reads no val) and without y_row_needed (it computes every row): they run with a mask that begins
+    // behind their last slice (a no-op). Any other company keeps its variant and is refused below like any mixed group
+    bool smask = false;
+    for (int q = 0; q < m; ++q) smask = smask || pp[q].variant == SPMM_V_SMASK_W;
+    for (int q = 0; q < m && smask; ++q) {
+        const SpmmArgs& aq = pp[q].a;
+        if (pp[q].variant != SPMM_V_WEIGHTED || pp[q].family != 2 || aq.val || !aq.col_scale || aq.y_needed) continue;
+        pp[q].variant = SPMM_V_SMASK_W;
+        pp[q].a.smask_col0 = pp[q].a.n_slices * pp[q].a.d;
+    }
     GuestLaunch gl = {};
     if (guest) {                                                         // every check of the guest too, before anything is launched
         int rc;
@@ -971,7 +1235,11 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
             set_error("spmm_multi_guest: a plan of B_max %d > %d would cost the launch its occupancy", guest->u.plan_reach.B_max, LLMREC_SPMM_GUEST_MAX_PLAN_B);
             return LLMREC_EUNSUPPORTED;
         }
-        if (!(pp[0].family == 2 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED))) {
+        if (smask && guest->kind != LLMREC_SPMM_GUEST_LOSSES) {
+            set_error("spmm_multi_guest: the slice-masked product hosts the loss values only (guest kind %d)", guest->kind);
+            return LLMREC_EUNSUPPORTED;
+        }
+        if (!(pp[0].family == 2 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED || pp[0].variant == SPMM_V_SMASK_W))) {
             set_error("spmm_multi_guest: compiled for the unmasked float4 products of 33..64 columns only (family %d, variant %d)", pp[0].family, pp[0].variant);
             return LLMREC_EUNSUPPORTED;
         }
@@ -984,7 +1252,7 @@ static int spmm_run(int32_t n, const llmrec_spmm_problem_t* problems, hipStream_
             return LLMREC_EUNSUPPORTED;
         }
     }
-    if (m > 1 && !(pp[0].family <= 6 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED))) {
+    if (m > 1 && !(pp[0].family <= 6 && (pp[0].variant == SPMM_V_PLAIN || pp[0].variant == SPMM_V_WEIGHTED || pp[0].variant == SPMM_V_SMASK_W))) {
         set_error("spmm_multi: grouped launches are compiled for the unmasked products with vector loads only");
         return LLMREC_EUNSUPPORTED;
     }

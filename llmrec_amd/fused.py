@@ -138,8 +138,9 @@ class FusedStep:
         self.sc_U, self.sc_I, self.sc_prof = z(U, 2 * d), z(I, S * d), z(U, d)
         # one byte per row, stamped by the loss launch for the rows of the batch with the step's stamp (a device counter: nothing is ever
         # cleared, no reader races a clean-up): the fusion backward writes the ~90 % of rows no sample touched (zero gradient, zero
-        # sources) without reading them. (The same stamps offered to the transposed side product as "rows whose attribute streams are
-        # all-zero" bought nothing: at 4 edges per row that SpMM is bound by its per-row latency chain, not by the gathers.)
+        # sources) without reading them. (The same stamps offered to the transposed side product as a mask over ALL its slices, with the
+        # mask bytes loaded at gather time, bought nothing in round 3; restricted to the attribute slices, read on the device and with
+        # the in-place skip they do: bwd_mask below.)
         self.flag_u = torch.zeros(U, dtype=torch.uint8, device=dev)
         self.flag_i = torch.zeros(I, dtype=torch.uint8, device=dev)
         self.row_stamp = torch.zeros(1, dtype=torch.int32, device=dev)     # advanced by the scores launch (LLMREC_ROW_STAMP)
@@ -243,6 +244,19 @@ class FusedStep:
             self.ss_cap = 2 * 2048                                # >= the fusion launch's grid (two problems, <= 2048 blocks each)
             self.ss_partial = torch.zeros(self.ss_cap, dtype=torch.float32, device=dev)
             self.ss_n = 0
+        # MASKED side product of the backward (LLMREC_BWD_MASK=0: the dense calls; =spmm: the product's mask without the fusion backward's
+        # skip). dI_cat's attribute slices (2 ..) are exactly zero outside the rows of the batch's items - the argument of the row-listed
+        # weight gradient above, one product earlier - and the loss launch stamps those rows in flag_i. dU_cat += A_iu^T dI_cat then
+        # gathers, in the slices from 2 on, the stamped rows only and leaves user rows without a stamped neighbour untouched
+        # (llmrec_spmm_epilogue_t.x_mask_stamp: the stamp is read on the device, so a replayed graph follows it); the fusion backward in
+        # turn no longer writes the zeros nobody reads (llmrec_fuse_bwd_problem_t.zero_skip_from_term). Same bits as the dense calls.
+        # Needs the stamps (the folded loss launch), one 64-column slice per stream and exactly the product the mask is compiled for -
+        # latency-bound, pattern-only, weighted by col_scale (an adjacency that keeps its values runs the dense calls); dU_cat keeps
+        # its dense zeros (the dense weight-gradient fallbacks read every row).
+        want = os.environ.get("LLMREC_BWD_MASK", "1")
+        self.bwd_mask = (want != "0" and self.fold and d == 64 and len(self.keys) > 0 and self.iu.bwd.nnz < ops.SPMM_LATENCY_NNZ
+                         and self.iu.bwd.val is None and self.iu.bwd.col_scale is not None)
+        self.bwd_zero_skip = self.bwd_mask and want != "spmm"
         self._refuse_guests = False                           # tests: treat every guest launch as refused (the separate calls run)
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
@@ -296,9 +310,9 @@ class FusedStep:
         if self.stamps is not None:
             _call("llmrec_timestamp", self.stamps.data_ptr() + 8 * slot)
 
-    def _spmm_args(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None):
+    def _spmm_args(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None, mask=None):
         """(slice width, plan, partials, epilogue) of one product. tag: one partial-sum scratch per concurrent chain - and so per problem
-        of a grouped launch."""
+        of a grouped launch. mask (accumulate only): (row bytes, stamp counter, first masked slice) of ops.spmm_epilogue's slice-ranged mask."""
         d = X.shape[1]
         sw, pl = a.plan_for(d, whole_row=epilogue is not None and epilogue.op != ops.EPI_NONE)
         partials = None
@@ -308,14 +322,16 @@ class FusedStep:
             if partials is None:
                 partials = self._partials[key] = torch.empty(pl.n_seg * d, dtype=torch.float32, device=X.device)
         if accumulate:
-            epilogue = ops.spmm_epilogue(ops.EPI_NONE, 1.0, Y)
+            m = dict(x_row_mask=mask[0], x_mask_stamp=mask[1], mask_from_slice=mask[2]) if mask is not None else {}
+            epilogue = ops.spmm_epilogue(ops.EPI_NONE, 1.0, Y, **m)
         return sw, pl, partials, epilogue
 
-    def _spmm(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None):
-        """Y = epilogue(A X) (llmrec_spmm_f32); accumulate: Y += A X. tag: one partial-sum scratch per concurrent chain."""
+    def _spmm(self, a: ops.Csr, X, Y, accumulate=False, tag=0, epilogue=None, mask=None):
+        """Y = epilogue(A X) (llmrec_spmm_f32); accumulate: Y += A X. tag: one partial-sum scratch per concurrent chain. (A refused mask
+        raises: bwd_mask promised the shape, and the fusion backward has already left the masked rows unwritten.)"""
         d = X.shape[1]
         self.spmm_edge_units += a.nnz * (d / 64.0)
-        sw, pl, partials, epilogue = self._spmm_args(a, X, Y, accumulate, tag, epilogue)
+        sw, pl, partials, epilogue = self._spmm_args(a, X, Y, accumulate, tag, epilogue, mask)
         rp, ci = pl.csr_of(a)
         _call("llmrec_spmm_f32", a.n_rows, a.n_cols, _p(rp), _p(ci), _p(a.val), _p(a.row_scale), _p(a.col_scale),
               _p(X), _ld(X), _p(Y), _ld(Y), d, sw, _c.byref(pl.c_struct()), _p(partials),
@@ -676,7 +692,7 @@ class FusedStep:
         # dE_u / dE_i hold the scattered rows now. (Only the fused loss launch stamps the rows it touched; keep: alive until the launch.)
         fuse, keep = self._fuse_bwd_problems(hp.feat_reg_decay * 0.5 / self.I * replicated_scale, stamped=bpr_bwd_done)
         schedule = self._backward_streams if self.multi_stream else self._backward_one_stream
-        schedule(probs, (users, pos, neg, n_valid), fuse, side_work)
+        schedule(probs, (users, pos, neg, n_valid), fuse, side_work, masked=bpr_bwd_done and self.bwd_mask)
         self._weight_gradients(ev_reach)
         self._join(self.s2)
         if self.fold and side_work is not None:                          # (four streams: side_work ran on a stream of its own)
@@ -705,6 +721,8 @@ class FusedStep:
             if stamped:
                 pr.row_flags, pr.row_stamp = flags.data_ptr(), self.row_stamp.data_ptr()
         arr = (ops.FuseBwdProblem * 2)()
+        if stamped and self.bwd_zero_skip:                               # the attribute terms (behind image, text, profile) of idle item rows:
+            arr[0].zero_skip_from_term = 3                               # their only reader, the masked side product, skips those rows
         problem(arr[0], self.dE_i, self.I_cat, self.prof_i, self.dI_cat, self.dprof_i,
                 [self._side(self.sc_I, 0), self._side(self.sc_I, 1), None] + [self._side(self.sc_I, 2 + k) for k in range(len(self.keys))], self.flag_i)
         problem(arr[1], self.dE_u, self.U_cat, self.prof_u, self.dU_cat, self.dprof_u,
@@ -781,16 +799,36 @@ class FusedStep:
             if self.inline_adamw:                                                 # the item table's gradient is final: update it here,
                 self.opt.step_params(self._emb_params[1:])                        # beside the weight-gradient GEMM
 
-    def _side_bwd_jobs(self):
+    def _side_bwd_jobs(self, masked: bool = False):
         """(side chain, profile chain) of the backward as [(a, X, Y, kwargs)]. Side: I_cat = iu(U_cat), U_cat = ui(P_cat) (or the
-        pre-propagated projection); profile: prof_u = ui(prof_i), prof_i = iu(P_usr) - user_trans' weight gradient joins the item-side ones."""
-        side = [(self.iu.bwd, self.dI_cat, self.dU_cat, dict(accumulate=True))]
+        pre-propagated projection); profile: prof_u = ui(prof_i), prof_i = iu(P_usr) - user_trans' weight gradient joins the item-side ones.
+        masked: the first side product reads the attribute slices of the stamped item rows only (bwd_mask)."""
+        side = [(self.iu.bwd, self.dI_cat, self.dU_cat, dict(accumulate=True, mask=(self.flag_i, self.row_stamp, 2) if masked else None))]
         if not self.preprop:
             side.append((self.ui.bwd, self.dU_cat, self.dP_cat, {}))
         prof = [(self.ui.bwd, self.dprof_u, self.dprof_i, dict(accumulate=True, tag=1)), (self.iu.bwd, self.dprof_i, self.dP_usr, dict(tag=1))]
         return side, prof
 
-    def _backward_one_stream(self, probs, batch, fuse, side_work):
+    def _check_mask_promise(self, masked: bool, done: bool = False):
+        """LLMREC_CHECK_ZERO: the masked side product's promise. Before it: the idle item rows (flag_i != the step's stamp) of dI_cat's
+        attribute slices are all-zero - or, where the fusion backward no longer writes them, are poisoned with NaN so that a read would
+        show; done: behind it, dU_cat is finite."""
+        if not (masked and self.check_zero) or torch.cuda.is_current_stream_capturing():
+            return
+        if done:
+            if self.bwd_zero_skip and not bool(torch.isfinite(self.dU_cat).all()):
+                raise RuntimeError("FusedStep: the masked side product read an idle row of dI_cat's attribute slices")
+            return
+        idle = self.flag_i != (int(self.row_stamp.item()) % 255 + 1)
+        att = self.dI_cat[:, 2 * self.d:]
+        if self.bwd_zero_skip:
+            # (debug only: this WRITES the step's buffer. It is safe exactly as long as the masked side product is the only reader of
+            # these rows - the premise of zero_skip_from_term; whoever adds another reader must drop the skip, and this poison with it.)
+            att[idle] = float("nan")
+        elif idle.any() and float(att[idle].abs().max()) != 0.0:
+            raise RuntimeError("FusedStep: dI_cat's attribute slices are not all-zero outside the stamped item rows")
+
+    def _backward_one_stream(self, probs, batch, fuse, side_work, masked=False):
         """The backward up to the weight gradients on ONE stream: the k-th product of the ID chain, of the side chain and of the profile
         chain share a launch (_spmm_group); folded, the fusion backward shares the chain head's.
         Where side_work carries a guest descriptor (loss_backward's rider), its loss-value launch rides the FIRST group's launch instead of
@@ -801,20 +839,23 @@ class FusedStep:
             _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
         rides = side_work is not None and side_work.guest is not None
         self._chain_head(None if rides else side_work, fuse if self.fold else None)
-        chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs()
+        chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs(masked)
+        self._check_mask_promise(masked)
         for k, jobs in enumerate(zip_longest(chain, side, prof)):
             self._spmm_group(jobs, side_work if k == 0 and rides else None)
+        self._check_mask_promise(masked, done=True)
         if self.gemm != "bf16x3":                                        # (bf16x3: user_trans' gradient is in the multi-target launch)
             self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
         self._chain_tail(probs, batch)
 
-    def _backward_streams(self, probs, batch, fuse, side_work):
+    def _backward_streams(self, probs, batch, fuse, side_work, masked=False):
         """The backward up to the weight gradients on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule):
         fusion backward and side chain on the current stream, profile chain on s1, ID chain on s2."""
         ev_rows = self._mark()                                           # dE_u / dE_i hold the scattered rows: all the ID chain needs
         _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
         ev_fuse = self._mark()                                           # the fusion backward has read dE_u / dE_i
-        side, prof = self._side_bwd_jobs()
+        side, prof = self._side_bwd_jobs(masked)
+        self._check_mask_promise(masked)
         # folded step: the critical transposed side product is captured BEFORE the two side branches (main_first) and the logged-scalar
         # launch gets a stream of its own (loss_s3) - each alone lost, both together won: profiles/experiments/r05_step_chain.md
         main_first, loss_s3 = self.fold, self.fold and side_work is not None
@@ -842,6 +883,7 @@ class FusedStep:
             self._chain_tail(probs, batch, ev_fuse)
         if not main_first:
             self._spmm_jobs(side)
+        self._check_mask_promise(masked, done=True)
 
     def _weight_gradients(self, ev_reach=None):
         """The four Linears' gradients from dU_cat (pre-propagated; else dP_cat) and dP_usr, and - with inline_adamw - their update.

@@ -71,7 +71,8 @@ class SpmmEpilogueC(_c.Structure):
     """llmrec_spmm_epilogue_t"""
     _fields_ = [("op", _c.c_int32), ("alpha", _c.c_float), ("Z", _c.c_void_p), ("ldz", _c.c_int64), ("S", _c.c_void_p), ("lds", _c.c_int64),
                 ("post_scale", _c.c_void_p), ("x_row_mask", _c.c_void_p), ("x_mask_active", _c.c_int32), ("y_row_flag", _c.c_void_p),
-                ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32)]
+                ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32),
+                ("x_mask_stamp", _c.c_void_p), ("mask_from_slice", _c.c_int32)]
 
 
 class SpmmProblemC(_c.Structure):
@@ -402,13 +403,19 @@ class BipartiteGraph:
 def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tensor] = None, S: Optional[torch.Tensor] = None,
                   post_scale: Optional[torch.Tensor] = None, x_row_mask: Optional[torch.Tensor] = None, x_mask_active: int = 0,
                   y_row_flag: Optional[torch.Tensor] = None, z_row_flag: Optional[torch.Tensor] = None,
-                  y_row_gate: Optional[torch.Tensor] = None, y_row_needed: Optional[torch.Tensor] = None, rows_listed_only: bool = False):
+                  y_row_gate: Optional[torch.Tensor] = None, y_row_needed: Optional[torch.Tensor] = None, rows_listed_only: bool = False,
+                  x_mask_stamp: Optional[torch.Tensor] = None, mask_from_slice: int = 0):
     """llmrec_spmm_epilogue_t: Y = post_scale . op(alpha * Z + A X); S = forward softmax rows for EPI_SOFTMAX_BWD.
     x_row_mask (uint8 [n_cols]) / x_mask_active: X rows whose byte differs from the active value are promised all-zero and not read;
     y_row_flag (uint8 [n_rows]): receives the active value for rows whose result can be non-zero (z_row_flag: the non-zero rows of Z);
     y_row_gate (uint8 [n_rows]): rows without the active value are promised zero results and written as zeros unread;
     y_row_needed (uint8 [n_rows]): rows without the active value are neither computed nor written; rows_listed_only: compute the rows
-    in the plan's lists only (spmm_listed)."""
+    in the plan's lists only (spmm_listed).
+    x_mask_stamp (int32 [1], device) / mask_from_slice: the slice-ranged mask - in the 64-column slices from mask_from_slice on, X rows
+    whose x_row_mask byte differs from LLMREC_ROW_STAMP(x_mask_stamp[0]) are promised all-zero and not read; the in-place accumulate
+    then leaves rows without an active neighbour untouched in those slices. The library refuses shapes it is not compiled for."""
+    if x_mask_stamp is not None and (x_mask_stamp.dtype != torch.int32 or x_row_mask is None):
+        raise RuntimeError("spmm_epilogue: x_mask_stamp is an int32 device counter and needs x_row_mask")
     for t in (x_row_mask, y_row_flag, z_row_flag, y_row_gate, y_row_needed):
         if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
             raise RuntimeError("spmm_epilogue: row masks / flags are contiguous uint8 tensors")
@@ -419,7 +426,8 @@ def spmm_epilogue(op: int = EPI_NONE, alpha: float = 0.0, Z: Optional[torch.Tens
                          y_row_flag.data_ptr() if y_row_flag is not None else None,
                          z_row_flag.data_ptr() if z_row_flag is not None else None,
                          y_row_gate.data_ptr() if y_row_gate is not None else None,
-                         y_row_needed.data_ptr() if y_row_needed is not None else None, 1 if rows_listed_only else 0)
+                         y_row_needed.data_ptr() if y_row_needed is not None else None, 1 if rows_listed_only else 0,
+                         x_mask_stamp.data_ptr() if x_mask_stamp is not None else None, int(mask_from_slice))
 
 
 def listed_plan(a: Csr, rows: torch.Tensor, d: int, whole_row: bool = False) -> SpmmPlan:
@@ -796,7 +804,7 @@ class FuseBwdProblem(_c.Structure):
     _fields_ = [("rows", _c.c_int64), ("dOut", _c.c_void_p), ("lddo", _c.c_int64), ("n_norm", _c.c_int32), ("norm_terms", _c.c_void_p),
                 ("norm_ld", _c.c_void_p), ("rates", _c.c_void_p), ("d_terms", _c.c_void_p), ("d_ld", _c.c_void_p),
                 ("src_terms", _c.c_void_p), ("src_ld", _c.c_void_p), ("n_reg_terms", _c.c_int32), ("reg_two_coef", _c.c_float),
-                ("row_flags", _c.c_void_p), ("row_stamp", _c.c_void_p)]
+                ("row_flags", _c.c_void_p), ("row_stamp", _c.c_void_p), ("zero_skip_from_term", _c.c_int32)]
 
 
 class WgradProblem(_c.Structure):
