@@ -357,6 +357,16 @@ int llmrec_linear_wgrad_multi_adamw_bf16x3(int32_t n_targets, const llmrec_wgrad
  * kernel becomes HBM-bound on the X stream. */
 int llmrec_linear_fwd_grouped_bf16x3(int32_t n_problems, const llmrec_linear_problem_t* problems_host, int32_t N,
                                      llmrec_stream_t stream);
+/* llmrec_linear_fwd_grouped_bf16x3 hosting ONE independent SpMM (a problem as llmrec_spmm_multi_f32 takes it) as the TRAILING blocks
+ * of its launch: grid = the projection's work units + the product's blocks. Once the launch has more units than the device has block
+ * slots, its last round leaves slots empty; the product's blocks land there. The product depends on nothing the launch computes
+ * (spmm->X and spmm->Y overlap no projection's Y) and no block waits for another. The projections' Y and the product's Y are
+ * bit-identical to llmrec_linear_fwd_grouped_bf16x3 followed by llmrec_spmm_f32: the product's 256-thread blocks keep every row's
+ * summation tree. Compiled for the projection's <N = 49..64, 128-row units, 32-aligned K> instance and the unweighted, unmasked float4
+ * product of 33..64 columns without slices, split rows or epilogue. Anything else: LLMREC_EUNSUPPORTED before anything is launched,
+ * and the caller issues the two separate calls. */
+int llmrec_linear_fwd_grouped_host_spmm_bf16x3(int32_t n_problems, const llmrec_linear_problem_t* problems_host, int32_t N,
+                                               const llmrec_spmm_problem_t* spmm, llmrec_stream_t stream);
 int64_t llmrec_linear_wgrad_workspace_bytes(int64_t M, int32_t N, int32_t K);
 int llmrec_linear_wgrad_f32(int64_t M, int32_t N, int32_t K, const float* dY, int64_t lddy,
                             const float* X, int64_t ldx, float* dW, int64_t lddw, float* db,

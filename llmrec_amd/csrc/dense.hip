@@ -15,6 +15,7 @@
 //   wgrad   : lane l holds dY[m][4*(l&15) + q] / X[m][k0 + 4*(l&15) + q] with m = m0 + (l>>4) + 4s';
 //             component q selects one of four INTERLEAVED 16-wide tiles (n = 4 i + q, k = k0 + 4 j + q).
 #include "common.h"
+#include "spmm_body.h"
 
 namespace llmrec {
 
@@ -414,8 +415,10 @@ constexpr int GB_WS = 40;              // LDS row stride of one bf16 W tile in 2
 // select); 2: FAST and every K % 32 == 0 and all byte offsets < 2^32 - a k-step is then valid or invalid for the
 // whole wave, so the operand addresses are scalar base + one 32-bit lane offset + a SCALAR k offset (one v_add per
 // load, no clamps or selects on X: past K the staged W tile is zero and X is finite), W is zeroed by one select.
+// The body: one work unit (`unit`: its index in the launch) by one 256-thread block. Shared by the projection's own kernel and by the
+// kernel that hosts a product behind the units (linear_fwd_grouped_bf16x3_host_kernel).
 template <int NT, int RT, int MODE>
-__global__ __launch_bounds__(256, 2) void linear_fwd_grouped_bf16x3_kernel(LinearGroup g, int N) {
+__device__ __forceinline__ void linear_fwd_grouped_bf16x3_unit(const LinearGroup& g, const int N, const int unit) {
     constexpr bool FAST = MODE >= 1;
     constexpr bool K32 = MODE >= 2;
     constexpr bool XPOSE = MODE == 3;
@@ -424,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_grouped_bf16x3_kernel(Linea
     // MODE 3: each wave's 16 RT rows x 128 B of a k-step, as loaded (full 128-B lines), for the fragment-shaped re-read
     __shared__ float4 x_lds[XPOSE ? 4 : 1][XPOSE ? 16 * RT * 8 : 1];
     int prob = 0;
-    while (prob + 1 < g.n_problems && (int)blockIdx.x >= g.unit_begin[prob + 1]) ++prob;
+    while (prob + 1 < g.n_problems && unit >= g.unit_begin[prob + 1]) ++prob;
     const int64_t M = g.M[prob];
     const int K = g.K[prob];
     const bool vec_ok = g.vec_ok[prob];
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_grouped_bf16x3_kernel(Linea
     const int64_t ldx = g.ldx[prob], ldw = g.ldw[prob];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, lq = lane >> 4;
-    const int64_t row0 = (int64_t)(blockIdx.x - g.unit_begin[prob]) * (64 * RT) + wave * (16 * RT);
+    const int64_t row0 = (int64_t)(unit - g.unit_begin[prob]) * (64 * RT) + wave * (16 * RT);
 
     const float* xrow[RT];
     uint32_t xoff[RT];                                                     // K32: byte offset of (row, k = 8 lq) from X
@@ -624,6 +627,26 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_grouped_bf16x3_kernel(Linea
                 if (row < M) Y[row * ldy + c] = fmaf(rs[t][r], b, acc[t][n][r]);
             }
     }
+}
+
+template <int NT, int RT, int MODE>
+__global__ __launch_bounds__(256, 2) void linear_fwd_grouped_bf16x3_kernel(LinearGroup g, int N) {
+    linear_fwd_grouped_bf16x3_unit<NT, RT, MODE>(g, N, (int)blockIdx.x);
+}
+
+// The grouped projection HOSTING one SpMM (llmrec_linear_fwd_grouped_host_spmm_bf16x3): blocks [0, units) run the projection's work
+// units exactly as above, blocks [units, units + a.blk_end) the product's blocks (spmm_body.h, in their 256-thread form). The guests
+// TRAIL: the hardware hands blocks out in id order, so they start when the last round of units has been placed and take the slots
+// that round leaves empty. They depend on nothing the units compute and nothing waits for them. Only the step's instances are compiled
+// (N = 64, 128-row units, 32-aligned K; 16 lanes per row, float4, unweighted). __launch_bounds__(256, 4) caps the architectural VGPRs
+// at 128 (108 + 44 accumulation registers against the projection kernel's 140 + 0): no scratch and the same 3 waves per SIMD; the units
+// measured 1.2 us slower per step than under (256, 2), of the 13 the hosting saves (profiles/experiments/r15_host_chain.md).
+__global__ __launch_bounds__(256, 4) void linear_fwd_grouped_bf16x3_host_kernel(LinearGroup g, int N, int units, SpmmArgs a) {
+    constexpr int LPR = 16, NCHUNK = 1, VEC = 4, ROWW = NCHUNK * LPR * VEC;
+    __shared__ __attribute__((aligned(16))) float red_lds[(TPB / 64 - 1) * ROWW];
+    const int b = (int)blockIdx.x;
+    if (b < units) linear_fwd_grouped_bf16x3_unit<4, 2, 3>(g, N, b);       // (block-uniform)
+    else spmm_hosted_body<LPR, NCHUNK, VEC, false, 256>(a, b - units, red_lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1396,7 +1419,14 @@ int llmrec_linear_fwd_f32(int64_t M, int32_t N, int32_t K, const float* X, int64
     return LLMREC_OK;
 }
 
-static int linear_fwd_grouped_impl(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, bool bf16x3, llmrec_stream_t stream_);
+static int linear_fwd_grouped_impl(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, bool bf16x3, llmrec_stream_t stream_,
+                                   const llmrec_spmm_problem_t* spmm = nullptr);
+
+int llmrec_linear_fwd_grouped_host_spmm_bf16x3(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, const llmrec_spmm_problem_t* spmm,
+                                               llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(spmm, "linear_fwd_grouped_host_spmm: no product (llmrec_linear_fwd_grouped_bf16x3 is the call without one)");
+    return linear_fwd_grouped_impl(n_problems, p, N, true, stream_, spmm);
+}
 
 int llmrec_linear_fwd_grouped_f32(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, llmrec_stream_t stream_) {
     return linear_fwd_grouped_impl(n_problems, p, N, false, stream_);
@@ -1406,7 +1436,8 @@ int llmrec_linear_fwd_grouped_bf16x3(int32_t n_problems, const llmrec_linear_pro
     return linear_fwd_grouped_impl(n_problems, p, N, true, stream_);
 }
 
-static int linear_fwd_grouped_impl(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, bool bf16x3, llmrec_stream_t stream_) {
+static int linear_fwd_grouped_impl(int32_t n_problems, const llmrec_linear_problem_t* p, int32_t N, bool bf16x3, llmrec_stream_t stream_,
+                                   const llmrec_spmm_problem_t* spmm) {
     hipStream_t stream = (hipStream_t)stream_;
     LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= LLMREC_LINEAR_MAX_PROBLEMS && p && N > 0, "linear_fwd_grouped: bad argument");
     if (N > 64) { set_error("linear_fwd_grouped: N = %d > 64", N); return LLMREC_EUNSUPPORTED; }
@@ -1431,12 +1462,39 @@ static int linear_fwd_grouped_impl(int32_t n_problems, const llmrec_linear_probl
         units += (int)ceil_div(p[i].M, rows_per_unit);
     }
     for (int i = n_problems; i <= LLMREC_LINEAR_MAX_PROBLEMS; ++i) g.unit_begin[i] = units;
-    if (units == 0) return LLMREC_OK;
+    if (units == 0 && !spmm) return LLMREC_OK;
     bool fast = true;                                  // every problem: 16-byte aligned rows, K % 4 == 0
     for (int i = 0; i < n_problems; ++i) fast = fast && g.vec_ok[i] && (g.K[i] % 4 == 0) && g.K[i] >= 4;
     bool k32 = fast;                                   // scalar-k addressing of the bf16x3 kernel (MODE 2)
     for (int i = 0; i < n_problems; ++i)
         k32 = k32 && (g.K[i] % 32 == 0) && (p[i].M * p[i].ldx + g.K[i]) < (1ll << 30) && ((int64_t)N * p[i].ldw + g.K[i]) < (1ll << 30);
+    if (spmm) {
+        // the hosting kernel: one instance of the projection (the step's) and the hosted form of the product; every check before the launch
+        if (!(N > 48 && rows_per_unit == 128 && k32)) {
+            set_error("linear_fwd_grouped_host_spmm: compiled for N = 49..64, 128-row units (>= 256 of them) and 32-aligned K (N = %d, %d-row units, k32 = %d)",
+                      N, rows_per_unit, (int)k32);
+            return LLMREC_EUNSUPPORTED;
+        }
+        SpmmHosted h;
+        const int rc = spmm_prepare_hosted(*spmm, 256, h);
+        if (rc != LLMREC_OK) return rc;
+        if ((int64_t)units + h.blocks > 0x7fffffffll) { set_error("linear_fwd_grouped_host_spmm: too many blocks for one launch"); return LLMREC_EUNSUPPORTED; }
+        // the product runs beside the units: what either side writes must not be touched by the other
+        auto overlap = [](const void* a, int64_t na, const void* b, int64_t nb) {
+            return a && b && na > 0 && nb > 0 && (uintptr_t)a < (uintptr_t)b + (uintptr_t)nb && (uintptr_t)b < (uintptr_t)a + (uintptr_t)na;
+        };
+        for (int i = 0; i < n_problems; ++i) {
+            if (p[i].M == 0) continue;
+            const int64_t ny = ((p[i].M - 1) * p[i].ldy + N) * 4, nx = ((p[i].M - 1) * p[i].ldx + p[i].K) * 4, nw = ((int64_t)(N - 1) * p[i].ldw + p[i].K) * 4;
+            LLMREC_CHECK_ARG(!overlap(p[i].Y, ny, h.a.X, h.bytes_x) && !overlap(p[i].Y, ny, h.a.Y, h.bytes_y) && !overlap(h.a.Y, h.bytes_y, p[i].X, nx) &&
+                             !overlap(h.a.Y, h.bytes_y, p[i].W, nw) && !overlap(h.a.Y, h.bytes_y, p[i].bias, (int64_t)N * 4) &&
+                             !overlap(h.a.Y, h.bytes_y, g.bias_scale[i], p[i].M * 4),
+                             "linear_fwd_grouped_host_spmm: the product overlaps projection %d", i);
+        }
+        linear_fwd_grouped_bf16x3_host_kernel<<<(unsigned)(units + h.blocks), 256, 0, stream>>>(g, N, units, h.a);
+        LLMREC_LAUNCH_CHECK();
+        return LLMREC_OK;
+    }
 #define GROUPED_LAUNCH(KERNEL, NT_)                                                         \
     do {                                                                                    \
         if (rows_per_unit == 128) {                                                         \

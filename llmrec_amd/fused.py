@@ -1,4 +1,4 @@
-"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of HIP launches over preallocated buffers (17 at
+"""Fused training step: the whole Stage-2 step - sampler included - as a fixed sequence of HIP launches over preallocated buffers (16 at
 the benchmark's shape on one stream, FusedStep.entry_point_calls_per_step; more on four streams, where nothing is grouped), with the
 backward pass written out by hand (no autograd graph), captured into one HIP graph; likewise an evaluation (forward + scoring + top-K).
 
@@ -13,13 +13,14 @@ main.py:228-278); what changes is the organisation:
   * projections and weight gradients of the constant feature matrices are grouped launches (8 projections in one; all four Linears'
     gradients, row-listed, in one, with their AdamW in the reduction launch) in split-precision bf16x3 arithmetic (LLMREC_GEMM=f32: exact);
   * independent products share grouped SpMM launches on ONE stream - the sampler, the scatter plan with the reach marks and the loss
-    values ride three of them as guests (_Rider) - or run as chains on four HIP streams (LLMREC_STREAMS=1: fork/join = graph edges);
+    values ride three of them as guests (_Rider), and the ID chain's first product rides the projection launch as its trailing blocks
+    (host_chain) - or run as chains on four HIP streams (LLMREC_STREAMS=1: fork/join = graph edges);
   * the embedding tables' AdamW reads its gradient where it is formed (the user table's is inv * dE_u) and the row-wise clean-up of the
     scatter targets rides in the item table's AdamW launch;
   * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
 Falls outside its scope (use the modular path): dropout > 0 and the --mask branch.
-Schedule switches that remain: LLMREC_STREAMS=1 (four streams) and LLMREC_FOLD=0 (the separate small launches) are the A/B references of
-the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
+Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 (the
+chain's first product in an SpMM group of its own launch) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
 FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
 gradients before AdamW).
 """
@@ -258,6 +259,12 @@ class FusedStep:
                          and self.iu.bwd.val is None and self.iu.bwd.col_scale is not None)
         self.bwd_zero_skip = self.bwd_mask and want != "spmm"
         self._refuse_guests = False                           # tests: treat every guest launch as refused (the separate calls run)
+        # HOSTED ID chain (round 15; LLMREC_HOST_CHAIN=0: the chain's first product in the first SpMM group, as before). The chain's first
+        # product A_ui E_i needs nothing from the projection, and the grouped projection's last round of work units leaves block slots
+        # empty once the launch has more units than the device has slots: the product runs as trailing blocks of that launch
+        # (llmrec_linear_fwd_grouped_host_spmm_bf16x3) and the forward needs one SpMM group fewer. Same bits: every row keeps its tree.
+        self.host_chain = os.environ.get("LLMREC_HOST_CHAIN", "1") == "1"
+        self._block_slots = 2 * torch.cuda.get_device_properties(dev).multi_processor_count     # the projection keeps >= 2 blocks per CU
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
         # (Four streams: launch = capture order at the fork points decides which branch the graph runs behind its parent without a cross-queue
@@ -427,13 +434,39 @@ class FusedStep:
             for X, lin, out, _ in jobs:
                 self._linear(X, lin, out)
             return
+        arr = self._projection_problems(jobs)
+        _call("llmrec_linear_fwd_grouped_bf16x3" if self.gemm == "bf16x3" else "llmrec_linear_fwd_grouped_f32", len(jobs), arr, self.d)
+
+    @staticmethod
+    def _projection_problems(jobs):
         arr = (ops.LinearProblem * len(jobs))()
         for i, (X, lin, out, bscale) in enumerate(jobs):
             arr[i].X, arr[i].ldx, arr[i].M, arr[i].K = X.data_ptr(), _ld(X), X.shape[0], X.shape[1]
             arr[i].W, arr[i].ldw, arr[i].bias = lin.weight.data_ptr(), _ld(lin.weight), lin.bias.data_ptr()
             arr[i].Y, arr[i].ldy = out.data_ptr(), _ld(out)
             arr[i].bias_scale = bscale.data_ptr() if bscale is not None else None
-        _call("llmrec_linear_fwd_grouped_bf16x3" if self.gemm == "bf16x3" else "llmrec_linear_fwd_grouped_f32", len(jobs), arr, self.d)
+        return arr
+
+    def _project_all_hosting(self, job) -> bool:
+        """_project_all() with the independent product `job` (a, X, Y, kwargs of _spmm) as TRAILING blocks of the grouped launch
+        (llmrec_linear_fwd_grouped_host_spmm_bf16x3). False: nothing was launched - hosting is off, the launch has no tail to fill
+        (no more work units than block slots: the product would only queue behind the projection), or the library refuses the pair -
+        and the caller issues _project_all() and the product as before. Bit-identical either way."""
+        a, X, Y, kw = job
+        jobs = self.projection_jobs()
+        if not (self.host_chain and not self._refuse_guests and not self.multi_stream and self.gemm == "bf16x3" and self.d == 64
+                and len(jobs) <= _lib.CONST["LLMREC_LINEAR_MAX_PROBLEMS"] and a.nnz < ops.SPMM_LATENCY_NNZ
+                and kw.get("epilogue") is None and not kw.get("accumulate")
+                and sum(-(-j[0].shape[0] // 128) for j in jobs) > self._block_slots):
+            return False
+        probs, keep = self._spmm_problems([job])
+        arr = self._projection_problems(jobs)
+        if not _lib.call_unless_unsupported("llmrec_linear_fwd_grouped_host_spmm_bf16x3", len(jobs), arr, self.d, _c.byref(probs[0]),
+                                            ops._stream()):
+            return False
+        del keep
+        self.spmm_edge_units += a.nnz * (X.shape[1] / 64.0)
+        return True
 
     def _wgrad(self, dY, X, lin, accumulate, ws=None):
         ops.linear_wgrad_grouped([(dY, X)], lin.weight.grad, lin.bias.grad, accumulate, self.ws_wgrad if ws is None else ws,
@@ -534,20 +567,30 @@ class FusedStep:
                     and writes U_1, I_cat, prof_i: disjoint. The batch's last reader of the previous step, the item table's clean-up launch,
                     precedes this launch in stream order; its first reader is the plan, two launches later.
           plan + marks   read the batch and the by-item CSR; write the plan buffer and the reach flags. Their host reads I_1 and writes U_2;
-                    the flags are consumed by the fusion launch's compaction block, two launches later, the plan by the loss backward."""
+                    the flags are consumed by the fusion launch's compaction block, two launches later, the plan by the loss backward.
+        HOSTED (self.host_chain, _project_all_hosting): the chain's first product runs as trailing blocks of the projection launch and the
+        groups are those of chain[1:] - with L = 2 {I_1, I_cat, prof_i}, {U_2, prof_u}, {I_2}: three launches instead of four.
+          hosted product   reads the item ID table, last written by the previous step's item-table AdamW / clean-up launch (earlier in stream
+                    order), and writes U_1; the projection's units read the features and the Linears and write U_cat / P_cat and P_usr: disjoint.
+          sampler   rides the first group as before: that group now reads U_1, U_cat and P_usr and writes I_1, I_cat, prof_i.
+          plan + marks   ride the group that runs alone, now the last one (it reads U_2 and writes I_2); their readers - the fusion launch's
+                    compaction block and the loss backward - still follow it in stream order."""
         if sampler is not None and sampler.guest is None:
             sampler()
         if step is not None and not self.fold:
             self.opt.advance()
         if after_chain is not None and after_chain.guest is None:        # (reads the batch only)
             after_chain()
+        chain = self._chain_fwd_jobs()
         self._stamp(1)
-        self._project_all()
+        if chain and self._project_all_hosting(chain[0]):
+            chain = chain[1:]
+        else:
+            self._project_all()
         self._stamp(2)
         side = [(self.ui.fwd, self.P_cat, self.U_cat, {})] if not self.preprop else []
         side.append((self.iu.fwd, self.U_cat, self.I_cat, {}))
         prof = [(self.iu.fwd, self.P_usr, self.prof_i, dict(tag=1)), (self.ui.fwd, self.prof_i, self.prof_u, dict(tag=1))]
-        chain = self._chain_fwd_jobs()
         groups = list(zip_longest(chain, side, prof))                    # (two at least: the profile chain's)
         # the riders' hosts: the sampler's is the first group, the plan's comes behind it - the chain's third product where there is one
         hosts = {0: sampler, min(2, len(groups) - 1): after_chain}
