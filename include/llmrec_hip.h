@@ -502,6 +502,27 @@ int llmrec_bpr_prune_fwd_sharded_f32(const float* Eu, int64_t ldu, const float* 
                                      int32_t B_local, double remember_rate, float decay, float batch_size_flag,
                                      const float* global_m, int32_t global_B, int32_t my_offset, int32_t scores_only,
                                      float* out2, float* saved, llmrec_stream_t stream);
+/* Both single-problem forms above for batches of ANY size up to LLMREC_BPR_WIDE_MAX_B (B_local and global_B): the selection is an
+ * exact multi-block radix select (four histogram passes over the order-preserving image of m_b, then the ties at the threshold by
+ * global index) instead of rank counting in LDS - same keep set, same `saved` layout and bits, same reduction kernel, so out2 and
+ * saved equal the capped entry points' wherever both exist. Integer atomics only, no host synchronisation, no allocation; the
+ * launch sequence depends on the host arguments alone (hipGraph-capturable).
+ *   global_m == NULL, scores_only = 0   the batch is local (llmrec_bpr_prune_fwd_f32): B from n_valid_dev (may be NULL) or B_local;
+ *                                       scores, selection, reduction. my_offset = 0, global_B = 0 or B_local.
+ *   scores_only = 1                     pass 1 of the sharded form; no workspace needed.
+ *   global_m != NULL, scores_only = 0   pass 2: selection of this rank's B_local samples against the global_B gathered scores at
+ *                                       my_offset; out2[0] is this rank's share. n_valid_dev bounds the LOCAL samples only.
+ * workspace: llmrec_bpr_prune_wide_workspace_bytes(global_B, or B_local for a local batch) bytes, 4-byte aligned; the entry point's
+ * own launches initialise it. Too small: LLMREC_EWORKSPACE; a size above LLMREC_BPR_WIDE_MAX_B: LLMREC_EUNSUPPORTED (the query: -1).
+ * The multi-problem entry points below (FusedStep, DataParallelStep) stay capped at LLMREC_BPR_MAX_B. */
+#define LLMREC_BPR_WIDE_MAX_B (1 << 22)
+int64_t llmrec_bpr_prune_wide_workspace_bytes(int64_t global_B);
+int llmrec_bpr_prune_fwd_wide_f32(const float* Eu, int64_t ldu, const float* Ei, int64_t ldi, int32_t d,
+                                  const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                  int32_t B_local, double remember_rate, float decay, float batch_size_flag,
+                                  const float* global_m, int32_t global_B, int32_t my_offset, int32_t scores_only,
+                                  float* out2, float* saved, const int32_t* n_valid_dev,
+                                  void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
 /* Several (user table, item table) pairs over ONE batch in two launches - the reference computes
  * 8 such losses per step (main.py:232-254). out: [n_problems][2], saved: n_problems blocks of
  * LLMREC_BPR_SAVED_FLOATS(B_max). The backward takes the loss weights from the (host) problem

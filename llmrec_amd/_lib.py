@@ -49,8 +49,9 @@ def parse_header(path: str = HEADER):
 
 def header_constants(path: str = HEADER):
     out = {}
-    for m in re.finditer(r"#define\s+(LLMREC_\w+)\s+(-?\d+)", open(path).read()):
-        out[m.group(1)] = int(m.group(2))
+    # a decimal literal, or a power of two written (1 << n)
+    for m in re.finditer(r"#define\s+(LLMREC_\w+)\s+(?:(-?\d+)|\(1\s*<<\s*(\d+)\))", open(path).read()):
+        out[m.group(1)] = int(m.group(2)) if m.group(2) is not None else 1 << int(m.group(3))
     return out
 
 

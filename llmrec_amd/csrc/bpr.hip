@@ -638,6 +638,186 @@ __global__ __launch_bounds__(SAMPLE_WIDE_THREADS) void sample_batch_wide_kernel(
     guest_block<SAMPLE_WIDE_THREADS>(a, (int)blockIdx.x, nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------
+// WIDE selection (llmrec_bpr_prune_fwd_wide_f32): bpr_rank_kernel's decision for a list of ANY length. That kernel stages the whole
+// global batch in LDS and compares every sample with every other one - O(B Bg) compares in 64 KB, hence LLMREC_BPR_MAX_B. Here the
+// k-th smallest value is found by a most-significant-digit radix select over the order-preserving 32-bit image of m (four 8-bit
+// digits), and the ties at that value are resolved by global index:
+//   bpr_sel_init_kernel    clears the four 256-bin histograms of the workspace;
+//   bpr_sel_hist_kernel    pass p = 0..3, one block per SEL_CHUNK list entries: the prologue picks digit p - 1 from the previous pass's
+//                          histogram (every block does, redundantly; block 0 records it), then the block counts digit p of the entries
+//                          that carry the digits picked so far - in LDS first, then into the workspace with INTEGER atomics (their sum
+//                          does not depend on the order);
+//   bpr_sel_count_kernel   picks the last digit -> the threshold image T and r = k - #{m < T}; writes eq[chunk] = #{m == T} of its chunk;
+//   bpr_sel_write_kernel   chunk c adds eq[0 .. c), scans its own entries in index order and keeps  m < T  and the r equals of lowest
+//                          global index; it writes this rank's samples of the chunk exactly as bpr_rank_kernel does.
+// A kernel boundary is the only cross-block hand-over. Nothing here is a float sum: bpr_reduce_kernel, unchanged, produces the values.
+// workspace (uint32 words): hist[4][256] | state[p] = (digits picked before pass p, what is left of k in their bucket), p = 1..4 | eq[chunks]
+// ---------------------------------------------------------------------------------------------
+constexpr int SEL_THREADS = 256;
+constexpr int SEL_ITEMS = 8;
+constexpr int SEL_CHUNK = SEL_THREADS * SEL_ITEMS;                     // list entries per block
+constexpr int SEL_PASSES = 4;                                          // 8-bit digits of the 32-bit image
+constexpr int SEL_WS_STATE = SEL_PASSES * 256;                         // word offset of state[0] (state[0] itself is never stored: (0, k))
+constexpr int SEL_WS_EQ = SEL_WS_STATE + 16;                           // word offset of eq[]
+
+struct SelArgs {
+    const float* list;                 // the gathered log-sigmoids; null: the batch is local (the list is saved's m slots)
+    int slots;                         // capacity of the list: global_B, or B_max for a local batch
+    int B_max;
+    const int32_t* n_valid_dev;
+    double remember_rate;
+    float* saved;
+    int my_offset;                     // global index of this rank's sample 0
+    uint32_t* ws;
+};
+
+struct SelProblem { const float* list; int Bg, k; bool active; };      // active: 0 < k < Bg, a threshold has to be found
+__device__ __forceinline__ SelProblem sel_problem(const SelArgs& a) {
+    SelProblem s;
+    s.list = a.list ? a.list : a.saved + a.B_max + 4;
+    s.Bg = a.list ? a.slots : bpr_batch(a.n_valid_dev, a.B_max);
+    s.k = (int)(a.remember_rate * (double)s.Bg);                       // bpr_rank_kernel's k
+    s.active = s.k > 0 && s.k < s.Bg;
+    return s;
+}
+
+// ascending image <=> ascending float; -0.0f and +0.0f share one image, as they compare equal
+__device__ __forceinline__ uint32_t sel_key(float m) {
+    const uint32_t u = m == 0.f ? 0u : __float_as_uint(m);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// inclusive scan over the block's SEL_THREADS values (scan: SEL_THREADS words of LDS, free again on return)
+__device__ __forceinline__ uint32_t sel_block_scan(uint32_t v, uint32_t* scan) {
+    scan[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < SEL_THREADS; off <<= 1) {
+        const uint32_t w = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0u;
+        __syncthreads();
+        scan[threadIdx.x] += w;
+        __syncthreads();
+    }
+    const uint32_t r = scan[threadIdx.x];
+    __syncthreads();
+    return r;
+}
+
+// state[p]: digit p - 1 is the bin of hist[p - 1] in which the state[p - 1].y-th smallest entry of the current bucket lies
+__device__ __forceinline__ uint2 sel_state(const uint32_t* ws, int p, int k, uint32_t* scan, uint32_t* pick) {
+    if (p == 0) return make_uint2(0u, (uint32_t)k);
+    const uint32_t prefix = p == 1 ? 0u : ws[SEL_WS_STATE + 2 * (p - 1)];
+    const uint32_t rem = p == 1 ? (uint32_t)k : ws[SEL_WS_STATE + 2 * (p - 1) + 1];
+    const uint32_t h = ws[(p - 1) * 256 + threadIdx.x];
+    const uint32_t incl = sel_block_scan(h, scan);
+    if (threadIdx.x == 0) { pick[0] = prefix; pick[1] = 0u; }
+    __syncthreads();
+    if (incl - h < rem && rem <= incl) {                               // exactly one bin: 1 <= rem <= the bucket's size
+        pick[0] = prefix | ((uint32_t)threadIdx.x << (32 - 8 * p));
+        pick[1] = rem - (incl - h);
+    }
+    __syncthreads();
+    return make_uint2(pick[0], pick[1]);
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_init_kernel(uint32_t* __restrict__ ws) {
+    for (int i = threadIdx.x; i < SEL_WS_STATE; i += SEL_THREADS) ws[i] = 0u;
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_hist_kernel(SelArgs a, int p) {
+    __shared__ uint32_t scan[SEL_THREADS];
+    __shared__ uint32_t h[256];
+    __shared__ uint32_t pick[2];
+    const SelProblem s = sel_problem(a);
+    const int base = (int)blockIdx.x * SEL_CHUNK;
+    if (!s.active || base >= s.Bg) return;                             // block-uniform (block 0 always stays: Bg > k > 0)
+    const uint2 st = sel_state(a.ws, p, s.k, scan, pick);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p > 0) { a.ws[SEL_WS_STATE + 2 * p] = st.x; a.ws[SEL_WS_STATE + 2 * p + 1] = st.y; }
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const int shift = 24 - 8 * p;
+    const uint32_t himask = p == 0 ? 0u : 0xffffffffu << (shift + 8);
+#pragma unroll
+    for (int i = 0; i < SEL_ITEMS; ++i) {
+        const int j = base + i * SEL_THREADS + (int)threadIdx.x;
+        if (j < s.Bg) {
+            const uint32_t key = sel_key(s.list[j]);
+            if ((key & himask) == st.x) atomicAdd(&h[(key >> shift) & 255u], 1u);
+        }
+    }
+    __syncthreads();
+    const uint32_t c = h[threadIdx.x];
+    if (c) atomicAdd(&a.ws[p * 256 + threadIdx.x], c);
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_count_kernel(SelArgs a) {
+    __shared__ uint32_t scan[SEL_THREADS];
+    __shared__ uint32_t pick[2];
+    __shared__ uint32_t cnt;
+    const SelProblem s = sel_problem(a);
+    const int base = (int)blockIdx.x * SEL_CHUNK;
+    if (!s.active) return;
+    if (base >= s.Bg) { if (threadIdx.x == 0) a.ws[SEL_WS_EQ + blockIdx.x] = 0u; return; }
+    const uint2 st = sel_state(a.ws, SEL_PASSES, s.k, scan, pick);     // (T, r)
+    if (threadIdx.x == 0) {
+        cnt = 0u;
+        if (blockIdx.x == 0) { a.ws[SEL_WS_STATE + 2 * SEL_PASSES] = st.x; a.ws[SEL_WS_STATE + 2 * SEL_PASSES + 1] = st.y; }
+    }
+    __syncthreads();
+    uint32_t c = 0u;
+#pragma unroll
+    for (int i = 0; i < SEL_ITEMS; ++i) {
+        const int j = base + i * SEL_THREADS + (int)threadIdx.x;
+        if (j < s.Bg) c += sel_key(s.list[j]) == st.x;
+    }
+    if (c) atomicAdd(&cnt, c);
+    __syncthreads();
+    if (threadIdx.x == 0) a.ws[SEL_WS_EQ + blockIdx.x] = cnt;
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_write_kernel(SelArgs a) {
+    __shared__ uint32_t scan[SEL_THREADS];
+    __shared__ uint32_t before_s;
+    const SelProblem s = sel_problem(a);
+    const int B = bpr_batch(a.n_valid_dev, a.B_max);
+    const int base = (int)blockIdx.x * SEL_CHUNK;
+    if (base + SEL_CHUNK <= a.my_offset || base >= a.my_offset + a.B_max) return;   // none of this rank's samples in the chunk (block-uniform)
+    float* sc = a.saved + a.B_max + 4;
+    const int j0 = base + (int)threadIdx.x * SEL_ITEMS;                // SEL_ITEMS consecutive entries per thread: index order
+    uint32_t T = 0u, r = 0u, eq_before = 0u, keys[SEL_ITEMS];
+    if (s.active) {
+        T = a.ws[SEL_WS_STATE + 2 * SEL_PASSES]; r = a.ws[SEL_WS_STATE + 2 * SEL_PASSES + 1];
+        if (threadIdx.x == 0) before_s = 0u;
+        __syncthreads();
+        uint32_t part = 0u;
+        for (int c = threadIdx.x; c < (int)blockIdx.x; c += SEL_THREADS) part += a.ws[SEL_WS_EQ + c];
+        if (part) atomicAdd(&before_s, part);
+        uint32_t mine = 0u;
+#pragma unroll
+        for (int i = 0; i < SEL_ITEMS; ++i) {
+            keys[i] = j0 + i < s.Bg ? sel_key(s.list[j0 + i]) : 0u;
+            mine += j0 + i < s.Bg && keys[i] == T;
+        }
+        const uint32_t incl = sel_block_scan(mine, scan);              // (its barriers also publish before_s)
+        eq_before = before_s + incl - mine;
+    }
+#pragma unroll
+    for (int i = 0; i < SEL_ITEMS; ++i) {
+        const int j = j0 + i, b = j - a.my_offset;
+        bool keep = s.k >= s.Bg;
+        if (s.active && j < s.Bg) {                                    // EVERY entry of the list advances the count of equals, whichever rank's
+            const bool eq = keys[i] == T;                              // sample it is: a rank's samples need not begin at a thread's first entry
+            keep = keys[i] < T || (eq && eq_before < r);
+            eq_before += eq;
+        }
+        if (b < 0 || b >= a.B_max) continue;
+        if (b >= B) { a.saved[b] = 0.f; sc[a.B_max + b] = 0.f; continue; }
+        const float mb = sc[b];
+        a.saved[b] = keep ? (-1.0f / (float)s.k) * sc[a.B_max + b] : 0.f;
+        sc[a.B_max + b] = keep ? mb : 0.f;
+    }
+}
+
 }  // namespace llmrec
 
 using namespace llmrec;
@@ -703,6 +883,72 @@ int llmrec_bpr_prune_fwd_sharded_f32(const float* Eu, int64_t ldu, const float* 
     if (!scores_only) { ga.g = global_m; ga.n_ranks = 1; ga.stride = 0; ga.cap = global_B; ga.n_prob = 1; ga.my_offset = my_offset; ga.has_tail = 0; }
     return launch_bpr_fwd(t, 1, d, users, pos, neg, B_local, nullptr, remember_rate, decay, batch_size_flag, out2, saved,
                           ga, scores_only != 0, scores_only == 0, nullptr, (hipStream_t)stream_);
+}
+
+int64_t llmrec_bpr_prune_wide_workspace_bytes(int64_t global_B) {
+    if (global_B < 0 || global_B > LLMREC_BPR_WIDE_MAX_B) return -1;
+    return align_up(4 * (SEL_WS_EQ + ceil_div(global_B > 0 ? global_B : 1, SEL_CHUNK)), 256);
+}
+
+int llmrec_bpr_prune_fwd_wide_f32(const float* Eu, int64_t ldu, const float* Ei, int64_t ldi, int32_t d,
+                                  const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                  int32_t B_local, double remember_rate, float decay, float batch_size_flag,
+                                  const float* global_m, int32_t global_B, int32_t my_offset, int32_t scores_only,
+                                  float* out2, float* saved, const int32_t* n_valid_dev,
+                                  void* workspace, int64_t workspace_bytes, llmrec_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LLMREC_CHECK_ARG(B_local >= 0 && d > 0 && out2 && saved, "bpr_fwd_wide: bad argument");
+    if (B_local > LLMREC_BPR_WIDE_MAX_B || global_B > LLMREC_BPR_WIDE_MAX_B) {
+        set_error("bpr_fwd_wide: batch of %d (global %d) > %d", B_local, global_B, LLMREC_BPR_WIDE_MAX_B);
+        return LLMREC_EUNSUPPORTED;
+    }
+    LLMREC_CHECK_ARG(B_local == 0 || (Eu && Ei && users && pos && neg && ldu >= d && ldi >= d), "bpr_fwd_wide: null pointer or ld < d");
+    const bool local = !global_m;
+    if (!scores_only) {
+        if (local) LLMREC_CHECK_ARG(my_offset == 0 && (global_B == 0 || global_B == B_local),
+                                    "bpr_fwd_wide: a local batch (no gathered scores) has offset 0 and no other global size");
+        else LLMREC_CHECK_ARG(global_B >= B_local && my_offset >= 0 && my_offset + (int64_t)B_local <= global_B,
+                              "bpr_fwd_wide: pass 2 needs a valid offset into the gathered scores");
+    }
+    BprTables t = {};
+    t.Eu[0] = Eu; t.Ei[0] = Ei; t.ldu[0] = ldu; t.ldi[0] = ldi;
+    if (scores_only)                                                   // pass 1 of the sharded form: the per-sample scratch only
+        return launch_bpr_fwd(t, 1, d, users, pos, neg, B_local, n_valid_dev, remember_rate, decay, batch_size_flag, out2, saved,
+                              BprGather{}, true, false, nullptr, stream);
+    const int slots = local ? B_local : global_B;
+    const int64_t need = llmrec_bpr_prune_wide_workspace_bytes(slots);
+    if (!workspace || workspace_bytes < need) {
+        set_error("bpr_fwd_wide: workspace %lld < %lld", (long long)workspace_bytes, (long long)need);
+        return LLMREC_EWORKSPACE;
+    }
+    if (local) {
+        const int rc = launch_bpr_fwd(t, 1, d, users, pos, neg, B_local, n_valid_dev, remember_rate, decay, batch_size_flag, out2, saved,
+                                      BprGather{}, true, false, nullptr, stream);
+        if (rc != LLMREC_OK) return rc;
+    }
+    BprGather ga = {};
+    if (!local) { ga.g = global_m; ga.n_ranks = 1; ga.stride = 0; ga.cap = global_B; ga.n_prob = 1; ga.my_offset = my_offset; ga.has_tail = 0; }
+    const SelArgs a = {global_m, slots, B_local, n_valid_dev, remember_rate, saved, my_offset, (uint32_t*)workspace};
+    const unsigned chunks = (unsigned)ceil_div(slots > 0 ? slots : 1, SEL_CHUNK);
+    // a list length the host knows (no device batch count) settles k here: k <= 0 or k >= Bg needs no threshold
+    const bool host_len = !local || !n_valid_dev;
+    const int k_host = (int)(remember_rate * (double)slots);
+    if (!(host_len && (k_host <= 0 || k_host >= slots))) {
+        bpr_sel_init_kernel<<<1, SEL_THREADS, 0, stream>>>(a.ws);
+        LLMREC_LAUNCH_CHECK();
+        for (int p = 0; p < SEL_PASSES; ++p) {
+            bpr_sel_hist_kernel<<<chunks, SEL_THREADS, 0, stream>>>(a, p);
+            LLMREC_LAUNCH_CHECK();
+        }
+        bpr_sel_count_kernel<<<chunks, SEL_THREADS, 0, stream>>>(a);
+        LLMREC_LAUNCH_CHECK();
+    }
+    bpr_sel_write_kernel<<<chunks, SEL_THREADS, 0, stream>>>(a);
+    LLMREC_LAUNCH_CHECK();
+    bpr_reduce_kernel<<<1, BPR_THREADS, 0, stream>>>(B_local, n_valid_dev, remember_rate, decay, batch_size_flag, out2, saved,
+                                                    LLMREC_BPR_SAVED_FLOATS(B_local), ga);
+    LLMREC_LAUNCH_CHECK();
+    return LLMREC_OK;
 }
 
 static int fill_tables(BprTables& t, int n, const llmrec_bpr_problem_t* p, int d, bool need_grads) {

@@ -276,15 +276,31 @@ class HipBackend:
         saved = self._saved if (not scores_only and self._saved is not None and self._saved.numel() == o.bpr_saved_floats(B)) \
             else torch.empty(o.bpr_saved_floats(B), dtype=torch.float32, device=Eu.device)
         self._saved = saved if scores_only else None        # pass 2 reuses pass 1's per-sample scratch
-        o._lib.call("llmrec_bpr_prune_fwd_sharded_f32", o._p(Eu), o._ld(Eu), o._p(Ei), o._ld(Ei), Eu.shape[1], o._p(u), o._p(p), o._p(n),
-                    B, float(remember), float(decay), float(bsz), o._p(global_m), int(global_B), int(offset), 1 if scores_only else 0,
-                    o._p(out), o._p(saved), o._stream())
+        args = (o._p(Eu), o._ld(Eu), o._p(Ei), o._ld(Ei), Eu.shape[1], o._p(u), o._p(p), o._p(n),
+                B, float(remember), float(decay), float(bsz), o._p(global_m), int(global_B), int(offset), 1 if scores_only else 0,
+                o._p(out), o._p(saved))
+        cap = o.CONST["LLMREC_BPR_MAX_B"]
+        if B > cap or global_B > 3 * cap:                   # beyond the rank-counting kernel's LDS: the multi-block selection (by size only)
+            ws = None
+            if not scores_only:
+                ws = getattr(self, "_bpr_wide_ws", None)
+                if ws is None or ws.numel() < o._lib.query("llmrec_bpr_prune_wide_workspace_bytes", int(global_B)):
+                    ws = self._bpr_wide_ws = o.bpr_wide_workspace(int(global_B), Eu.device)
+            o._lib.call("llmrec_bpr_prune_fwd_wide_f32", *args, None, o._p(ws), ws.numel() if ws is not None else 0, o._stream())
+        else:
+            o._lib.call("llmrec_bpr_prune_fwd_sharded_f32", *args, o._stream())
         return out, saved
 
     def bpr_bwd(self, Eu, Ei, u, p, n, decay, bsz, saved, grads2):
         o = self.ops
         Eu, Ei = o._rowmajor(Eu), o._rowmajor(Ei)
         dEu, dEi = torch.zeros_like(Eu), torch.zeros_like(Ei)
+        if u.numel() > o.CONST["LLMREC_BPR_MAX_B"]:         # no scatter plan at this size: compact rows, then the sorted scatter (same order:
+            rows3 = torch.empty(3, u.numel(), Eu.shape[1], dtype=torch.float32, device=Eu.device)   # ascending slot, positives first)
+            self.bpr_bwd_rows(Eu, Ei, u, p, n, decay, bsz, saved, grads2.contiguous(), rows3)
+            self.scatter_rows(u, rows3[0], dEu, 1.0)
+            self.scatter_rows(torch.cat([p, n]), rows3[1:].view(-1, Eu.shape[1]), dEi, 1.0)
+            return dEu, dEi
         plan = o.bpr_scatter_plan(u, p, n)
         o._lib.call("llmrec_bpr_prune_bwd_f32", o._p(Eu), o._ld(Eu), o._p(Ei), o._ld(Ei), Eu.shape[1], o._p(u), o._p(p), o._p(n),
                     u.numel(), None, float(decay), float(bsz), o._p(saved), o._p(grads2.contiguous()), o._p(dEu), o._ld(dEu),

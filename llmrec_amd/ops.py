@@ -964,15 +964,73 @@ class _BprPrune(torch.autograd.Function):
         return dEu, dEi, None, None, None, None, None, None, None
 
 
+def bpr_wide_workspace(global_B: int, device) -> torch.Tensor:
+    """A workspace of llmrec_bpr_prune_wide_workspace_bytes(global_B) bytes for llmrec_bpr_prune_fwd_wide_f32 (uninitialised: the
+    entry point's own launches initialise it)."""
+    need = _lib.query("llmrec_bpr_prune_wide_workspace_bytes", int(global_B))
+    if need < 0:
+        raise RuntimeError("bpr_wide_workspace: batch of %d exceeds LLMREC_BPR_WIDE_MAX_B" % global_B)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+_scatter_ws = {}                                                   # device -> the sorted scatter's workspace (grown, never shrunk)
+
+
+def _scatter_rows(ids, rows, dst):
+    """dst[ids[j]] += rows[j], rows of one id in ascending j (llmrec_scatter_rows_f32: deterministic). Calls on one device share one
+    workspace: they are ordered by the stream they are issued on."""
+    n = ids.numel()
+    need = _lib.query("llmrec_scatter_rows_workspace_bytes", n)
+    ws = _scatter_ws.get(dst.device)
+    if ws is None or ws.numel() < need:
+        ws = _scatter_ws[dst.device] = torch.empty(need, dtype=torch.uint8, device=dst.device)
+    _lib.call("llmrec_scatter_rows_f32", n, _p(ids), _p(rows), _ld(rows), rows.shape[1], 1.0, _p(dst), _ld(dst), _p(ws), ws.numel(), _stream())
+
+
+class _BprPruneWide(torch.autograd.Function):
+    """_BprPrune beyond LLMREC_BPR_MAX_B: the multi-block selection forward; the backward writes compact rows and scatters them sorted -
+    the scatter plan's order (ascending slot, positives before negatives) without its LDS-sized rank-counting sort."""
+    @staticmethod
+    def forward(ctx, Eu, Ei, users, pos, neg, remember_rate, decay, batch_size_flag, n_valid):
+        _need_gpu(Eu, Ei, users, pos, neg)
+        Eu, Ei = _rowmajor(Eu), _rowmajor(Ei)
+        B = users.numel()
+        out = torch.empty(2, dtype=torch.float32, device=Eu.device)
+        saved = torch.empty(bpr_saved_floats(B), dtype=torch.float32, device=Eu.device)
+        ws = bpr_wide_workspace(B, Eu.device)
+        _lib.call("llmrec_bpr_prune_fwd_wide_f32", _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), Eu.shape[1], _p(users), _p(pos), _p(neg), B,
+                  float(remember_rate), float(decay), float(batch_size_flag), None, 0, 0, 0, _p(out), _p(saved), _p(n_valid),
+                  _p(ws), ws.numel(), _stream())
+        ctx.save_for_backward(Eu, Ei, users, pos, neg, saved)
+        ctx.n_valid, ctx.decay, ctx.bsz = n_valid, float(decay), float(batch_size_flag)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Eu, Ei, users, pos, neg, saved = ctx.saved_tensors
+        g = g.contiguous()
+        B, d = users.numel(), Eu.shape[1]
+        dEu, dEi = torch.zeros_like(Eu), torch.zeros_like(Ei)
+        rows3 = torch.empty(3, B, d, dtype=torch.float32, device=Eu.device)
+        _lib.call("llmrec_bpr_prune_bwd_rows_f32", _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), d, _p(users), _p(pos), _p(neg), B, _p(ctx.n_valid),
+                  ctx.decay, ctx.bsz, _p(saved), _p(g), _p(rows3), _stream())
+        # rows of samples b >= n_valid are zeros: their (padded, in-range) ids add nothing, no mask and no host read
+        _scatter_rows(users, rows3[0], dEu)
+        _scatter_rows(torch.cat([pos, neg]), rows3[1:].view(-1, d), dEi)
+        return dEu, dEi, None, None, None, None, None, None, None
+
+
 def bpr_prune(Eu, Ei, users, pos, neg, drop_rate: float, decay: float, batch_size_flag: float, n_valid=None):
     """Returns a 2-vector [mf_loss, emb_loss] (reference main.py:330-342 with prune_loss :158-165).
-    users/pos/neg: int64 device vectors indexing rows of Eu / Ei."""
+    users/pos/neg: int64 device vectors indexing rows of Eu / Ei. Batches above LLMREC_BPR_MAX_B (up to LLMREC_BPR_WIDE_MAX_B) take
+    the multi-block selection (llmrec_bpr_prune_fwd_wide_f32); the routing is by size only."""
     if users.dtype != torch.int64 or pos.dtype != torch.int64 or neg.dtype != torch.int64:
         raise RuntimeError("bpr_prune: int64 index tensors expected")
-    if users.numel() > CONST["LLMREC_BPR_MAX_B"]:
-        raise RuntimeError("bpr_prune: batch of %d exceeds LLMREC_BPR_MAX_B" % users.numel())
+    if users.numel() > CONST["LLMREC_BPR_WIDE_MAX_B"]:
+        raise RuntimeError("bpr_prune: batch of %d exceeds LLMREC_BPR_WIDE_MAX_B" % users.numel())
     remember = 1 - drop_rate                                       # python float, as main.py:161
-    return _BprPrune.apply(Eu, Ei, users, pos, neg, remember, decay, batch_size_flag, n_valid)
+    fn = _BprPruneWide if users.numel() > CONST["LLMREC_BPR_MAX_B"] else _BprPrune
+    return fn.apply(Eu, Ei, users, pos, neg, remember, decay, batch_size_flag, n_valid)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -357,11 +357,14 @@ class Trainer(object):
             # the fused path reads the unmasked features, so any of the three sends the step down the modular path
             ok = (os.environ.get("LLMREC_FUSED", "1") == "1" and not args.mask and args.drop_rate == 0
                   and args.mask_rate == 0 and device.type == "cuda")
+            # the fused step's eight-problem loss launches stage the batch in LDS (LLMREC_BPR_MAX_B); a larger batch trains on the
+            # modular path, whose ops.bpr_prune selects with the multi-block kernels
+            b_max = self.batch_size + int(self.batch_size * args.aug_sample_rate)
+            ok = ok and b_max <= ops.CONST["LLMREC_BPR_MAX_B"]
             if ok:
                 from llmrec_amd.fused import FusedStep
                 graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(self.ui_graph),
                                        "iu": ops.operand_from_sparse_tensor(self.iu_graph)})
-                b_max = self.batch_size + int(self.batch_size * args.aug_sample_rate)
                 self._fused = FusedStep(self.model_mm, graph, self.hyper,
                                         (args.model_cat_rate, args.user_cat_rate, args.item_cat_rate), self.optimizer, b_max)
             else:
