@@ -392,8 +392,13 @@ def test_bpr_prune_forward_backward(ops, drop, B, d):
     Eug = Eu.detach().to(DEV).requires_grad_(True); Eig = Ei.detach().to(DEV).requires_grad_(True)
     out = ops.bpr_prune(Eug, Eig, users.to(DEV), pos.to(DEV), neg.to(DEV), drop, 1e-5, 1024)
     (0.7 * out[0] + 1.3 * out[1]).backward()
-    if int((1 - drop) * B) == 0:
+    if int((1 - drop) * B) == 0:                              # nothing kept: mf is the empty mean, the gradient is the regulariser's alone
         assert np.isnan(float(out[0])) and np.isnan(float(mf))
+        Eu64, Ei64 = Eu.detach().double().requires_grad_(True), Ei.detach().double().requires_grad_(True)
+        (1.3 * O.bpr_loss(Eu64[users], Ei64[pos], Ei64[neg], cfg)[1]).backward()
+        for got, want in ((Eug.grad, Eu64.grad), (Eig.grad, Ei64.grad)):
+            assert bool(torch.isfinite(got).all()) and float(want.abs().max()) > 0
+            assert rel_err(got.cpu(), want) < 2e-5
         return
     assert abs(float(out[0]) - float(mf)) < 2e-6 * abs(float(mf))
     assert abs(float(out[1]) - float(emb)) < 2e-6 * abs(float(emb))
