@@ -215,6 +215,35 @@ int llmrec_spmm_f32(int64_t n_rows, int64_t n_cols,
                     const llmrec_spmm_plan_t* plan_host, float* partials,
                     const llmrec_spmm_epilogue_t* epilogue_host /* NULL = none */, llmrec_stream_t stream);
 
+/* MIXED-PRECISION PROPAGATION (opt-in: llmrec_amd/dist_fused.py, gather_dtype = "bf16"): the product that gathers BF16 rows. At scale the
+ * SpMM is bound by the fabric's rate for random row gathers, and a d = 64 row is two 128-B lines in fp32 but one in bf16. Only the gathered
+ * operand is narrow: indices, weights, accumulation, the epilogue's operands and Y are fp32, as in llmrec_spmm_f32.
+ *   llmrec_rows_to_bf16     Xb[r] = RNE_bf16(row_scale[r] * X[r]) (row_scale NULL = none): one dense pass, the bf16 shadow of an fp32 tensor
+ *                           (round to nearest even, NaN -> quiet NaN: torch's float -> bfloat16). Any d and ld; 16-byte rows of X and 8-byte
+ *                           rows of Xb take the vector path.
+ *   llmrec_spmm_xbf16_f32   Y = post_scale . op(alpha Z + diag(row_scale) (P (.) val) diag(col_scale) widen(Xb)) - every argument but Xb / Yb
+ *                           as in llmrec_spmm_f32, without column slices. The fp32 vector families' lanes per row (d <= 16 / 32 / 64 / 128 /
+ *                           256) each load their four columns as ONE 8-byte access and widen them by a 16-bit shift; buckets, plans (permuted
+ *                           CSR included) and summation trees are those of llmrec_spmm_f32, so the result is BIT-IDENTICAL to llmrec_spmm_f32
+ *                           on the fp32 tensor widen(Xb).
+ *                           Yb (NULL = none): Yb[r] = RNE_bf16(Y[r]) of the FINISHED row - after the epilogue and post_scale; for split rows
+ *                           by the finalize launch - the shadow the next product of a chain gathers from. Yb must not overlap Xb.
+ *                           Supported: d % 4 == 0, d <= 256; ldxb % 4 == 0 and Xb 8-byte aligned; Yb rows 8-byte aligned; Y, Z, S, partials as
+ *                           the vector path of llmrec_spmm_f32 needs them (16-byte rows); epilogue ops NONE / SOFTMAX / SOFTMAX_BWD with
+ *                           alpha, Z (may alias Y), S, post_scale. LLMREC_EUNSUPPORTED for any other d and for an epilogue with x_row_mask,
+ *                           y_row_flag, z_row_flag, y_row_gate, y_row_needed, rows_listed_only or x_mask_stamp (masked products gather few
+ *                           rows and stay fp32); LLMREC_EINVAL for bad arguments (null pointers, ld < d, misaligned rows, a bad plan) -
+ *                           either way before anything is launched, nothing written. No grouped, guest or hosted form. */
+int llmrec_rows_to_bf16(int64_t n_rows, int32_t d, const float* row_scale /* NULL = none */,
+                        const float* X, int64_t ldx, uint16_t* Xb, int64_t ldxb, llmrec_stream_t stream);
+int llmrec_spmm_xbf16_f32(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* colidx, const float* val,
+                          const float* row_scale, const float* col_scale,
+                          const uint16_t* Xb, int64_t ldxb,            /* the gathered operand: bf16 rows */
+                          float* Y, int64_t ldy,
+                          uint16_t* Yb, int64_t ldyb,                  /* NULL, or: Yb[r] = RNE_bf16(Y[r]) of the FINISHED row */
+                          int32_t d, const llmrec_spmm_plan_t* plan_host, float* partials,
+                          const llmrec_spmm_epilogue_t* epilogue_host /* NULL = none */, llmrec_stream_t stream);
+
 /* Independent products in ONE launch (the latency-bound step: each product alone leaves most CUs idle). Each llmrec_spmm_problem_t carries
  * exactly the arguments of one llmrec_spmm_f32 call and is checked like one; the problems' blocks follow each other in the given order
  * (longest first keeps the tail short), and problems with split rows share one finalize launch after the main one. Every row keeps its

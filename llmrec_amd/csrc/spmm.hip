@@ -142,41 +142,6 @@ __global__ __launch_bounds__(TPB, 5) void spmm_smask_multi_guest_kernel(SpmmMult
     }
 }
 
-// one block per (split row, slice): the 256/LPR lane groups each add every (256/LPR)-th segment partial (ascending),
-// then the groups are combined through LDS in group order - a fixed summation tree; then the row's epilogue
-template <int LPR, int NCHUNK, int VEC>
-__device__ __forceinline__ void spmm_finalize_body(const SpmmArgs& a, int32_t blk, float* fin_lds) {
-    constexpr int G = 256 / LPR;
-    constexpr int ROWW = NCHUNK * LPR * VEC;
-    const int gl = threadIdx.x & (LPR - 1), g = threadIdx.x / LPR;
-    const int32_t slice = blk / a.n_split_rows, slot = blk - slice * a.n_split_rows;
-    const int32_t crow = a.split_rows[slot];
-    const int32_t row = a.slot_row ? a.slot_row[crow] : crow;
-    const int32_t deg = a.rowptr[crow + 1] - a.rowptr[crow];
-    const int32_t nseg = (deg + a.segment - 1) / a.segment;
-    const float* pr = a.partials + ((int64_t)slice * a.n_segments + a.split_seg_begin[slot]) * a.d;
-    Vec<VEC> acc[NCHUNK];
-#pragma unroll
-    for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
-    for (int s0 = g; s0 < nseg; s0 += G) {
-#pragma unroll
-        for (int k = 0; k < NCHUNK; ++k) {
-            const int col = (k * LPR + gl) * VEC;
-            if (col < a.d) { Vec<VEC> v; v.load(pr + (int64_t)s0 * a.d + col); acc[k].add(v); }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NCHUNK; ++k) acc[k].store(fin_lds + g * ROWW + (k * LPR + gl) * VEC);
-    __syncthreads();
-    if (g != 0) return;
-#pragma unroll
-    for (int k = 0; k < NCHUNK; ++k) {
-        acc[k].zero();
-        for (int gg = 0; gg < G; ++gg) { Vec<VEC> o; o.load(fin_lds + gg * ROWW + (k * LPR + gl) * VEC); acc[k].add(o); }
-    }
-    finish_row<LPR, NCHUNK, VEC>(a, (int64_t)slice * a.d, row, gl, acc);
-}
-
 template <int LPR, int NCHUNK, int VEC>
 __global__ __launch_bounds__(256) void spmm_finalize_kernel(SpmmArgs a) {
     __shared__ __attribute__((aligned(16))) float fin_lds[(256 / LPR) * NCHUNK * LPR * VEC];
@@ -520,6 +485,19 @@ int spmm_prepare_hosted(const llmrec_spmm_problem_t& pr, int tpb, SpmmHosted& ou
     out.blocks = spmm_layout(out.a, kSpmmFamilyLpr[pp.family], 0, tpb);
     if (out.blocks < 0) { set_error("spmm (hosted): too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
     out.bytes_x = pp.bytes_x; out.bytes_y = pp.bytes_y;
+    return LLMREC_OK;
+}
+
+// One unmasked product for a launch of its own by another translation unit (spmm_body.h: SpmmSingle; the caller has refused the masks).
+int spmm_prepare_single(const llmrec_spmm_problem_t& pr, SpmmSingle& out) {
+    SpmmPrepared pp;
+    const int rc = spmm_prepare(pr, pp);
+    if (rc != LLMREC_OK) return rc;
+    out.a = pp.a; out.family = pp.family; out.weighted = pp.variant == SPMM_V_WEIGHTED || pp.variant == SPMM_V_MASKED_W;
+    out.empty = pp.empty; out.blocks = 0;
+    if (pp.empty) return LLMREC_OK;
+    out.blocks = spmm_layout(out.a, kSpmmFamilyLpr[pp.family], 0);
+    if (out.blocks < 0) { set_error("spmm: too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
     return LLMREC_OK;
 }
 

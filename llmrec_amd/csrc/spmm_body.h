@@ -9,12 +9,27 @@ namespace llmrec {
 
 constexpr int UNROLL = 8;
 
+// fp32 -> bf16, round to nearest even, as the high half of a word (the idiom of topk.hip's tk_rn_bf16_bits); a NaN stays a quiet NaN
+__device__ __forceinline__ uint32_t rn_bf16_bits(float x) {
+    const uint32_t b = __float_as_uint(x);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc00000u;
+    return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
+}
+
 template <int VEC> struct Vec;
 template <> struct Vec<4> {
     float4 v;
     __device__ __forceinline__ void zero() { v = make_float4(0.f, 0.f, 0.f, 0.f); }
     __device__ __forceinline__ void load(const float* p) { v = *reinterpret_cast<const float4*>(p); }
     __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = v; }
+    // four bf16 values (one 8-byte access), widened exactly: a bf16 is the high half of the fp32 with the same value
+    __device__ __forceinline__ void load(const uint16_t* p) {
+        const uint2 r = *reinterpret_cast<const uint2*>(p);
+        v = make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u));
+    }
+    __device__ __forceinline__ void store_bf16(uint16_t* p) const {
+        *reinterpret_cast<uint2*>(p) = make_uint2(rn_bf16_bits(v.x) >> 16 | rn_bf16_bits(v.y), rn_bf16_bits(v.z) >> 16 | rn_bf16_bits(v.w));
+    }
     __device__ __forceinline__ void add(const Vec& o) { v.x += o.v.x; v.y += o.v.y; v.z += o.v.z; v.w += o.v.w; }
     __device__ __forceinline__ void fma(float w, const Vec& o) {
         v.x = fmaf(w, o.v.x, v.x); v.y = fmaf(w, o.v.y, v.y); v.z = fmaf(w, o.v.z, v.z); v.w = fmaf(w, o.v.w, v.w);
@@ -26,7 +41,14 @@ template <> struct Vec<4> {
     }
     __device__ __forceinline__ float hmax() const { return fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)); }
     __device__ __forceinline__ float hsum() const { return (v.x + v.y) + (v.z + v.w); }
-    __device__ __forceinline__ float dot(const Vec& o) const { return (v.x * o.v.x + v.y * o.v.y) + (v.z * o.v.z + v.w * o.v.w); }
+    // (x0 y0 + x1 y1) + (x2 y2 + x3 y3) with its two fused multiply-adds WRITTEN OUT and no contraction left to the compiler: how the
+    // plain expression is contracted depends on the code around it, and the softmax backward of one row must round the same way in
+    // every kernel that finishes it (the fp32 and the bf16-row products, single and grouped launches: they are compared bit for bit)
+    __device__ __forceinline__ float dot(const Vec& o) const {
+#pragma clang fp contract(off)
+        const float t1 = __builtin_fmaf(v.x, o.v.x, v.y * o.v.y), t2 = __builtin_fmaf(v.z, o.v.z, v.w * o.v.w);
+        return t1 + t2;
+    }
     __device__ __forceinline__ void exp_sub(float m) { v.x = expf(v.x - m); v.y = expf(v.y - m); v.z = expf(v.z - m); v.w = expf(v.w - m); }
     // this = s * (this - c)    (softmax backward: y * (g - sum(g y)))
     __device__ __forceinline__ void sub_mul(float c, const Vec& s) { v.x = s.v.x * (v.x - c); v.y = s.v.y * (v.y - c); v.z = s.v.z * (v.z - c); v.w = s.v.w * (v.w - c); }
@@ -101,13 +123,31 @@ struct SpmmArgs {
     int32_t blk_begin, blk_seg, blk_block, blk_wave, blk_end;
 };
 
+// The product that gathers BF16 rows (spmm_bf16.hip: llmrec_spmm_xbf16_f32). The bodies below take their argument block as a template
+// parameter and reach the gathered operand and the finished row through x_row / store_shadow only: with SpmmArgs they are the fp32
+// product, token for token; with SpmmArgsXb every gather is one 8-byte load of four bf16 values widened by a shift (Vec<4>::load) - the
+// same lanes, chunks and order of additions, so the result is bit for bit that of the fp32 product on the widened operand - and the
+// finished row (after the epilogue and post_scale) is also stored rounded to bf16 when Yb is given.
+struct SpmmArgsXb : SpmmArgs {
+    const uint16_t* Xb;          // [n_cols, d] bf16 rows (SpmmArgs::X is unused)
+    int64_t ldxb;
+    uint16_t* Yb;                // NULL, or [n_rows, d]: Yb[r] = RNE_bf16(Y[r])
+    int64_t ldyb;
+};
+__device__ __forceinline__ const float* x_row(const SpmmArgs& a, int32_t c) { return a.X + (int64_t)c * a.ldx; }
+__device__ __forceinline__ const uint16_t* x_row(const SpmmArgsXb& a, int32_t c) { return a.Xb + (int64_t)c * a.ldxb; }
+template <int VEC> __device__ __forceinline__ void store_shadow(const SpmmArgs&, int64_t, int64_t, const Vec<VEC>&) {}
+__device__ __forceinline__ void store_shadow(const SpmmArgsXb& a, int64_t row, int64_t col, const Vec<4>& v) {
+    if (a.Yb) v.store_bf16(a.Yb + row * a.ldyb + col);
+}
+
 // Accumulate sum_{j in [s, e)} w_j * X[col_j, chunk columns] into acc, in ascending j order. MASKED: rows of X that are not active
 // (a.x_mask) are known to be all-zero and are not fetched; `any` collects whether this lane saw an active column.
 // unmasked ranges (round 6): the NEXT chunk's column indices (and adjacency values) are fetched while the current chunk's rows are gathered, the
 // col_scale factors of the current chunk ride beside its gathers - one memory round trip per chunk of LPR non-zeros instead of two or three.
 // Same gathers, same order of additions as one chunk at a time: bit-identical to the masked loop with every column active.
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED>
-__device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK]) {
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, class A>
+__device__ __forceinline__ void accumulate_range_plain(const A& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK]) {
     int32_t c_next = 0;
     float v_next = 1.0f;
     if (s + gl < e) { c_next = a.colidx[s + gl]; if (WEIGHTED && a.val) v_next = a.val[s + gl]; }
@@ -125,7 +165,7 @@ __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_
             for (int u = 0; u < UNROLL; ++u) {
                 const int tt = t + u;
                 const int32_t c = __shfl(myc, tt & (LPR - 1), LPR);
-                const float* xr = a.X + (int64_t)c * a.ldx + col0;
+                const auto* xr = x_row(a, c) + col0;
 #pragma unroll
                 for (int k = 0; k < NCHUNK; ++k) {
                     const int col = (k * LPR + gl) * VEC;
@@ -148,8 +188,8 @@ __device__ __forceinline__ void accumulate_range_plain(const SpmmArgs& a, int64_
     }
 }
 
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK], int& any,
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, class A>
+__device__ __forceinline__ void accumulate_range(const A& a, int64_t col0, int32_t s, int32_t e, int gl, Vec<VEC> (&acc)[NCHUNK], int& any,
                                                  const uint8_t* xm, int xa) {
     if constexpr (!MASKED) {
         accumulate_range_plain<LPR, NCHUNK, VEC, WEIGHTED>(a, col0, s, e, gl, acc);
@@ -181,7 +221,7 @@ __device__ __forceinline__ void accumulate_range(const SpmmArgs& a, int64_t col0
                     bits &= bits - 1ull;                                   // (0 stays 0)
                     const int32_t c = __shfl(myc, j, LPR);
                     if (WEIGHTED) w[u] = valid ? __shfl(myw, j, LPR) : 0.f; else w[u] = 0.f;
-                    const float* xr = a.X + (int64_t)c * a.ldx + col0;
+                    const auto* xr = x_row(a, c) + col0;
 #pragma unroll
                     for (int k = 0; k < NCHUNK; ++k) {
                         const int col = (k * LPR + gl) * VEC;
@@ -211,8 +251,8 @@ __device__ __forceinline__ bool write_row_flag(const SpmmArgs& a, int64_t row, b
 }
 
 // The finished row (unscaled sum in acc, held by the LPR lanes of one lane group): scale, init term, epilogue, store.
-template <int LPR, int NCHUNK, int VEC>
-__device__ __forceinline__ void finish_row(const SpmmArgs& a, int64_t col0, int64_t row, int gl, Vec<VEC> (&acc)[NCHUNK], bool zero_row = false) {
+template <int LPR, int NCHUNK, int VEC, class A>
+__device__ __forceinline__ void finish_row(const A& a, int64_t col0, int64_t row, int gl, Vec<VEC> (&acc)[NCHUNK], bool zero_row = false) {
     const float rs = a.row_scale ? a.row_scale[row] : 1.0f;
     float* yr = a.Y + row * a.ldy + col0;
     if (zero_row) {                                              // (uniform per lane group) a masked product's row without an active neighbour
@@ -266,15 +306,15 @@ __device__ __forceinline__ void finish_row(const SpmmArgs& a, int64_t col0, int6
 #pragma unroll
     for (int k = 0; k < NCHUNK; ++k) {
         const int col = (k * LPR + gl) * VEC;
-        if (col < a.d) acc[k].store(yr + col);
+        if (col < a.d) { acc[k].store(yr + col); store_shadow(a, row, col0 + col, acc[k]); }
     }
 }
 
 constexpr int TPB = 512;                                        // threads per block: 8 wavefronts
 
 // one lane group per (row, slice) task; rows with more than LLMREC_SPMM_LONG_ROW nnz belong to the other ranges
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, int BT = TPB>
-__device__ __forceinline__ void rows_body(const SpmmArgs& a, int64_t block) {
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, int BT = TPB, class A>
+__device__ __forceinline__ void rows_body(const A& a, int64_t block) {
     constexpr int GPB = BT / LPR;
     const int gl = threadIdx.x & (LPR - 1);
     const int64_t task = block * GPB + (threadIdx.x / LPR);
@@ -320,8 +360,8 @@ __device__ __forceinline__ void rows_body(const SpmmArgs& a, int64_t block) {
 // rows of task i are gathered, the indices of task i + 1 and the row pointers of task i + 2 are already in flight - ONE round trip per task
 // after a two-deep prologue, and pipe x fewer blocks to schedule. Same gathers in the same order: bit-identical sums. (The other shape tried -
 // one task per row looping over the slices, indices loaded once - was no faster in the step and slower alone: 29.4 vs 28.3 us.)
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, int BT = TPB>
-__device__ __forceinline__ void rows_body_pipe(const SpmmArgs& a, int64_t block, int64_t n_blocks) {
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, int BT = TPB, class A>
+__device__ __forceinline__ void rows_body_pipe(const A& a, int64_t block, int64_t n_blocks) {
     constexpr int GPB = BT / LPR;
     constexpr int NI = (LLMREC_SPMM_LONG_ROW + LPR - 1) / LPR;         // index registers per lane
     const int gl = threadIdx.x & (LPR - 1);
@@ -377,7 +417,7 @@ __device__ __forceinline__ void rows_body_pipe(const SpmmArgs& a, int64_t block,
                     for (int u = 0; u < UNROLL; ++u) {
                         const int tt = t + u;
                         const int32_t c = __shfl(c0[ki], tt & (LPR - 1), LPR);
-                        const float* xr = a.X + (int64_t)c * a.ldx + col00;
+                        const auto* xr = x_row(a, c) + col00;
 #pragma unroll
                         for (int k = 0; k < NCHUNK; ++k) {
                             const int col = (k * LPR + gl) * VEC;
@@ -530,8 +570,8 @@ __device__ __forceinline__ void rows_body_pipe_smask(const SpmmArgs& a, int64_t 
 }
 
 // one wavefront over [s, e): the 64/LPR lane groups take contiguous parts, butterfly sum -> every group holds the total
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ void wave_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, int lane, Vec<VEC> (&acc)[NCHUNK], int& any,
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, class A>
+__device__ __forceinline__ void wave_range(const A& a, int64_t col0, int32_t s, int32_t e, int lane, Vec<VEC> (&acc)[NCHUNK], int& any,
                                            const uint8_t* xm, int xa) {
     constexpr int G = 64 / LPR;
     const int gl = lane & (LPR - 1), g = lane / LPR;
@@ -558,8 +598,8 @@ __device__ __forceinline__ void list_task(const SpmmArgs& a, const int32_t* list
 }
 
 // one wavefront per (row, slice) of the wave-row list
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, int BT = TPB>
-__device__ __forceinline__ void wave_rows_body(const SpmmArgs& a, int32_t block) {
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, int BT = TPB, class A>
+__device__ __forceinline__ void wave_rows_body(const A& a, int32_t block) {
     const int lane = threadIdx.x & 63;
     const int64_t task = (int64_t)block * (BT / 64) + (threadIdx.x >> 6);
     if (task >= (int64_t)a.n_wave_rows * a.n_slices) return;
@@ -616,8 +656,8 @@ __device__ __forceinline__ void wave_rows_body_smask(const SpmmArgs& a, int32_t 
 
 // one block over [s, e): the 8 waves take contiguous parts, summed through LDS in wave order; the total ends up in the
 // first lane group of wave 0 (returns true there)
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED>
-__device__ __forceinline__ bool block_range(const SpmmArgs& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK],
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, class A>
+__device__ __forceinline__ bool block_range(const A& a, int64_t col0, int32_t s, int32_t e, float* lds, Vec<VEC> (&acc)[NCHUNK],
                                             const uint8_t* xm, int xa) {
     constexpr int ROWW = NCHUNK * LPR * VEC;
     constexpr int NW = TPB / 64;
@@ -689,8 +729,8 @@ __device__ __forceinline__ bool block_range_smask(const SpmmArgs& a, int64_t col
 // One problem's block b (a global block id) of the ranges of SpmmArgs: the heavy blocks come first. The segment partials are indexed by
 // the problem-local block id, so a grouped launch addresses them exactly like a launch of its own.
 // SMASK (with MASKED = false): the slice-masked product - the run-time choice between the plain and the masked loops per task.
-template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool SMASK = false>
-__device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* red_lds) {
+template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, bool MASKED, bool SMASK = false, class A>
+__device__ __forceinline__ void spmm_body(const A& a, int32_t b, float* red_lds) {
     static_assert(!SMASK || (WEIGHTED && !MASKED), "spmm_body: the slice-masked product is weighted and has no host-stamped mask");
     if (b >= a.blk_wave) {
         const int64_t lb = (int64_t)b - a.blk_wave;
@@ -741,6 +781,42 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, int32_t b, float* r
     }
 }
 
+// The finalize launch of the split rows. One block of 256 threads per (split row, slice): the 256/LPR lane groups each add every
+// (256/LPR)-th segment partial (ascending), then the groups are combined through LDS in group order - a fixed summation tree; then the
+// row's epilogue
+template <int LPR, int NCHUNK, int VEC, class A>
+__device__ __forceinline__ void spmm_finalize_body(const A& a, int32_t blk, float* fin_lds) {
+    constexpr int G = 256 / LPR;
+    constexpr int ROWW = NCHUNK * LPR * VEC;
+    const int gl = threadIdx.x & (LPR - 1), g = threadIdx.x / LPR;
+    const int32_t slice = blk / a.n_split_rows, slot = blk - slice * a.n_split_rows;
+    const int32_t crow = a.split_rows[slot];
+    const int32_t row = a.slot_row ? a.slot_row[crow] : crow;
+    const int32_t deg = a.rowptr[crow + 1] - a.rowptr[crow];
+    const int32_t nseg = (deg + a.segment - 1) / a.segment;
+    const float* pr = a.partials + ((int64_t)slice * a.n_segments + a.split_seg_begin[slot]) * a.d;
+    Vec<VEC> acc[NCHUNK];
+#pragma unroll
+    for (int k = 0; k < NCHUNK; ++k) acc[k].zero();
+    for (int s0 = g; s0 < nseg; s0 += G) {
+#pragma unroll
+        for (int k = 0; k < NCHUNK; ++k) {
+            const int col = (k * LPR + gl) * VEC;
+            if (col < a.d) { Vec<VEC> v; v.load(pr + (int64_t)s0 * a.d + col); acc[k].add(v); }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NCHUNK; ++k) acc[k].store(fin_lds + g * ROWW + (k * LPR + gl) * VEC);
+    __syncthreads();
+    if (g != 0) return;
+#pragma unroll
+    for (int k = 0; k < NCHUNK; ++k) {
+        acc[k].zero();
+        for (int gg = 0; gg < G; ++gg) { Vec<VEC> o; o.load(fin_lds + gg * ROWW + (k * LPR + gl) * VEC); acc[k].add(o); }
+    }
+    finish_row<LPR, NCHUNK, VEC>(a, (int64_t)slice * a.d, row, gl, acc);
+}
+
 // spmm_body for a product HOSTED by another kernel's launch of BT-thread blocks: unmasked, no split rows (the host of the launch refuses
 // such a plan: blk_seg == blk_begin), block b of a layout made for BT threads (spmm_layout). red_lds: (TPB / 64 - 1) rows of floats.
 template <int LPR, int NCHUNK, int VEC, bool WEIGHTED, int BT>
@@ -769,5 +845,16 @@ struct SpmmHosted {
     int64_t blocks, bytes_x, bytes_y;
 };
 int spmm_prepare_hosted(const llmrec_spmm_problem_t& pr, int tpb, SpmmHosted& out);
+
+// host side of a single product launched by another translation unit (spmm_bf16.hip, whose X is not an fp32 tensor: pr.X = NULL, pr.ldx =
+// the operand's ld): the checks of llmrec_spmm_f32, the kernel family (spmm.hip: 0..4 = the float4 families of up to 16 / 32 / 64 / 128 /
+// 256 columns), whether the operand is weighted, and the arguments laid out as a launch of their own with its block count
+struct SpmmSingle {
+    SpmmArgs a;
+    int family;
+    bool weighted, empty;
+    int64_t blocks;
+};
+int spmm_prepare_single(const llmrec_spmm_problem_t& pr, SpmmSingle& out);
 
 }  // namespace llmrec

@@ -104,9 +104,23 @@ class HipBackend:
     def degrees(self, csr) -> torch.Tensor:
         return (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.float32)
 
-    def spmm(self, csr, X, out=None, epilogue=None):
+    supports_bf16_gather = True                    # spmm(x_bf16=...) / to_bf16: llmrec_spmm_xbf16_f32, llmrec_rows_to_bf16
+
+    def bf16_gather_refusal(self, d: int):
+        """None, or why llmrec_spmm_xbf16_f32 has no kernel for rows of d columns."""
+        if d % 4 != 0 or d > self.ops.SPMM_BF16_MAX_D:
+            return "d = %d (the bf16-row product is compiled for multiples of 4 up to %d)" % (d, self.ops.SPMM_BF16_MAX_D)
+        return None
+
+    def to_bf16(self, X, out, row_scale=None):
+        """out[r] = bf16(row_scale[r] * X[r]) (round to nearest even): the shadow a bf16-row product gathers from."""
+        return self.ops.rows_to_bf16(X, out=out, row_scale=row_scale)
+
+    def spmm(self, csr, X, out=None, epilogue=None, x_bf16=None, out_bf16=None):
         """Y = epilogue(A X); epilogue: None or {"op": "none" | "softmax" | "softmax_bwd", "alpha", "Z", "S", "post_scale",
-        "x_row_mask", "x_mask_active", "y_row_flag", "z_row_flag", "y_row_gate", "y_row_needed"} (llmrec_spmm_epilogue_t's row sparsity)."""
+        "x_row_mask", "x_mask_active", "y_row_flag", "z_row_flag", "y_row_gate", "y_row_needed"} (llmrec_spmm_epilogue_t's row sparsity).
+        x_bf16 (the bf16 shadow of X): the rows are gathered from IT (llmrec_spmm_xbf16_f32; X is not read) and out_bf16, if given,
+        receives bf16(Y) - dense products only, the library refuses a row-sparsity key."""
         o = self.ops
         epi = None
         if epilogue is not None:
@@ -114,6 +128,10 @@ class HipBackend:
             epi = o.spmm_epilogue(op, epilogue.get("alpha", 0.0), epilogue.get("Z"), epilogue.get("S"), epilogue.get("post_scale"),
                                   epilogue.get("x_row_mask"), epilogue.get("x_mask_active", 0), epilogue.get("y_row_flag"), epilogue.get("z_row_flag"),
                                   epilogue.get("y_row_gate"), epilogue.get("y_row_needed"))
+        if x_bf16 is not None:
+            return o.spmm_bf16(csr, x_bf16, out=out, out_bf16=out_bf16, epilogue=epi)
+        if out_bf16 is not None:
+            raise RuntimeError("HipBackend.spmm: out_bf16 is written by the bf16-row product only (pass x_bf16)")
         return o.spmm_raw(csr, X, out=out, epilogue=epi)
 
     def spmm_listed(self, csr, X, rows, out):

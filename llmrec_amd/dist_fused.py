@@ -36,6 +36,7 @@ torch-CPU stand-in to run this file under gloo with two ranks against the single
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional
 
 import torch
@@ -133,14 +134,21 @@ class ShardedFusedID:
                  lr: float, batch_local: int, drop_rate: float, decay: float, n_chunks: Optional[int] = None,
                  user_init: Optional[torch.Tensor] = None, item_init: Optional[torch.Tensor] = None,
                  batch_size_flag: Optional[float] = None, exchange: str = "all_reduce", sparse_backward: bool = True,
-                 sparse_forward: bool = True, owner_updates_items: Optional[bool] = None):
+                 sparse_forward: bool = True, owner_updates_items: Optional[bool] = None, gather_dtype: Optional[str] = None):
         """batch_size_flag: the divisor of the BPR regulariser - the reference divides by the --batch_size FLAG, not by the
         number of triples in the batch (main.py:340: augmented triples do not change it); default = batch_local * world.
         exchange: "all_reduce" | "rs_ag" (module docstring). sparse_backward: skip the all-zero operand rows in the two SpMMs of the last
         layer's backward (False: the dense products, for A/B runs). sparse_forward: compute the last layer's two forward products only in
         the rows the step reads (forward(needed=...)). owner_updates_items (default: on with "rs_ag"): the item table's AdamW is SHARDED - the
         last backward message's gradient is reduce-scattered, each rank updates the rows it owns (parameters + both moments: 28 B per
-        parameter once per row instead of once per rank) and the all-gather returns updated table rows instead of gradient rows."""
+        parameter once per row instead of once per rank) and the all-gather returns updated table rows instead of gradient rows.
+        gather_dtype: "fp32" | "bf16"; None reads the environment variable LLMREC_GATHER_DTYPE (default fp32, the parity contract).
+        "bf16" is MIXED-PRECISION PROPAGATION: every dense SpMM of forward() and step() gathers its operand rows from a bf16 shadow
+        (llmrec_spmm_xbf16_f32: half the bytes per gathered row); accumulation, epilogues, outputs, tables, the loss, the optimiser and
+        every exchanged message stay fp32, and the masked / row-restricted products keep the fp32 call on the fp32 tensors. A user-side
+        output's shadow is written by the bf16 product that produces it (or by one conversion pass behind a masked fp32 producer); an
+        item-side operand is complete only after its exchange, so its shadow is one conversion pass over I x d at that point. Two
+        preallocated shadows, [U, d] and [I, d] bf16 (message_bytes_per_step()["bf16_shadow_bytes"]); replicas stay bit-identical."""
         self.g, self.comm, self.be = graph, comm, backend
         self.d, self.L, self.B = d, n_layers, batch_local
         self.remember, self.decay = 1.0 - drop_rate, decay
@@ -148,6 +156,18 @@ class ShardedFusedID:
         if exchange not in ("all_reduce", "rs_ag"):
             raise ValueError("ShardedFusedID: exchange must be all_reduce or rs_ag")
         self.exchange = exchange
+        if gather_dtype is None:
+            gather_dtype = os.environ.get("LLMREC_GATHER_DTYPE", "fp32")
+        if gather_dtype not in ("fp32", "bf16"):
+            raise ValueError("ShardedFusedID: gather_dtype must be fp32 or bf16, got %r" % (gather_dtype,))
+        self.gather_dtype, self.bf16 = gather_dtype, gather_dtype == "bf16"
+        if self.bf16:
+            if not getattr(backend, "supports_bf16_gather", False):
+                raise RuntimeError("ShardedFusedID: gather_dtype='bf16' needs a backend with the bf16-row SpMM (supports_bf16_gather); %s has none"
+                                   % type(backend).__name__)
+            why = backend.bf16_gather_refusal(d)
+            if why:
+                raise RuntimeError("ShardedFusedID: gather_dtype='bf16' is not available at " + why)
         self.owner_updates_items = (exchange == "rs_ag") if owner_updates_items is None else bool(owner_updates_items and exchange == "rs_ag")
         dev = graph.s_i.device
         U, I = graph.n_users_local, graph.n_items
@@ -179,6 +199,9 @@ class ShardedFusedID:
         self.hU = f(U, d)
         self.E_u, self.E_i = self.hU, f(I, d)
         self.bufI, self.tmpI = f(I, d), f(I, d)
+        # bf16 mode: the shadows the dense products gather from - one per side, each consumed before the next one is written
+        self.Ub = torch.empty(U, d, dtype=torch.bfloat16, device=dev) if self.bf16 else None
+        self.Ib = torch.empty(I, d, dtype=torch.bfloat16, device=dev) if self.bf16 else None
         self.item_tab.grad, self.user_tab.grad = f(I, d), self.dE_u
         self.opt = backend.optimizer([self.user_tab, self.item_tab], lr)
         # the backward runs the PATTERN operands (no per-edge col_scale gather): the tensor an SpMM gathers from is scaled by
@@ -232,19 +255,34 @@ class ShardedFusedID:
         return [self.user_tab, self.item_tab]
 
     # -- the chunked, overlapped all-reduce ----------------------------------------------------------
-    def _reduced_spmm(self, chunk_ops, X, out, epilogue_for=None, after=None, owner_update=None):
+    def _dense_spmm(self, csr, X, out, epilogue=None, x_shadow=None, out_shadow=None):
+        """One DENSE product. fp32 mode: be.spmm(csr, X). bf16 mode: the rows are gathered from x_shadow (= bf16(X), already written) and
+        out_shadow, if given, receives bf16(out) from the finished rows."""
+        if not self.bf16:
+            return self.be.spmm(csr, X, out=out, epilogue=epilogue)
+        return self.be.spmm(csr, X, out=out, epilogue=epilogue, x_bf16=x_shadow, out_bf16=out_shadow)
+
+    def _shadow(self, X, buf):
+        """bf16 mode: buf = bf16(X) by one dense pass (X is complete: behind its exchange / its masked fp32 producer); fp32 mode: nothing."""
+        if not self.bf16:
+            return None
+        self.be.to_bf16(X, buf)
+        return buf
+
+    def _reduced_spmm(self, chunk_ops, X, out, epilogue_for=None, after=None, owner_update=None, x_shadow=None):
         """out[rows_c] = sum over ranks of chunk_ops[c] @ X, chunk by chunk: the exchange of chunk c is in flight
         while chunk c + 1 is computed. after(view): optional row-local op on reduced rows (the softmax) - on the whole
         chunk after an all-reduce, on the owned piece between the reduce-scatter and the all-gather of "rs_ag".
         owner_update = (table, fn(row0, row1, reduced_rows)) ("rs_ag" only; `out` is the table's gradient): the rank that owns a piece
         of a chunk applies fn to ITS rows of `table` with the reduced gradient piece and the all-gather moves the updated TABLE rows (in
-        place) instead of the gradient; chunks that do not split evenly are all-reduced and every rank applies fn to all their rows."""
+        place) instead of the gradient; chunks that do not split evenly are all-reduced and every rank applies fn to all their rows.
+        x_shadow (bf16 mode): bf16(X), which every chunk's product gathers from."""
         comm = self.comm
         collective = comm.dist is not None and (comm.world > 1 or comm.force)
         pending, started = [], []
         for c, (r0, r1) in enumerate(self.chunks):
             view = out[r0:r1]
-            self.be.spmm(chunk_ops[c], X, out=view, epilogue=epilogue_for(r0, r1) if epilogue_for else None)
+            self._dense_spmm(chunk_ops[c], X, view, epilogue_for(r0, r1) if epilogue_for else None, x_shadow=x_shadow)
             self.allreduce_bytes += view.numel() * 4
             if collective and self.exchange == "rs_ag" and self.shards[c] is not None:
                 if owner_update is not None:
@@ -294,9 +332,12 @@ class ShardedFusedID:
                 be.softmax_rows_into(part, part)
                 be.scatter_set_rows(rows, n_rows, part, self.Il[l])
                 break
-            be.spmm(self.g.ui_fwd, i_prev, out=self.Ul[l], epilogue={"op": "softmax"} if last else None)      # local users
+            # (bf16 mode: i_prev is complete here - the table, or a layer behind its exchange: one conversion pass; U^{l+1}'s shadow
+            #  is written by the product itself)
+            self._dense_spmm(self.g.ui_fwd, i_prev, self.Ul[l], {"op": "softmax"} if last else None,            # local users
+                             x_shadow=self._shadow(i_prev, self.Ib), out_shadow=self.Ub)
             self._reduced_spmm(self.iu_fwd_chunks, self.Ul[l], self.Il[l],
-                               after=(lambda view: be.softmax_rows_into(view, view)) if last else None)
+                               after=(lambda view: be.softmax_rows_into(view, view)) if last else None, x_shadow=self.Ub)
             i_prev = self.Il[l]
         if dense_users:
             be.layer_mean_into([self.user_tab.detach()] + self.Ul, self.E_u)
@@ -387,7 +428,12 @@ class ShardedFusedID:
                 epi["S"] = self.Ul[l]
             if sparse:                                            # rows of g outside the batch's items are zero: not gathered; flag_u := rows of h that can be non-zero
                 epi.update({"x_row_mask": self.flag_i, "x_mask_active": stamp, "z_row_flag": self.flag_u, "y_row_gate": self.flag_u})
-            be.spmm(self.R_user, g, out=self.hU, epilogue=epi)                           # h = s_u . dU[l+1] (softmax backward on the last layer)
+            if sparse:                                            # (the masked product stays fp32 in bf16 mode too: it gathers few rows)
+                be.spmm(self.R_user, g, out=self.hU, epilogue=epi)                       # h = s_u . dU[l+1] (softmax backward on the last layer)
+                h_shadow = self._shadow(self.hU, self.Ub)
+            else:
+                self._dense_spmm(self.R_user, g, self.hU, epi, x_shadow=self._shadow(g, self.Ib), out_shadow=self.Ub)
+                h_shadow = self.Ub
             dst = self.item_tab.grad if l == 0 else self.bufI
             w = inv / comm.world
             # (h itself is NOT sparse enough to mask: the users two hops from the batch - through its most popular items - are ~40 % of
@@ -399,7 +445,7 @@ class ShardedFusedID:
             self._reduced_spmm(self.ui_bwd_chunks, self.hU, dst,
                                epilogue_for=lambda r0, r1: {"op": "none", "alpha": w, "Z": self.dE_i[r0:r1],
                                                             "post_scale": None if l == 0 else self.s_i[r0:r1]},
-                               owner_update=upd if sharded_update else None)
+                               owner_update=upd if sharded_update else None, x_shadow=h_shadow)
             g = self.bufI
         if L == 0:
             be.axpy_into(inv, self.dE_i, self.item_tab.grad)
@@ -418,7 +464,8 @@ class ShardedFusedID:
     def eval_topk(self, query_users_local: torch.Tensor, K: int = 50, forward: bool = True):
         """Full-rank evaluation of this rank's users (reference utility/batch_test.py:112-169): users shard, the item table
         is replicated, so ranks are independent - no-grad forward (with its layer all-reduces) + scoring + masked top-K
-        against the local training rows. Returns (idx int32 [n, K], scores)."""
+        against the local training rows. Returns (idx int32 [n, K], scores). forward=True runs forward() in this object's gather_dtype:
+        with "bf16" the evaluation's propagation gathers bf16 rows exactly as the training step's does (scoring and top-K are unchanged)."""
         if forward:
             self.forward()
         return self.be.score_topk(self.E_u, self.E_i, query_users_local, self.g.by_user, K)
@@ -427,4 +474,6 @@ class ShardedFusedID:
     def message_bytes_per_step(self) -> dict:
         out = message_plan(self.I, self.d, self.L, self.B, len(self.chunks), self.exchange, self.sparse_forward)
         out["exchanged_bytes_last_step"] = int(self.allreduce_bytes)
+        out["gather_dtype"] = self.gather_dtype
+        out["bf16_shadow_bytes"] = 2 * (self.U + self.I) * self.d if self.bf16 else 0      # memory the mode adds (nothing of it is exchanged)
         return out

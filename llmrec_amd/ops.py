@@ -534,6 +534,51 @@ def spmm_raw(a: Csr, X: torch.Tensor, out: Optional[torch.Tensor] = None, accumu
     return Y
 
 
+SPMM_BF16_MAX_D = 256             # llmrec_spmm_xbf16_f32: d % 4 == 0, d <= 256
+
+
+def _bf16_rows(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
+        raise RuntimeError("%s: a 2-D torch.bfloat16 tensor with unit inner stride expected, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    return t
+
+
+def rows_to_bf16(X: torch.Tensor, out: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r] = bf16(row_scale[r] * X[r]), round to nearest even (llmrec_rows_to_bf16): the bf16 shadow an llmrec_spmm_xbf16_f32 product
+    gathers from. One dense pass; X may be a strided row view."""
+    _need_gpu(X, out, row_scale)
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1:
+        raise RuntimeError("rows_to_bf16: a 2-D fp32 tensor with unit inner stride expected")
+    if out is None:
+        out = torch.empty(X.shape, dtype=torch.bfloat16, device=X.device)
+    if _bf16_rows(out, "rows_to_bf16").shape != X.shape:
+        raise RuntimeError("rows_to_bf16: out is %s, X is %s" % (tuple(out.shape), tuple(X.shape)))
+    _lib.call("llmrec_rows_to_bf16", X.shape[0], X.shape[1], _p(row_scale), _p(X), _ld(X), _p(out), _ld(out), _stream())
+    return out
+
+
+def spmm_bf16(a: Csr, Xb: torch.Tensor, out: Optional[torch.Tensor] = None, out_bf16: Optional[torch.Tensor] = None, epilogue=None,
+              plan: Optional[SpmmPlan] = None) -> torch.Tensor:
+    """Y = epilogue(A widen(Xb)) through llmrec_spmm_xbf16_f32: the gathered rows are torch.bfloat16, everything else fp32 - bit for bit
+    spmm_raw(a, Xb.float(), plan=the same whole-row plan). out_bf16: also receives bf16(Y), written from the finished rows. The plan
+    (whole rows: this product has no column slices) and its scratch are the operand's cached ones. Raises on anything the library refuses
+    (masked epilogues, d % 4 != 0, d > 256)."""
+    _need_gpu(Xb, a.rowptr, out, out_bf16)
+    _bf16_rows(Xb, "spmm_bf16")
+    if Xb.shape[0] != a.n_cols:
+        raise RuntimeError("spmm_bf16: Xb has %d rows, operand has %d columns" % (Xb.shape[0], a.n_cols))
+    d = Xb.shape[1]
+    Y = out if out is not None else torch.empty(a.n_rows, d, dtype=torch.float32, device=Xb.device)
+    if out_bf16 is not None and _bf16_rows(out_bf16, "spmm_bf16").shape != Y.shape:
+        raise RuntimeError("spmm_bf16: out_bf16 is %s, the product is %s" % (tuple(out_bf16.shape), tuple(Y.shape)))
+    pl = plan if plan is not None else a.plan_for(d, whole_row=True)[1]
+    rp, ci = pl.csr_of(a)
+    _lib.call("llmrec_spmm_xbf16_f32", a.n_rows, a.n_cols, _p(rp), _p(ci), _p(a.val), _p(a.row_scale), _p(a.col_scale), _p(Xb), _ld(Xb),
+              _p(Y), _ld(Y), _p(out_bf16), _ld(out_bf16) if out_bf16 is not None else 0, d, _c.byref(pl.c_struct()), _p(pl.scratch(d, Xb.device)),
+              _c.byref(epilogue) if epilogue is not None else None, _stream())
+    return Y
+
+
 def spmm_multi(problems: Sequence[SpmmProblemC]) -> bool:
     """Up to LLMREC_SPMM_MAX_PROBLEMS independent products in ONE llmrec_spmm_multi_f32 launch on the current stream (results bit-identical
     to separate llmrec_spmm_f32 calls). False: the library refused the group (LLMREC_EUNSUPPORTED - e.g. the problems resolve to different
