@@ -59,65 +59,23 @@ def _ld(t: torch.Tensor) -> int:
 # ---------------------------------------------------------------------------------------------
 # R1: CSR operands
 # ---------------------------------------------------------------------------------------------
-class SpmmPlanC(_c.Structure):
-    """llmrec_spmm_plan_t"""
-    _fields_ = [("t_wave", _c.c_int32), ("t_block", _c.c_int32), ("segment", _c.c_int32),
-                ("n_wave_rows", _c.c_int32), ("wave_rows", _c.c_void_p), ("n_block_rows", _c.c_int32), ("block_rows", _c.c_void_p),
-                ("n_split_rows", _c.c_int32), ("split_rows", _c.c_void_p), ("split_seg_begin", _c.c_void_p),
-                ("n_segments", _c.c_int32), ("seg_split", _c.c_void_p), ("n_short_rows", _c.c_int32), ("slot_row", _c.c_void_p)]
+# The argument blocks of include/llmrec_hip.h, bound from the header itself (_lib.parse_structs): fields in the header's order, every pointer
+# a c_void_p (an int address, None, a ctypes array or addressof)
+SpmmPlanC = _lib.STRUCT["llmrec_spmm_plan_t"]
+SpmmEpilogueC = _lib.STRUCT["llmrec_spmm_epilogue_t"]
+SpmmProblemC = _lib.STRUCT["llmrec_spmm_problem_t"]              # the arguments of one llmrec_spmm_f32 call, for llmrec_spmm_multi_f32
+GuestSamplerC = _lib.STRUCT["llmrec_guest_sampler_t"]            # the arguments of llmrec_sample_batch_wide
+GuestPlanReachC = _lib.STRUCT["llmrec_guest_plan_reach_t"]       # the arguments of llmrec_bpr_scatter_plan_reach_mark
+GuestLossesC = _lib.STRUCT["llmrec_guest_losses_t"]              # the arguments of llmrec_bpr_multi_losses_assemble_f32
 
 
-class SpmmEpilogueC(_c.Structure):
-    """llmrec_spmm_epilogue_t"""
-    _fields_ = [("op", _c.c_int32), ("alpha", _c.c_float), ("Z", _c.c_void_p), ("ldz", _c.c_int64), ("S", _c.c_void_p), ("lds", _c.c_int64),
-                ("post_scale", _c.c_void_p), ("x_row_mask", _c.c_void_p), ("x_mask_active", _c.c_int32), ("y_row_flag", _c.c_void_p),
-                ("z_row_flag", _c.c_void_p), ("y_row_gate", _c.c_void_p), ("y_row_needed", _c.c_void_p), ("rows_listed_only", _c.c_int32),
-                ("x_mask_stamp", _c.c_void_p), ("mask_from_slice", _c.c_int32)]
-
-
-class SpmmProblemC(_c.Structure):
-    """llmrec_spmm_problem_t: the arguments of one llmrec_spmm_f32 call, for llmrec_spmm_multi_f32"""
-    _fields_ = [("n_rows", _c.c_int64), ("n_cols", _c.c_int64), ("rowptr", _c.c_void_p), ("colidx", _c.c_void_p), ("val", _c.c_void_p),
-                ("row_scale", _c.c_void_p), ("col_scale", _c.c_void_p), ("X", _c.c_void_p), ("ldx", _c.c_int64), ("Y", _c.c_void_p),
-                ("ldy", _c.c_int64), ("d", _c.c_int32), ("slice_width", _c.c_int32), ("plan", _c.c_void_p), ("partials", _c.c_void_p),
-                ("epilogue", _c.c_void_p)]
-
-
-class GuestSamplerC(_c.Structure):
-    """llmrec_guest_sampler_t: the arguments of llmrec_sample_batch_wide"""
-    _fields_ = [("seed", _c.c_uint64), ("step_dev", _c.c_void_p), ("n_exist_users", _c.c_int64), ("exist_users", _c.c_void_p),
-                ("n_items", _c.c_int64), ("train_rowptr", _c.c_void_p), ("train_colidx", _c.c_void_p), ("B_global", _c.c_int32),
-                ("slice_begin", _c.c_int32), ("B", _c.c_int32), ("n_aug", _c.c_int32), ("aug_pos", _c.c_void_p), ("aug_neg", _c.c_void_p),
-                ("users", _c.c_void_p), ("pos", _c.c_void_p), ("neg", _c.c_void_p), ("n_valid_dev", _c.c_void_p), ("ticket", _c.c_void_p)]
-
-
-class GuestPlanReachC(_c.Structure):
-    """llmrec_guest_plan_reach_t: the arguments of llmrec_bpr_scatter_plan_reach_mark"""
-    _fields_ = [("users", _c.c_void_p), ("pos", _c.c_void_p), ("neg", _c.c_void_p), ("B_max", _c.c_int32), ("n_valid_dev", _c.c_void_p),
-                ("plan", _c.c_void_p), ("n_users", _c.c_int64), ("n_items", _c.c_int64), ("item_rowptr", _c.c_void_p),
-                ("item_colidx", _c.c_void_p), ("flags", _c.c_void_p)]
-
-
-class GuestLossesC(_c.Structure):
-    """llmrec_guest_losses_t: the arguments of llmrec_bpr_multi_losses_assemble_f32"""
-    _fields_ = [("n_problems", _c.c_int32), ("B_max", _c.c_int32), ("n_valid_dev", _c.c_void_p), ("remember_rate", _c.c_double),
-                ("decay", _c.c_float), ("batch_size_flag", _c.c_float), ("out", _c.c_void_p), ("saved", _c.c_void_p),
-                ("w_mf_host", _c.c_void_p), ("sumsq_partial", _c.c_void_p), ("n_partial", _c.c_int32), ("feat_reg_coef", _c.c_float),
-                ("scal4", _c.c_void_p), ("running_sums3", _c.c_void_p)]
-
-
-class _SpmmGuestU(_c.Union):
-    _fields_ = [("sampler", GuestSamplerC), ("plan_reach", GuestPlanReachC), ("losses", GuestLossesC)]
-
-
-class SpmmGuestC(_c.Structure):
+class SpmmGuestC(_lib.STRUCT["llmrec_spmm_guest_t"]):
     """llmrec_spmm_guest_t: the tagged guest of llmrec_spmm_multi_guest_f32. keep: host arrays the descriptor points into."""
-    _fields_ = [("kind", _c.c_int32), ("u", _SpmmGuestU)]
     keep = None
 
 
-GUEST_SAMPLER, GUEST_PLAN_REACH, GUEST_LOSSES = 1, 2, 3
-EPI_NONE, EPI_SOFTMAX, EPI_SOFTMAX_BWD = 0, 1, 2
+GUEST_SAMPLER, GUEST_PLAN_REACH, GUEST_LOSSES = (CONST["LLMREC_SPMM_GUEST_" + k] for k in ("SAMPLER", "PLAN_REACH", "LOSSES"))
+EPI_NONE, EPI_SOFTMAX, EPI_SOFTMAX_BWD = (CONST["LLMREC_SPMM_EPI_" + k] for k in ("NONE", "SOFTMAX", "SOFTMAX_BWD"))
 SPMM_LATENCY_NNZ = 4_000_000      # below: the graph is L2-resident and a step is launch-bound (Netflix scale)
 
 
@@ -818,56 +776,14 @@ def bpr_scatter_plan(users, pos, neg, n_valid=None, out: Optional[torch.Tensor] 
     return out
 
 
-class BprProblem(_c.Structure):
-    """llmrec_bpr_problem_t"""
-    _fields_ = [("Eu", _c.c_void_p), ("ldu", _c.c_int64), ("Ei", _c.c_void_p), ("ldi", _c.c_int64),
-                ("dEu", _c.c_void_p), ("lddu", _c.c_int64), ("dEi", _c.c_void_p), ("lddi", _c.c_int64),
-                ("g_mf", _c.c_float), ("g_emb", _c.c_float)]
-
-
-class LinearProblem(_c.Structure):
-    """llmrec_linear_problem_t"""
-    _fields_ = [("X", _c.c_void_p), ("ldx", _c.c_int64), ("M", _c.c_int64), ("K", _c.c_int32),
-                ("W", _c.c_void_p), ("ldw", _c.c_int64), ("bias", _c.c_void_p), ("Y", _c.c_void_p), ("ldy", _c.c_int64),
-                ("bias_scale", _c.c_void_p)]
-
-
-class ZeroTensor(_c.Structure):
-    """llmrec_zero_tensor_t"""
-    _fields_ = [("p", _c.c_void_p), ("n", _c.c_int64)]
-
-
-class FuseFwdProblem(_c.Structure):
-    """llmrec_fuse_fwd_problem_t"""
-    _fields_ = [("rows", _c.c_int64), ("mean_scale", _c.c_float), ("n_mean", _c.c_int32), ("mean_terms", _c.c_void_p), ("mean_ld", _c.c_void_p),
-                ("n_norm", _c.c_int32), ("norm_terms", _c.c_void_p), ("norm_ld", _c.c_void_p), ("rates", _c.c_void_p),
-                ("out", _c.c_void_p), ("ldo", _c.c_int64)]
-
-
-class FuseBwdProblem(_c.Structure):
-    """llmrec_fuse_bwd_problem_t"""
-    _fields_ = [("rows", _c.c_int64), ("dOut", _c.c_void_p), ("lddo", _c.c_int64), ("n_norm", _c.c_int32), ("norm_terms", _c.c_void_p),
-                ("norm_ld", _c.c_void_p), ("rates", _c.c_void_p), ("d_terms", _c.c_void_p), ("d_ld", _c.c_void_p),
-                ("src_terms", _c.c_void_p), ("src_ld", _c.c_void_p), ("n_reg_terms", _c.c_int32), ("reg_two_coef", _c.c_float),
-                ("row_flags", _c.c_void_p), ("row_stamp", _c.c_void_p), ("zero_skip_from_term", _c.c_int32)]
-
-
-class WgradProblem(_c.Structure):
-    """llmrec_wgrad_problem_t"""
-    _fields_ = [("dY", _c.c_void_p), ("lddy", _c.c_int64), ("X", _c.c_void_p), ("ldx", _c.c_int64), ("M", _c.c_int64),
-                ("db_row_weight", _c.c_void_p), ("row_list", _c.c_void_p), ("n_rows", _c.c_void_p), ("rows_expected", _c.c_int64)]
-
-
-class WgradTarget(_c.Structure):
-    """llmrec_wgrad_target_t"""
-    _fields_ = [("n_problems", _c.c_int32), ("problems", _c.c_void_p), ("K", _c.c_int32), ("dW", _c.c_void_p), ("lddw", _c.c_int64),
-                ("db", _c.c_void_p), ("accumulate", _c.c_int32), ("block_budget", _c.c_int32)]
-
-
-class WgradUpdate(_c.Structure):
-    """llmrec_wgrad_update_t"""
-    _fields_ = [("W", _c.c_void_p), ("m_W", _c.c_void_p), ("v_W", _c.c_void_p), ("b", _c.c_void_p), ("m_b", _c.c_void_p), ("v_b", _c.c_void_p),
-                ("g_scale", _c.c_float)]
+BprProblem = _lib.STRUCT["llmrec_bpr_problem_t"]
+LinearProblem = _lib.STRUCT["llmrec_linear_problem_t"]
+ZeroTensor = _lib.STRUCT["llmrec_zero_tensor_t"]
+FuseFwdProblem = _lib.STRUCT["llmrec_fuse_fwd_problem_t"]
+FuseBwdProblem = _lib.STRUCT["llmrec_fuse_bwd_problem_t"]
+WgradProblem = _lib.STRUCT["llmrec_wgrad_problem_t"]
+WgradTarget = _lib.STRUCT["llmrec_wgrad_target_t"]
+WgradUpdate = _lib.STRUCT["llmrec_wgrad_update_t"]
 
 
 def _wgrad_targets(targets, block_budget: int = 0):
@@ -1115,15 +1031,8 @@ def sumsq(coef: float, Xs: Sequence[torch.Tensor]):
 # ---------------------------------------------------------------------------------------------
 # R8: AdamW
 # ---------------------------------------------------------------------------------------------
-class AdamwTensor(_c.Structure):
-    """llmrec_adamw_tensor_t"""
-    _fields_ = [("p", _c.c_void_p), ("g", _c.c_void_p), ("m", _c.c_void_p), ("v", _c.c_void_p), ("n", _c.c_int64), ("g_scale", _c.c_float),
-                ("g_out", _c.c_void_p)]
-
-
-class ZeroRowsJob(_c.Structure):
-    """llmrec_zero_rows_job_t"""
-    _fields_ = [("ids", _c.c_void_p), ("dst", _c.c_void_p), ("ldd", _c.c_int64), ("d", _c.c_int32)]
+AdamwTensor = _lib.STRUCT["llmrec_adamw_tensor_t"]
+ZeroRowsJob = _lib.STRUCT["llmrec_zero_rows_job_t"]
 
 
 class FusedAdamW:
@@ -1255,7 +1164,7 @@ class FusedAdamW:
 # ---------------------------------------------------------------------------------------------
 # R9/R10: scoring + top-K, R11: sampler
 # ---------------------------------------------------------------------------------------------
-TOPK_MODES = {"exact": 0, "prefilter": 1}
+TOPK_MODES = {"exact": CONST["LLMREC_TOPK_MODE_EXACT_SWEEP"], "prefilter": CONST["LLMREC_TOPK_MODE_PREFILTER"]}
 
 
 def topk_mode(mode=None, n_items: int = 0, d: int = 64, K: int = 50) -> int:
@@ -1332,7 +1241,7 @@ def score_topk(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, 
     if stats is not None:
         off = _lib.query("llmrec_score_topk_stats_offset", n, Ei.shape[0])
         stats["tiles"] = (n + 15) // 16
-        pre = topk_mode(mode, Ei.shape[0], Eu.shape[1], K) == 1 and K <= CONST["LLMREC_TOPK_PREFILTER_MAX_K"]
+        pre = topk_mode(mode, Ei.shape[0], Eu.shape[1], K) == TOPK_MODES["prefilter"] and K <= CONST["LLMREC_TOPK_PREFILTER_MAX_K"]
         stats["fallback_tiles"] = int(ws[off + 4:off + 8].view(torch.int32).item()) if pre else 0
         stats["drains"] = int(ws[off:off + 4].view(torch.int32).item()) if pre else None                # pool drains of the bf16 sweep, summed over its blocks
         stats["bitmap_rows"] = int(ws[off + 8:off + 12].view(torch.int32).item()) if pre else None     # long train rows swept as per-block bitmaps (bf16 mode's launch)

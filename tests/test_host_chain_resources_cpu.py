@@ -8,38 +8,20 @@ test_hosting_kernel_keeps_its_hosts_residency: against the kernel it hosts in, l
 per SIMD, no scratch, as many blocks per CU by LDS as the host, and registers that allow that residency: a SIMD's unified file holds 512
 registers per lane, architectural and accumulation registers together, so w resident waves may have 512 // w each (the capped build keeps
 some values in accumulation registers: 108 + 44)."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DENSE = os.path.join(os.path.dirname(HERE), "llmrec_amd", "csrc", "dense.hip")
+from tests._hipcc import needs_hipcc, resource_usage
+
 HOSTING = "_ZN6llmrec37linear_fwd_grouped_bf16x3_host_kernelENS_11LinearGroupEiiNS_8SpmmArgsE"
 HOST = "_ZN6llmrec32linear_fwd_grouped_bf16x3_kernelILi4ELi2ELi3EEEvNS_11LinearGroupEi"
 LDS_PER_CU = 160 * 1024
-KEYS = ("VGPRs", "AGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "VGPRs Spill", "LDS Size [bytes/block]")
 
-pytestmark = pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+pytestmark = needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def usage():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", os.devnull, DENSE], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); res[cur] = {}
-        for key in KEYS:
-            m = re.search(r"\s" + re.escape(key) + r": (\d+)", line)
-            if m and cur:
-                res[cur].setdefault(key, int(m.group(1)))
+    res = resource_usage("dense.hip")
     assert HOSTING in res and HOST in res, sorted(k for k in res if "grouped_bf16x3" in k)
     print("[host chain resources] hosting %s\n[host chain resources] host    %s" % (res[HOSTING], res[HOST]))
     return res

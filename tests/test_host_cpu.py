@@ -295,11 +295,9 @@ def test_py_sample_replay_is_verified_on_each_branch_of_random_sample(monkeypatc
 def test_host_helper_library_exports_what_its_header_declares():
     """include/llmrec_host.h <-> llmrec_amd/lib/libllmrec_host.so (plain C, gcc): both entry points load."""
     import ctypes
-    import re
     from llmrec_amd import build as _build
     so = _build.build_host(force=False)
-    hdr = open(os.path.join(os.path.dirname(_lib.HEADER), "llmrec_host.h")).read()
-    names = re.findall(r"\b(llmrec_host_\w+)\s*\(", hdr)
+    names = list(_lib.parse_header(_lib.HOST_HEADER))               # the call utility/load_data.py binds the library with
     assert set(names) == {"llmrec_host_draw_items", "llmrec_host_py_sample"}
     lib = ctypes.CDLL(so)
     for n in names:

@@ -2,39 +2,16 @@
 kernel-resource-usage remarks for the six .hip files. A spill in one of the sweeps or GEMMs costs tens of per cent and is silent otherwise
 (the register allocator of this toolchain is sensitive to small source changes - profiles/experiments/r05_topk.md)."""
 import os
-import re
-import shutil
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "llmrec_amd", "csrc")
+from tests._hipcc import needs_hipcc, resource_usage
 
 
-def _usage(src):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", os.devnull, os.path.join(CSRC, src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); out[cur] = {}
-        for key in ("ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "Occupancy [waves/SIMD]", "VGPRs"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and cur:
-                out[cur].setdefault(key, int(m.group(1)))
-    return src, out
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+@needs_hipcc
 def test_no_hand_written_kernel_uses_scratch():
     from llmrec_amd.build import SOURCES
     with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
-        res = dict(ex.map(_usage, SOURCES))
+        res = dict(zip(SOURCES, ex.map(resource_usage, SOURCES)))
     n = 0
     for src, kernels in res.items():
         assert kernels, src

@@ -1,76 +1,19 @@
-"""CPU: the guest launch (llmrec_spmm_multi_guest_f32) - the ctypes mirrors of llmrec_spmm_guest_t and its three members have the C
-layout; every guest instance keeps the waves per SIMD of its host spmm_kernel instance without scratch, and its LDS leaves room for the
-blocks that occupancy allows (hipcc's resource remarks); the entry point checks a guest like the guest's own entry point, before any
-launch. (The call sequence of a guest-path step needs a device: tests/test_gpu_spmm_guests.py.)"""
+"""CPU: the guest launch (llmrec_spmm_multi_guest_f32) - every guest instance keeps the waves per SIMD of its host spmm_kernel instance
+without scratch, and its LDS leaves room for the blocks that occupancy allows (hipcc's resource remarks); the entry point checks a guest
+like the guest's own entry point, before any launch. (The call sequence of a guest-path step needs a device:
+tests/test_gpu_spmm_guests.py; the layout of llmrec_spmm_guest_t and its members: tests/test_abi_layout_cpu.py.)"""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 from llmrec_amd import _lib, ops
+from tests._hipcc import needs_hipcc, resource_usage
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPMM = os.path.join(os.path.dirname(HERE), "llmrec_amd", "csrc", "spmm.hip")
 FAKE = 0x10000          # a 16-byte aligned "device" address: argument checks never dereference device pointers
-MEMBERS = {"llmrec_guest_sampler_t": ops.GuestSamplerC, "llmrec_guest_plan_reach_t": ops.GuestPlanReachC,
-           "llmrec_guest_losses_t": ops.GuestLossesC}
 
 
-def _c_fields(text, typename):
-    end = re.search(r"\}\s*%s\s*;" % typename, text)
-    assert end, typename
-    body = text[text.index("{", text.rfind("typedef struct", 0, end.start())) + 1:end.start()]
-    body = re.sub(r"/\*.*?\*/", " ", body, flags=re.S)
-    return [re.findall(r"\w+", part)[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
-
-
-def test_guest_struct_layouts(tmp_path):
-    text = open(_lib.HEADER).read()
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % _lib.HEADER, "int main(void) {"]
-    want = []
-    for typename, mirror in MEMBERS.items():
-        names = _c_fields(text, typename)
-        assert [f[0] for f in mirror._fields_] == names, typename
-        src.append('printf("%%zu", sizeof(%s));' % typename)
-        src += ['printf(" %%zu", offsetof(%s, %s));' % (typename, n) for n in names]
-        src.append('printf("\\n");')
-        want.append([C.sizeof(mirror)] + [getattr(mirror, n).offset for n in names])
-    src.append('printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(llmrec_spmm_guest_t), offsetof(llmrec_spmm_guest_t, kind), '
-               'offsetof(llmrec_spmm_guest_t, u), offsetof(llmrec_spmm_guest_t, u.sampler), offsetof(llmrec_spmm_guest_t, u.plan_reach), '
-               'offsetof(llmrec_spmm_guest_t, u.losses));')
-    G = ops.SpmmGuestC
-    want.append([C.sizeof(G), G.kind.offset, G.u.offset] + [G.u.offset + getattr(ops._SpmmGuestU, n).offset for n in ("sampler", "plan_reach", "losses")])
-    src.append("return 0; }")
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-o", str(exe), str(c)], check=True)
-    got = [[int(x) for x in line.split()] for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()]
-    assert got == want
-    assert (ops.GUEST_SAMPLER, ops.GUEST_PLAN_REACH, ops.GUEST_LOSSES) == tuple(
-        _lib.CONST["LLMREC_SPMM_GUEST_" + k] for k in ("SAMPLER", "PLAN_REACH", "LOSSES"))
-    assert _lib.CONST["LLMREC_ABI_VERSION"] == 8
-    assert len(_lib.parse_header()["llmrec_spmm_multi_guest_f32"][1]) == 4
-
-
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+@needs_hipcc
 def test_guest_kernels_keep_their_hosts_occupancy():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", os.devnull, SPMM], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); res[cur] = {}
-        for key in ("VGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and cur:
-                res[cur].setdefault(key, int(m.group(1)))
+    res = resource_usage("spmm.hip")
     host = lambda w: res["_ZN6llmrec11spmm_kernelILi16ELi1ELi4ELb%dELb0EEEvNS_8SpmmArgsE" % w]
     assert host(0)["Occupancy [waves/SIMD]"] == 7 and host(1)["Occupancy [waves/SIMD]"] == 5
     # _ZN6llmrec23spmm_multi_guest_kernelILb0ENS_11SamplerArgsEEEvNS_14SpmmMultiGuestIT0_EE

@@ -3,35 +3,17 @@ each keep the 5 waves per SIMD of their host (the weighted float4 16-lane spmm_k
 the LDS room a guest instance must (hipcc's resource remarks); no other instance of them is compiled; the entry points check the new
 fields and refuse what is not compiled before any launch."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 from llmrec_amd import _lib, ops
+from tests._hipcc import needs_hipcc, resource_usage
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SPMM = os.path.join(os.path.dirname(HERE), "llmrec_amd", "csrc", "spmm.hip")
 FAKE = 0x10000          # a 16-byte aligned "device" address: argument checks never dereference device pointers
 
 
-@pytest.mark.skipif(not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")), reason="hipcc not available")
+@needs_hipcc
 def test_slice_masked_kernels_keep_their_hosts_occupancy():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-                        "-o", os.devnull, SPMM], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1); res[cur] = {}
-        for key in ("VGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and cur:
-                res[cur].setdefault(key, int(m.group(1)))
+    res = resource_usage("spmm.hip")
     host = res["_ZN6llmrec11spmm_kernelILi16ELi1ELi4ELb1ELb0EEEvNS_8SpmmArgsE"]
     assert host["Occupancy [waves/SIMD]"] == 5
     masked = {n: u for n, u in res.items() if re.match(r"_ZN6llmrec\d+spmm_smask_", n)}

@@ -236,14 +236,13 @@ class Data(object):
             try:
                 import ctypes
                 import os
-                so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llmrec_amd", "lib", "libllmrec_host.so")
+                from llmrec_amd import _lib
+                so = os.path.join(_lib.HERE, "lib", "libllmrec_host.so")
                 if os.path.exists(so):
                     lib = ctypes.CDLL(so)
-                    lib.llmrec_host_draw_items.restype = ctypes.c_int64
-                    lib.llmrec_host_draw_items.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-                    lib.llmrec_host_py_sample.restype = ctypes.c_int32
-                    lib.llmrec_host_py_sample.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+                    for name, (restype, argtypes, _) in _lib.parse_header(_lib.HOST_HEADER).items():
+                        fn = getattr(lib, name)
+                        fn.restype, fn.argtypes = restype, argtypes
                     ptr = np.zeros(self.n_users + 1, dtype=np.int64)
                     for u_, items in self.train_items.items():
                         ptr[u_ + 1] = len(items)
