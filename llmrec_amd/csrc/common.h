@@ -76,6 +76,39 @@ __device__ __forceinline__ float group_max(float v) {
     for (int off = WIDTH / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
     return v;
 }
+
+// --- primitives that more than one file must spell the same way (each exists once, here) ---
+typedef float f32x4 __attribute__((ext_vector_type(4)));      // an MFMA accumulator
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));    // a bf16 MFMA operand
+
+// elements [k, k+4) of a row of length K; zero beyond K
+__device__ __forceinline__ float4 load4_guard(const float* row, int k, int K, bool vec_ok) {
+    if (vec_ok && k + 3 < K) return *reinterpret_cast<const float4*>(row + k);
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < K) r.x = row[k];
+    if (k + 1 < K) r.y = row[k + 1];
+    if (k + 2 < K) r.z = row[k + 2];
+    if (k + 3 < K) r.w = row[k + 3];
+    return r;
+}
+__device__ __forceinline__ float comp(const float4& v, int s) { return s == 0 ? v.x : (s == 1 ? v.y : (s == 2 ? v.z : v.w)); }
+
+__device__ __forceinline__ f32x4 mfma_bf16(const uint4& a, const uint4& b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// high halves of e0 (-> low half of the result) and e1 (-> high half) in one v_perm_b32: no masking needed
+__device__ __forceinline__ uint32_t pack_hi16(uint32_t e0, uint32_t e1) { return __builtin_amdgcn_perm(e1, e0, 0x07060302u); }
+
+// fp32 -> bf16, round to nearest even, as the high half of a word (low 16 bits zero): of a FINITE float ...
+__device__ __forceinline__ uint32_t rn_bf16_bits_finite(float x) {
+    const uint32_t b = __float_as_uint(x);
+    return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
+}
+// ... and of any float: a NaN stays a quiet NaN
+__device__ __forceinline__ uint32_t rn_bf16_bits(float x) {
+    if ((__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u) return 0x7fc00000u;
+    return rn_bf16_bits_finite(x);
+}
 #endif
 
 }  // namespace llmrec

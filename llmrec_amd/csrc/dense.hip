@@ -15,24 +15,12 @@
 //   wgrad   : lane l holds dY[m][4*(l&15) + q] / X[m][k0 + 4*(l&15) + q] with m = m0 + (l>>4) + 4s';
 //             component q selects one of four INTERLEAVED 16-wide tiles (n = 4 i + q, k = k0 + 4 j + q).
 #include "common.h"
+#include "adamw.h"
 #include "spmm_body.h"
 
 namespace llmrec {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 load4_guard(const float* row, int k, int K, bool vec_ok) {
-    // elements [k, k+4) of a row of length K; zero beyond K
-    if (vec_ok && k + 3 < K) return *reinterpret_cast<const float4*>(row + k);
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < K) r.x = row[k];
-    if (k + 1 < K) r.y = row[k + 1];
-    if (k + 2 < K) r.z = row[k + 2];
-    if (k + 3 < K) r.w = row[k + 3];
-    return r;
-}
-
-// Branch-free variant for 16-byte aligned rows with K % 4 == 0: the address is clamped into the row
+// Branch-free variant of common.h's load4_guard for 16-byte aligned rows with K % 4 == 0: the address is clamped into the row
 // and the value zeroed by a select. (A branch around a load makes hipcc fall back to
 // s_waitcnt vmcnt(0) inside the k-loop, which serialises the whole software pipeline.)
 __device__ __forceinline__ float4 load4_fast(const float* row, int k, int K) {
@@ -61,10 +49,6 @@ __device__ __forceinline__ float4 load4_global(global_cptr base, uint32_t byte_o
     typedef const raw4 __attribute__((address_space(1))) * graw4;
     const raw4 v = *(graw4)(base + byte_off);
     return make_float4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ float comp(const float4& v, int s) {
-    return s == 0 ? v.x : (s == 1 ? v.y : (s == 2 ? v.z : v.w));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -339,8 +323,6 @@ __global__ __launch_bounds__(256, 3) void linear_fwd_grouped_kernel(LinearGroup 
 // X is split in registers on the fly (6 integer/float VALU ops per element), W when it is staged
 // into LDS. A/B operand = 8 consecutive k per lane (lane l: row l&15, k = 8 (l>>4) + j).
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 struct Split3 { uint32_t h, m, l; };                       // each: a bf16 value in the HIGH 16 bits (l: low half not cleared)
 __device__ __forceinline__ Split3 split3(float x) {
     Split3 r;
@@ -351,9 +333,6 @@ __device__ __forceinline__ Split3 split3(float x) {
     r.l = __float_as_uint(r2);                             // the pack below keeps only its high half
     return r;
 }
-// high halves of e0 (-> low half of the result) and e1 (-> high half) in one v_perm_b32: no masking needed
-__device__ __forceinline__ uint32_t pack_hi16(uint32_t e0, uint32_t e1) { return __builtin_amdgcn_perm(e1, e0, 0x07060302u); }
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // two register-adjacent floats -> their packed (hi, mid, lo) bf16 pairs: 2 + 2 masks, 2 packed subtractions, 3 v_perm_b32
@@ -403,11 +382,6 @@ __device__ __forceinline__ void split32(const float4 (&v)[8], uint4 (&H)[4], uin
         L[c] = make_uint4(pack_hi16(l[0][c], l[1][c]), pack_hi16(l[2][c], l[3][c]), pack_hi16(l[4][c], l[5][c]), pack_hi16(l[6][c], l[7][c]));
     }
 }
-
-__device__ __forceinline__ f32x4 mfma_bf16(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 
 constexpr int GB_WS = 40;              // LDS row stride of one bf16 W tile in 2-byte units (32 k + 8 pad = 80 B)
 
@@ -678,6 +652,14 @@ struct WgradGroup {
     int32_t n_problems;
 };
 
+// column sums of dY held per row group (lq = lane >> 4): the wave's four groups combined in a fixed order, every lane gets the sum
+__device__ __forceinline__ void sum_row_groups(float4& dbs) {
+    dbs.x += __shfl_xor(dbs.x, 16, 64); dbs.y += __shfl_xor(dbs.y, 16, 64);
+    dbs.z += __shfl_xor(dbs.z, 16, 64); dbs.w += __shfl_xor(dbs.w, 16, 64);
+    dbs.x += __shfl_xor(dbs.x, 32, 64); dbs.y += __shfl_xor(dbs.y, 32, 64);
+    dbs.z += __shfl_xor(dbs.z, 32, 64); dbs.w += __shfl_xor(dbs.w, 32, 64);
+}
+
 // One wave = (slab = chunk of MC rows of one problem, 64-wide k slab, 64-wide n block).
 // Three register stages rotate STATICALLY (the loop is unrolled by 3), so a tile's loads have two
 // full MFMA stages (2 x 2048 cycles) to land before they are consumed.
@@ -789,10 +771,7 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void linear_wgrad_kernel(WgradGr
         }
     if (kslab == 0 && partial_db) {
         // column sums of dY over this slab: combine the 4 row groups (lq) in a fixed order
-        dbs.x += __shfl_xor(dbs.x, 16, 64); dbs.y += __shfl_xor(dbs.y, 16, 64);
-        dbs.z += __shfl_xor(dbs.z, 16, 64); dbs.w += __shfl_xor(dbs.w, 16, 64);
-        dbs.x += __shfl_xor(dbs.x, 32, 64); dbs.y += __shfl_xor(dbs.y, 32, 64);
-        dbs.z += __shfl_xor(dbs.z, 32, 64); dbs.w += __shfl_xor(dbs.w, 32, 64);
+        sum_row_groups(dbs);
         if (lq == 0) {
             float* pd = partial_db + (int64_t)slab * N;
             if (n_base + 0 < N) pd[n_base + 0] = dbs.x;
@@ -906,10 +885,7 @@ __device__ __forceinline__ void wgrad_bf16x3_body(const WgradGroup& g, int N, in
             if (m_full + 4 * j + lq >= m_end) a0[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         mma_tile(a0, b0);
     }
-    dbs.x += __shfl_xor(dbs.x, 16, 64); dbs.y += __shfl_xor(dbs.y, 16, 64);
-    dbs.z += __shfl_xor(dbs.z, 16, 64); dbs.w += __shfl_xor(dbs.w, 16, 64);
-    dbs.x += __shfl_xor(dbs.x, 32, 64); dbs.y += __shfl_xor(dbs.y, 32, 64);
-    dbs.z += __shfl_xor(dbs.z, 32, 64); dbs.w += __shfl_xor(dbs.w, 32, 64);
+    sum_row_groups(dbs);
     if (wave > 0) {                                               // tile element (q, p, r) of lane l at [(q * 4 + p) * 4 + r][l]: conflict-free
         float* rw = red[wave - 1];
 #pragma unroll
@@ -1279,7 +1255,21 @@ struct ReduceUpdate {
     const float* state;
     float decay_mul, b1, b2, eps;
 };
-// reduce_chunks_kernel for every target of a multi-target launch (same chunk order, same four-way summation)
+// one element of a slab reduction: partial[chunk][e] over the chunks in ascending order, as four interleaved sums (deterministic)
+__device__ __forceinline__ float sum_chunks(const float* __restrict__ src, int64_t stride, int64_t n_chunks) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int64_t c = 0;
+    for (; c + 4 <= n_chunks; c += 4) {                          // 4 independent loads in flight
+        s0 += src[c * stride];
+        s1 += src[(c + 1) * stride];
+        s2 += src[(c + 2) * stride];
+        s3 += src[(c + 3) * stride];
+    }
+    for (; c < n_chunks; ++c) s0 += src[c * stride];
+    return (s0 + s1) + (s2 + s3);
+}
+
+// reduce_chunks_kernel for every target of a multi-target launch (sum_chunks for both)
 template <bool UPDATE>
 __global__ void reduce_chunks_multi_kernel(ReduceMulti m, ReduceUpdate u) {
     int t = 0;
@@ -1291,35 +1281,20 @@ __global__ void reduce_chunks_multi_kernel(ReduceMulti m, ReduceUpdate u) {
     const bool second = e >= n_elem;
     const float* src = second ? m.partial_b[t] + (e - n_elem) : m.partial[t] + e;
     const int64_t stride = second ? n_b : n_elem;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int64_t c = 0;
-    for (; c + 4 <= n_chunks; c += 4) {
-        s0 += src[c * stride];
-        s1 += src[(c + 1) * stride];
-        s2 += src[(c + 2) * stride];
-        s3 += src[(c + 3) * stride];
-    }
-    for (; c < n_chunks; ++c) s0 += src[c * stride];
-    const float s = (s0 + s1) + (s2 + s3);
+    const float s = sum_chunks(src, stride, n_chunks);
     float* o;
     if (second) o = m.out_b[t] + (e - n_elem);
     else { const int64_t r = e / m.row_len[t], col = e % m.row_len[t]; o = m.out[t] + r * m.ld_out[t] + col; }
     const float g = m.accumulate[t] ? (*o + s) : s;
     *o = g;
-    if (UPDATE) {                                                // adamw_multi_kernel's arithmetic (rowops.hip) on this element
+    if (UPDATE) {                                                // this element's AdamW update (adamw.h: what adamw_multi_kernel runs)
         const int64_t i = second ? e - n_elem : e;               // (W contiguous: ld_out == row_len)
         float* __restrict__ p = (second ? u.pb[t] : u.p[t]) + i;
         float* __restrict__ mo = (second ? u.mb[t] : u.mo[t]) + i;
         float* __restrict__ vo = (second ? u.vb[t] : u.vo[t]) + i;
-        const float gs = u.gscale[t];
-        const float step_size = u.state[1], bc2s = u.state[2];
-        const float w1 = 1.0f - u.b1, w2 = 1.0f - u.b2;
-        const float gi = gs == 1.0f ? g : gs * g;
-        float pi = *p * u.decay_mul;
-        const float mi = *mo + w1 * (gi - *mo);
-        const float vi = fmaf(w2 * gi, gi, *vo * u.b2);
-        const float denom = sqrtf(vi) / bc2s + u.eps;
-        pi = pi - step_size * (mi / denom);
+        const AdamwConsts c = adamw_consts(u.state, u.decay_mul, u.b1, u.b2, u.eps);
+        float pi = *p, mi = *mo, vi = *vo;
+        adamw_element(c, adamw_grad(u.gscale[t], g), pi, mi, vi);
         *p = pi; *mo = mi; *vo = vi;
     }
 }
@@ -1333,16 +1308,7 @@ __global__ void reduce_chunks_kernel(int64_t n_elem, int64_t n_chunks, const flo
         const bool second = e >= n_elem;
         const float* src = second ? partial_b + (e - n_elem) : partial + e;
         const int64_t stride = second ? n_b : n_elem;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int64_t c = 0;
-        for (; c + 4 <= n_chunks; c += 4) {                      // 4 independent loads in flight
-            s0 += src[c * stride];
-            s1 += src[(c + 1) * stride];
-            s2 += src[(c + 2) * stride];
-            s3 += src[(c + 3) * stride];
-        }
-        for (; c < n_chunks; ++c) s0 += src[c * stride];
-        const float s = (s0 + s1) + (s2 + s3);
+        const float s = sum_chunks(src, stride, n_chunks);
         float* o;
         if (second) o = out_b + (e - n_elem);
         else { const int64_t r = e / row_len, col = e % row_len; o = out + r * ld_out + col; }
@@ -1770,7 +1736,7 @@ int llmrec_linear_wgrad_multi_adamw_bf16x3(int32_t n_targets, const llmrec_wgrad
         u.p[i] = upd[i].W; u.mo[i] = upd[i].m_W; u.vo[i] = upd[i].v_W; u.pb[i] = upd[i].b; u.mb[i] = upd[i].m_b; u.vb[i] = upd[i].v_b;
         u.gscale[i] = upd[i].g_scale;
     }
-    u.state = state3; u.decay_mul = (float)(1.0 - (double)lr * (double)weight_decay); u.b1 = beta1; u.b2 = beta2; u.eps = eps;
+    u.state = state3; u.decay_mul = adamw_decay_mul(lr, weight_decay); u.b1 = beta1; u.b2 = beta2; u.eps = eps;
     return linear_wgrad_multi_impl(n_targets, t, N, workspace, workspace_bytes, &u, stream_);
 }
 

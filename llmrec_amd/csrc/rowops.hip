@@ -4,6 +4,7 @@
 // Replaces nn.Softmax / torch.mean(torch.stack) / F.normalize + scaled adds (reference
 // Models.py:176-177,185-197), (x**2).sum() (main.py:151-156) and AdamW.step (main.py:100-104,278).
 #include "common.h"
+#include "adamw.h"
 #include "reach.h"
 #include <type_traits>
 
@@ -409,15 +410,10 @@ __global__ void timestamp_kernel(uint64_t* slot) { *slot = wall_clock64(); }
 __global__ __launch_bounds__(256) void adamw_kernel(int64_t n, float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     const float* __restrict__ state, float decay_mul, float b1, float b2, float eps) {
-    const float step_size = state[1], bc2s = state[2];
-    const float w1 = 1.0f - b1, w2 = 1.0f - b2;
+    const AdamwConsts c = adamw_consts(state, decay_mul, b1, b2, eps);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gi = g[i];
-        float pi = p[i] * decay_mul;                                   // p.mul_(1 - lr * wd)
-        const float mi = m[i] + w1 * (gi - m[i]);                      // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = fmaf(w2 * gi, gi, v[i] * b2);                 // mul_(beta2).addcmul_(g, g, 1 - beta2)
-        const float denom = sqrtf(vi) / bc2s + eps;
-        pi = pi - step_size * (mi / denom);                            // addcdiv_(exp_avg, denom, -step_size)
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(c, g[i], pi, mi, vi);
         p[i] = pi; m[i] = mi; v[i] = vi;
     }
 }
@@ -446,23 +442,6 @@ struct ZeroRowJobs {
     const int32_t* n_valid;
 };
 
-struct AdamwConsts { float decay_mul, b2, eps, step_size, bc2s, w1, w2; };
-
-// THE update of one element of a multi-tensor launch (gi = the gradient the update uses): the scalar and the float4 path of adamw_block
-// both call it. Contraction is OFF inside: the compiler fuses a * b + c into an fma where it pays - for the packed two-float
-// instructions the float4 path is compiled to, not for the scalar ones of adamw_kernel and of the weight-gradient reduction's update
-// (dense.hip), which round the product first. Only the fmaf below is fused, everywhere.
-__device__ __forceinline__ void adamw_element(const AdamwConsts& c, float gi, float& p, float& m, float& v) {
-#pragma clang fp contract(off)
-    float pi = p * c.decay_mul;
-    const float mi = m + c.w1 * (gi - m);
-    const float vi = fmaf(c.w2 * gi, gi, v * c.b2);
-    const float denom = sqrtf(vi) / c.bc2s + c.eps;
-    pi = pi - c.step_size * (mi / denom);
-    p = pi; m = mi; v = vi;
-}
-__device__ __forceinline__ float adamw_grad(float gs, float g) { return gs == 1.0f ? g : gs * g; }
-
 // block vb of a multi-tensor update -> (tensor, ADAMW_PER_BLOCK-element chunk). A chunk that lies inside the tensor and whose five pointers
 // are 16-byte aligned moves as float4 - every load of the thread issued before the first arithmetic; the tensor's tail chunk and
 // misaligned views take the 4-byte loop.
@@ -475,10 +454,7 @@ __device__ __forceinline__ void adamw_block(int vb, const AdamwTensors& t, const
     const int64_t n = t.n[k];
     const float gs = t.gscale[k];
     float* __restrict__ go = t.gout[k];
-    AdamwConsts c;
-    c.decay_mul = decay_mul; c.b2 = b2; c.eps = eps;
-    c.step_size = state[1]; c.bc2s = state[2];
-    c.w1 = 1.0f - b1; c.w2 = 1.0f - b2;
+    const AdamwConsts c = adamw_consts(state, decay_mul, b1, b2, eps);
     const bool wide = base + ADAMW_PER_BLOCK <= n &&
                       (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)go) & 15) == 0;
     if (wide) {                                                        // (uniform over the block)
@@ -1185,7 +1161,7 @@ int llmrec_adamw_f32(int64_t n, float* p, const float* g, float* m, float* v, co
     LLMREC_CHECK_ARG(n >= 0 && state3, "adamw: bad argument");
     if (n == 0) return LLMREC_OK;
     LLMREC_CHECK_ARG(p && g && m && v, "adamw: null pointer");
-    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    const float decay_mul = adamw_decay_mul(lr, weight_decay);
     adamw_kernel<<<grid_for(n, 256 * 4), 256, 0, (hipStream_t)stream_>>>(n, p, g, m, v, state3, decay_mul, beta1, beta2, eps);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
@@ -1214,7 +1190,7 @@ int llmrec_adamw_multi_f32(int32_t n_tensors, const llmrec_adamw_tensor_t* tenso
     int blocks = 0;
     if (int rc = fill_adamw(t, n_tensors, tensors_host, state3, blocks)) return rc;
     if (blocks == 0) return LLMREC_OK;
-    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    const float decay_mul = adamw_decay_mul(lr, weight_decay);
     adamw_multi_kernel<<<blocks, 256, 0, (hipStream_t)stream_>>>(t, state3, decay_mul, beta1, beta2, eps);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
@@ -1239,7 +1215,7 @@ int llmrec_adamw_multi_zero_rows_f32(int32_t n_tensors, const llmrec_adamw_tenso
     }
     const int total = blocks + n_jobs * z.blocks_per_job;
     if (total == 0) return LLMREC_OK;
-    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    const float decay_mul = adamw_decay_mul(lr, weight_decay);
     adamw_multi_zero_rows_kernel<<<total, 256, 0, (hipStream_t)stream_>>>(t, state3, decay_mul, beta1, beta2, eps, z);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
@@ -1278,7 +1254,7 @@ int llmrec_step_rows_group_f32(int32_t n_fuse_problems, const llmrec_fuse_bwd_pr
     }
     const int total = fuse_blocks + adamw_blocks + sm_blocks;
     if (total == 0) return LLMREC_OK;
-    const float decay_mul = (float)(1.0 - (double)lr * (double)weight_decay);
+    const float decay_mul = adamw_decay_mul(lr, weight_decay);
     step_rows_group_kernel<<<total, 256, 0, (hipStream_t)stream_>>>(d, m, t, state3, decay_mul, beta1, beta2, eps, s, fuse_blocks,
                                                                     fuse_blocks + adamw_blocks);
     LLMREC_LAUNCH_CHECK();

@@ -9,13 +9,6 @@ namespace llmrec {
 
 constexpr int UNROLL = 8;
 
-// fp32 -> bf16, round to nearest even, as the high half of a word (the idiom of topk.hip's tk_rn_bf16_bits); a NaN stays a quiet NaN
-__device__ __forceinline__ uint32_t rn_bf16_bits(float x) {
-    const uint32_t b = __float_as_uint(x);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc00000u;
-    return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
-}
-
 template <int VEC> struct Vec;
 template <> struct Vec<4> {
     float4 v;

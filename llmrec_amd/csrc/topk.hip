@@ -31,19 +31,6 @@
 
 namespace llmrec {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ld4g(const float* row, int k, int K, bool vec_ok) {
-    if (vec_ok && k + 3 < K) return *reinterpret_cast<const float4*>(row + k);
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < K) r.x = row[k];
-    if (k + 1 < K) r.y = row[k + 1];
-    if (k + 2 < K) r.z = row[k + 2];
-    if (k + 3 < K) r.w = row[k + 3];
-    return r;
-}
-__device__ __forceinline__ float cmp4(const float4& v, int s) { return s == 0 ? v.x : (s == 1 ? v.y : (s == 2 ? v.z : v.w)); }
-
 struct TopkArgs {
     int n_query;
     const int64_t* query_users;
@@ -86,7 +73,7 @@ __device__ __forceinline__ void load_items(const TopkArgs& a, int64_t base, int 
         if (item > a.n_items - 1) item = a.n_items - 1;
         const float* row = a.Ei + item * a.ldi;
 #pragma unroll
-        for (int c = 0; c < DK; ++c) b[n][c] = ld4g(row, 16 * c + 4 * lq, a.d, a.vec_ok);
+        for (int c = 0; c < DK; ++c) b[n][c] = load4_guard(row, 16 * c + 4 * lq, a.d, a.vec_ok);
     }
 }
 
@@ -312,7 +299,7 @@ __global__ __launch_bounds__(256) void scores_kernel(TopkArgs a) {
     const int64_t user_a = a.query_users[qa];
     float4 ua[DK];
 #pragma unroll
-    for (int c = 0; c < DK; ++c) ua[c] = ld4g(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
+    for (int c = 0; c < DK; ++c) ua[c] = load4_guard(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
     const int64_t tiles_total = (a.n_items + 63) / 64;
     for (int64_t t = w; t < tiles_total; t += 4) {
         const int64_t base = t * 64;
@@ -327,7 +314,7 @@ __global__ __launch_bounds__(256) void scores_kernel(TopkArgs a) {
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int n = 0; n < 4; ++n)
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(cmp4(ua[c], s), cmp4(b[n][c], s), acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(ua[c], s), comp(b[n][c], s), acc[n], 0, 0, 0);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
 #pragma unroll
@@ -352,13 +339,13 @@ __global__ __launch_bounds__(256) void topk_pack_items_kernel(TopkArgs a, int DK
     const int64_t tn = f / DK;                                     // tile * 2 + n
     int64_t item = tn * 16 + li;
     if (item > a.n_items - 1) item = a.n_items - 1;                // the partial last tile repeats the last item (masked by the range check)
-    packed[v] = ld4g(a.Ei + item * a.ldi, 16 * c + 4 * lq, a.d, a.vec_ok);
+    packed[v] = load4_guard(a.Ei + item * a.ldi, 16 * c + 4 * lq, a.d, a.vec_ok);
 }
 
 // FAST: d == 16 DK and 16-byte aligned rows - plain float4 loads. (A branch around a global load makes
 // hipcc wait for each load before issuing the next: the guarded loader costs ~8 exposed L2 latencies per round.)
 // PACKED: the item tiles come from a.packed (fragment order, one contiguous KB per load instruction). The user rows are still
-// read from Eu: <DK, false, true> is the packed sweep of a ragged d or an unaligned table (its 16 user rows through ld4g, once).
+// read from Eu: <DK, false, true> is the packed sweep of a ragged d or an unaligned table (its 16 user rows through load4_guard, once).
 template <int DK, bool FAST, bool PACKED>
 __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(TopkArgs a) {
     __shared__ float buf_s[4][16][TK_CAP];
@@ -395,7 +382,7 @@ __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(Topk
 #pragma unroll
     for (int c = 0; c < DK; ++c)
         ua[c] = FAST ? *reinterpret_cast<const float4*>(a.Eu + user_a * a.ldu + 16 * c + 4 * lq)
-                     : ld4g(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
+                     : load4_guard(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
 
     const int64_t tiles_all = (a.n_items + TK_TILE - 1) / TK_TILE;
     const int64_t part_begin = tiles_all * part / n_parts, tiles_total = tiles_all * (part + 1) / n_parts;   // this block's item tiles
@@ -455,8 +442,8 @@ __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(Topk
         }
 #pragma unroll
         for (int c = 0; c < DK; ++c) {
-            b[0][c] = FAST ? *reinterpret_cast<const float4*>(r0 + 16 * c + 4 * lq) : ld4g(r0, 16 * c + 4 * lq, a.d, a.vec_ok);
-            b[1][c] = FAST ? *reinterpret_cast<const float4*>(r1 + 16 * c + 4 * lq) : ld4g(r1, 16 * c + 4 * lq, a.d, a.vec_ok);
+            b[0][c] = FAST ? *reinterpret_cast<const float4*>(r0 + 16 * c + 4 * lq) : load4_guard(r0, 16 * c + 4 * lq, a.d, a.vec_ok);
+            b[1][c] = FAST ? *reinterpret_cast<const float4*>(r1 + 16 * c + 4 * lq) : load4_guard(r1, 16 * c + 4 * lq, a.d, a.vec_ok);
         }
         row0 += tile_stride; row1 += tile_stride;
     };
@@ -516,7 +503,7 @@ __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(Topk
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(cmp4(ua[c], s), cmp4(b[n][c], s), acc[n], 0, 0, 0);
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(ua[c], s), comp(b[n][c], s), acc[n], 0, 0, 0);
         const uint32_t hm_now = hm;                                    // (this tile's bitmap word: the prefetch below overwrites hm)
         // the next tile's operands go into the registers the MFMAs have just read: the loads fly during the selection (the train-mask
         // code below touches LDS only - a refill of the staged window, once per 16 items of a walked row, is the one wait)
@@ -610,22 +597,13 @@ __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(Topk
 // launch (blocks of unflagged tiles exit at once). The first version of the mode rescored every candidate at every drain: bit-identical too,
 // but 5 - 20 % SLOWER than the exact sweep (profiles/experiments/r05_topk.md).
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef __bf16 tk_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x4 tk_mfma_bf16(const uint4& a, const uint4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tk_bf16x8, a), __builtin_bit_cast(tk_bf16x8, b), c, 0, 0, 0);
-}
-// round-to-nearest-even bf16 of a finite float, as a float (low 16 bits zero)
-__device__ __forceinline__ uint32_t tk_rn_bf16_bits(float x) {
-    const uint32_t b = __float_as_uint(x);
-    return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u;
-}
-// two floats -> packed (hi, mid) bf16 pairs, round-to-nearest splits (h = RN(x); the residual x - h is exact in fp32; m = RN(x - h))
+// two (finite) floats -> packed (hi, mid) bf16 pairs, round-to-nearest splits (h = RN(x); the residual x - h is exact in fp32; m = RN(x - h))
 __device__ __forceinline__ void tk_split2(float x0, float x1, uint32_t& H, uint32_t& M) {
-    const uint32_t h0 = tk_rn_bf16_bits(x0), h1 = tk_rn_bf16_bits(x1);
+    const uint32_t h0 = rn_bf16_bits_finite(x0), h1 = rn_bf16_bits_finite(x1);
     const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-    const uint32_t m0 = tk_rn_bf16_bits(r0), m1 = tk_rn_bf16_bits(r1);
-    H = __builtin_amdgcn_perm(h1, h0, 0x07060302u);                      // high halves: e0 -> low 16 bits, e1 -> high 16 bits
-    M = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
+    const uint32_t m0 = rn_bf16_bits_finite(r0), m1 = rn_bf16_bits_finite(r1);
+    H = pack_hi16(h0, h1);
+    M = pack_hi16(m0, m1);
 }
 __device__ __forceinline__ void tk_split8(const float (&x)[8], uint4& H, uint4& M) {
     tk_split2(x[0], x[1], H.x, M.x); tk_split2(x[2], x[3], H.y, M.y);
@@ -704,17 +682,17 @@ __device__ __forceinline__ void tk_finalize_user(const TopkArgs& a, const float*
 #pragma unroll
             for (int b = 0; b < BATCH; ++b)
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) iv[b][qq] = ld4g(ir, 16 * (c0 + b) + 4 * qq, a.d, a.vec_ok);   // (zeros past d)
+                for (int qq = 0; qq < 4; ++qq) iv[b][qq] = load4_guard(ir, 16 * (c0 + b) + 4 * qq, a.d, a.vec_ok);   // (zeros past d)
 #pragma unroll
             for (int b = 0; b < BATCH; ++b) {
                 float4 uv[4];
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) uv[qq] = ld4g(urow, 16 * (c0 + b) + 4 * qq, ulen, u_vec);
+                for (int qq = 0; qq < 4; ++qq) uv[qq] = load4_guard(urow, 16 * (c0 + b) + 4 * qq, ulen, u_vec);
                 if (c0 + b < nc) {                                       // (wave-uniform; chunks past d stay out of the chain: fma(0, 0, -0.0f) is +0.0f)
 #pragma unroll
                     for (int s_ = 0; s_ < 4; ++s_)
 #pragma unroll
-                        for (int qq = 0; qq < 4; ++qq) acc = __builtin_fmaf(cmp4(uv[qq], s_), cmp4(iv[b][qq], s_), acc);
+                        for (int qq = 0; qq < 4; ++qq) acc = __builtin_fmaf(comp(uv[qq], s_), comp(iv[b][qq], s_), acc);
                 }
             }
         }
@@ -941,9 +919,9 @@ __global__ __launch_bounds__(256, (DK32 <= 2 ? 4 : 2)) void score_topk_pre_kerne
         for (int c = 0; c < DK32; ++c)
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
-                acc[n] = tk_mfma_bf16(uM[c], bH[n][c], acc[n]);
-                acc[n] = tk_mfma_bf16(uH[c], bM[n][c], acc[n]);
-                acc[n] = tk_mfma_bf16(uH[c], bH[n][c], acc[n]);
+                acc[n] = mfma_bf16(uM[c], bH[n][c], acc[n]);
+                acc[n] = mfma_bf16(uH[c], bM[n][c], acc[n]);
+                acc[n] = mfma_bf16(uH[c], bH[n][c], acc[n]);
             }
         const float cn_now[2] = {cnv[0], cnv[1]};                       // (this tile's factors: the prefetch below overwrites cnv)
         const uint32_t hm_now = hm;
@@ -982,7 +960,7 @@ __global__ __launch_bounds__(256, (DK32 <= 2 ? 4 : 2)) void score_topk_pre_kerne
             constexpr bool MASKED = decltype(masked_tag)::value;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float rthr = cmp4(t4, r);
+                const float rthr = comp(t4, r);
                 const uint32_t rm = rm4[r];
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
@@ -1372,11 +1350,11 @@ __device__ __forceinline__ float auc_chain(const float* ur, const float* ir, int
     for (int c = 0; c < d / 16; ++c) {
         float4 uv[4], iv[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { uv[q] = ld4g(ur, 16 * c + 4 * q, d, vec); iv[q] = ld4g(ir, 16 * c + 4 * q, d, vec); }
+        for (int q = 0; q < 4; ++q) { uv[q] = load4_guard(ur, 16 * c + 4 * q, d, vec); iv[q] = load4_guard(ir, 16 * c + 4 * q, d, vec); }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(cmp4(uv[q], s), cmp4(iv[q], s), acc);
+            for (int q = 0; q < 4; ++q) acc = __builtin_fmaf(comp(uv[q], s), comp(iv[q], s), acc);
     }
     return acc;
 }
@@ -1415,7 +1393,7 @@ __global__ __launch_bounds__(256) void auc_sweep_kernel(AucArgs a) {
     const int64_t user_a = a.query_users[qa];
     float4 ua[DK];
 #pragma unroll
-    for (int c = 0; c < DK; ++c) ua[c] = ld4g(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
+    for (int c = 0; c < DK; ++c) ua[c] = load4_guard(a.Eu + user_a * a.ldu, 16 * c + 4 * lq, a.d, a.vec_ok);
 
     // this wave's item tiles: a quarter of the part
     const int64_t tiles_all = (a.n_items + TK_TILE - 1) / TK_TILE;
@@ -1516,7 +1494,7 @@ __global__ __launch_bounds__(256) void auc_sweep_kernel(AucArgs a) {
                 int64_t item = base + 16 * n + li;
                 if (item > a.n_items - 1) item = a.n_items - 1;
 #pragma unroll
-                for (int c = 0; c < DK; ++c) b[n][c] = ld4g(a.Ei + item * a.ldi, 16 * c + 4 * lq, a.d, a.vec_ok);
+                for (int c = 0; c < DK; ++c) b[n][c] = load4_guard(a.Ei + item * a.ldi, 16 * c + 4 * lq, a.d, a.vec_ok);
             }
             f32x4 acc[2];
             acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
@@ -1526,7 +1504,7 @@ __global__ __launch_bounds__(256) void auc_sweep_kernel(AucArgs a) {
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
                     for (int n = 0; n < 2; ++n)
-                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(cmp4(ua[c], s), cmp4(b[n][c], s), acc[n], 0, 0, 0);
+                        acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp(ua[c], s), comp(b[n][c], s), acc[n], 0, 0, 0);
             // the tile's train items of user li (lanes 0..15; rows ascending, the cursor never falls behind the tile)
             uint32_t m = 0u;
             while ((int64_t)nxt < base + TK_TILE) {
