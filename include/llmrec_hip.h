@@ -958,6 +958,39 @@ int llmrec_sample_batch_wide(uint64_t seed, uint64_t* step_dev, int64_t n_exist_
                              int64_t* users, int64_t* pos, int64_t* neg, int32_t* n_valid_dev, int32_t* ticket, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * R12  dropout on the projections        replaces nn.Dropout on the eight projected feature
+ *                                        tensors (reference Models.py:145-150) in the fused step,
+ *                                        and its backward (the same mask on the gradient).
+ * In-place inverted dropout of the row-major [rows, cols] view X (any ldx >= cols, any 4-byte-aligned
+ * base; columns [cols, ldx) are never read or written). The mask is NOT torch's stream: it is this pure
+ * function of (seed, step, tensor_tag, row, column), which a test can restate from these lines alone.
+ *   generator  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ *              0x9E3779B9 / 0xBB67AE85), as the sampler above.
+ *   key        k = seed ^ 0xD1B54A32D192ED03; key word 0 = low 32 bits of k, key word 1 = high 32 bits
+ *              (a stream of its own: the sampler's keys are seed and seed ^ 0x9E3779B97F4A7C15).
+ *   counter    (c >> 2, r, (uint32) s, (uint32) (s >> 32) * 256 + tensor_tag)   [the last word mod 2^32]
+ *              for the element in row r, column c, with s = *step_dev as the launch reads it. The element
+ *              uses output word c & 3 of that call: one call serves four consecutive columns.
+ *   keep rule  the element is kept iff word >= T, T = (uint32) llrint((double) p * 4294967296.0) computed
+ *              on the host and clamped to [1, 2^32 - 1].
+ *   values     kept: x * scale with scale = 1.0f / (1.0f - p), both in fp32 (one rounding each);
+ *              dropped: +0.0f exactly, whatever x was (a NaN or an infinity included).
+ * LLMREC_EINVAL, before any HIP call, for: p outside (0, 1) or NaN; cols < 1; tensor_tag outside [0, 256);
+ * rows < 0 or rows >= 2^32; with rows > 0, a null X or step_dev, a base that is not 4-byte aligned or
+ * ldx < cols. rows == 0 succeeds without a launch.
+ * The step counter is device memory, so a replayed graph follows it. ticket == NULL: the launch only READS
+ * *step_dev. Otherwise ticket is one int32 of device memory, ZERO before the first call: every block
+ * increments it after its last read of *step_dev, and the block that draws the last ticket adds 1 to
+ * *step_dev and puts the ticket back to 0 (the count-off of llmrec_sample_batch_wide: no float atomics, no
+ * block waits for another, no host action between replays). The caller orders the ticketed launch behind
+ * every other reader of the counter in that step. tensor_tag names the tensor, so that tensors of one step
+ * draw independent masks; the tags the fused step uses are in llmrec_amd/ops.py.
+ * ------------------------------------------------------------------------------------------ */
+int llmrec_dropout_rows_f32(int64_t rows, int32_t cols, float* X, int64_t ldx, float p,
+                            uint64_t seed, uint64_t* step_dev, int32_t tensor_tag,
+                            int32_t* ticket /* NULL: do not advance */, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`; nothing on the product path calls it). One single-lane launch that
  * stores the device's constant-rate real-time counter (s_memrealtime) into *slot when the stream reaches it.
  * A captured HIP graph cannot carry event-record nodes for external events; a pair of these around a launch

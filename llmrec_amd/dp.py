@@ -57,7 +57,12 @@ class DataParallelStep(FusedStep):
     slots of it). comm: llmrec_amd.dist.Comm (.rank, .world, .dist = torch.distributed); None = single
     replica or a loop-back harness that moves the two exchange buffers itself (rank=, world=)."""
 
-    def __init__(self, model, graph, hp, rates, optimizer, b_max: int, comm=None, rank: int = None, world: int = None):
+    def __init__(self, model, graph, hp, rates, optimizer, b_max: int, comm=None, rank: int = None, world: int = None,
+                 drop_rate: float = 0.0, drop_seed: int = 0):
+        if drop_rate != 0:
+            # (the replicas would have to draw ONE mask for the replicated projections and advance one counter across three phases)
+            raise RuntimeError("DataParallelStep: drop_rate = %r is not supported; dropout inside the step is FusedStep's (single replica) only"
+                               % (drop_rate,))
         self.bucket, self.n_grad = bucket_gradients(model)
         super().__init__(model, graph, hp, rates, optimizer, b_max)
         self.comm = comm

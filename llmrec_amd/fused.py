@@ -18,7 +18,8 @@ main.py:228-278); what changes is the organisation:
   * the embedding tables' AdamW reads its gradient where it is formed (the user table's is inv * dE_u) and the row-wise clean-up of the
     scatter targets rides in the item table's AdamW launch;
   * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
-Falls outside its scope (use the modular path): dropout > 0 and the --mask branch.
+Falls outside its scope (use the modular path): the --mask branch, and dropout > 0 unless the step is built for it (drop_rate=: the
+project's own counter-based masks on the device, llmrec_dropout_rows_f32 - FusedStep.__init__, "DROPOUT").
 Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 (the
 chain's first product in an SpMM group of its own launch) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
 FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
@@ -106,9 +107,13 @@ class FusedStep:
     wgrad_blocks = 224
     WGRAD_ROWS = INLINE_ADAMW = FOLD = True      # schedule switches of the class: DataParallelStep (llmrec_amd/dp.py) turns all three off
 
-    def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int):
+    def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int, drop_rate: float = 0.0, drop_seed: int = 0):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
-        or any object with .ui/.iu SparseOperands; rates: (model_cat, user_cat, item_cat)."""
+        or any object with .ui/.iu SparseOperands; rates: (model_cat, user_cat, item_cat); drop_rate / drop_seed: dropout on the eight
+        projections inside the step (reference Models.py:145-150; below, "DROPOUT") - 0 = none: the step is what it is without the option."""
+        if not 0.0 <= float(drop_rate) < 1.0:                  # (false for a NaN)
+            raise ValueError("FusedStep: drop_rate %r outside [0, 1)" % (drop_rate,))
+        self.drop_rate, self.drop_seed = float(drop_rate), int(drop_seed)
         self.m, self.hp, self.opt = model, hp, optimizer
         self.ui, self.iu = graph.ui, graph.iu
         self.U, self.I = model.n_users, model.n_items
@@ -207,6 +212,19 @@ class FusedStep:
         # default = pre-propagate iff U <= I. LLMREC_PREPROPAGATE=1 / 0 forces either order.
         want = os.environ.get("LLMREC_PREPROPAGATE", "auto")
         self.preprop = d <= 64 and (want == "1" or (want not in ("0", "1") and U <= I))
+        # DROPOUT (drop_rate > 0; opt-in: main.py builds such a step under LLMREC_FUSED_DROPOUT=1 only). nn.Dropout acts on the projections
+        # F_k W^T + b BEFORE they are propagated, and A (drop(F W^T)) is not (A F) W^T: the step runs in the reference's order of operations
+        # (P_cat / dP_cat; the row-listed weight gradient, which needs the pre-propagated operands, is off with it). The masks are
+        # llmrec_dropout_rows_f32's - a function of (drop_seed, drop_step, tensor tag, row, column), not torch's stream: two launches on
+        # P_cat / P_usr behind the projection launch of a TRAINING forward, the same two masks on dP_cat / dP_usr ahead of the weight
+        # gradients. drop_step is device memory: the backward's second launch advances it (drop_ticket: its blocks' count-off), so a
+        # replayed graph draws a new mask every step with no host action. An evaluation's forward launches none and never touches the counter.
+        if self.drop_rate > 0:
+            if want == "1":
+                raise RuntimeError("FusedStep: drop_rate > 0 needs the reference's order of operations; LLMREC_PREPROPAGATE=1 cannot be honoured")
+            self.preprop = False
+            self.drop_step = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
+            self.drop_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         if not self.preprop:
             self.P_cat, self.dP_cat = f(I, S * d), f(I, S * d)        # the projected features and their gradient (reference order)
         else:
@@ -472,6 +490,15 @@ class FusedStep:
         ops.linear_wgrad_grouped([(dY, X)], lin.weight.grad, lin.bias.grad, accumulate, self.ws_wgrad if ws is None else ws,
                                  precision=self.gemm)
 
+    def _dropout(self, backward: bool = False):
+        """The step's two dropout launches (drop_rate > 0): the item-side streams, then the user profile - the projections in the
+        forward, their gradients (the same masks: the counter has not moved) in the backward, whose second launch carries the ticket
+        and so advances the counter: it is the step's last reader of it."""
+        cat, usr = (self.dP_cat, self.dP_usr) if backward else (self.P_cat, self.P_usr)
+        ops.dropout_rows_(cat, self.drop_rate, self.drop_seed, self.drop_step, ops.DROPOUT_TAG_ITEM_STREAMS)
+        ops.dropout_rows_(usr, self.drop_rate, self.drop_seed, self.drop_step, ops.DROPOUT_TAG_USER_PROFILE,
+                          ticket=self.drop_ticket if backward else None)
+
     def _softmax_bwd(self, Y, dY, dZ, alpha: float = 1.0):
         _call("llmrec_softmax_rows_bwd_scaled_f32", Y.shape[0], self.d, float(alpha), _p(Y), _ld(Y), _p(dY), _ld(dY), _p(dZ), _ld(dZ))
 
@@ -574,7 +601,11 @@ class FusedStep:
                     order), and writes U_1; the projection's units read the features and the Linears and write U_cat / P_cat and P_usr: disjoint.
           sampler   rides the first group as before: that group now reads U_1, U_cat and P_usr and writes I_1, I_cat, prof_i.
           plan + marks   ride the group that runs alone, now the last one (it reads U_2 and writes I_2); their readers - the fusion launch's
-                    compaction block and the loss backward - still follow it in stream order."""
+                    compaction block and the loss backward - still follow it in stream order.
+        DROPOUT (drop_rate > 0, training forward only): two launches between the projection launch and the first group.
+          dropout   reads the dropout counter (last written by the previous step's backward, earlier in stream order) and P_cat / P_usr,
+                    written by the projection launch's units; writes P_cat / P_usr in place, read first by the first group. A hosted
+                    product's U_1 is not touched. Neither launch carries the ticket: the counter stays where it is until the backward."""
         if sampler is not None and sampler.guest is None:
             sampler()
         if step is not None and not self.fold:
@@ -588,6 +619,8 @@ class FusedStep:
         else:
             self._project_all()
         self._stamp(2)
+        if step is not None and self.drop_rate > 0:
+            self._dropout()
         side = [(self.ui.fwd, self.P_cat, self.U_cat, {})] if not self.preprop else []
         side.append((self.iu.fwd, self.U_cat, self.I_cat, {}))
         prof = [(self.iu.fwd, self.P_usr, self.prof_i, dict(tag=1)), (self.ui.fwd, self.prof_i, self.prof_u, dict(tag=1))]
@@ -615,6 +648,8 @@ class FusedStep:
         self._stamp(1)
         self._project_all()
         self._stamp(2)
+        if step is not None and self.drop_rate > 0:                      # (ahead of ev1: the profile stream reads the dropped P_usr)
+            self._dropout()
         ev1 = self._mark()
         if not self.preprop:
             self._spmm(self.ui.fwd, self.P_cat, self.U_cat)              # 7 streams, one adjacency pass
@@ -736,10 +771,28 @@ class FusedStep:
         fuse, keep = self._fuse_bwd_problems(hp.feat_reg_decay * 0.5 / self.I * replicated_scale, stamped=bpr_bwd_done)
         schedule = self._backward_streams if self.multi_stream else self._backward_one_stream
         schedule(probs, (users, pos, neg, n_valid), fuse, side_work, masked=bpr_bwd_done and self.bwd_mask)
+        if self.drop_rate > 0:
+            self._dropout_backward()
         self._weight_gradients(ev_reach)
         self._join(self.s2)
         if self.fold and side_work is not None:                          # (four streams: side_work ran on a stream of its own)
             self._join(self.s3)
+
+    def _dropout_backward(self):
+        """drop_rate > 0: the forward's two masks on dP_cat and dP_usr, between the schedule that forms them and the weight gradients -
+        the only readers of either. Read / write sets:
+          dP_cat launch   reads the counter and dP_cat, written by the side chain's last transposed product (the current stream); writes dP_cat.
+          dP_usr launch   reads the counter and dP_usr, written by the profile chain's last transposed product (one stream: the same
+                    group as dP_cat's; four streams: s1, joined here first); writes dP_usr, and - the ticket - the counter and the ticket
+                    word. It is the step's last reader of the counter, and nothing runs beside it that reads it: the other three readers
+                    precede it on this stream, and what the ID chain's stream still has queued (its products, the clean-up, the item
+                    table's AdamW) reads neither the counter nor a projection's gradient.
+        user_trans' exact-fp32 weight gradient, which the schedules otherwise issue right behind the profile chain, follows here: it reads
+        the dropped dP_usr."""
+        self._join(self.s1)
+        self._dropout(backward=True)
+        if self.gemm != "bf16x3":
+            self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
 
     def _fuse_bwd_problems(self, coef: float, stamped: bool):
         """The backward of both fusions as the two problems of ONE launch (llmrec_fuse_bwd_src_multi_f32) -> (problems, the arrays they
@@ -887,7 +940,7 @@ class FusedStep:
         for k, jobs in enumerate(zip_longest(chain, side, prof)):
             self._spmm_group(jobs, side_work if k == 0 and rides else None)
         self._check_mask_promise(masked, done=True)
-        if self.gemm != "bf16x3":                                        # (bf16x3: user_trans' gradient is in the multi-target launch)
+        if self.gemm != "bf16x3" and not self.drop_rate > 0:             # (bf16x3: user_trans' gradient is in the multi-target launch; dropout: _dropout_backward)
             self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
         self._chain_tail(probs, batch)
 
@@ -914,7 +967,7 @@ class FusedStep:
             side_work = None
         with self._on(self.s1):
             self._spmm_jobs(prof)
-            if self.gemm != "bf16x3":
+            if self.gemm != "bf16x3" and not self.drop_rate > 0:         # (dropout: behind the mask on dP_usr, _dropout_backward)
                 self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
         # the ID chain depends on the BPR rows only, not on the fusion backward: it starts beside it (captured after it, so that the
         # fusion backward stays the graph's same-queue successor of the BPR launch) and has most of its SpMMs behind it when the

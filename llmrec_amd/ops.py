@@ -1374,6 +1374,25 @@ def sample_batch_wide(seed: int, step_dev: torch.Tensor, exist_users: torch.Tens
               B_global, slice_begin, B, n_aug, _p(aug_pos), _p(aug_neg), _p(users), _p(pos), _p(neg), _p(n_valid), _p(ticket), _stream())
 
 
+# the tensor tags of llmrec_dropout_rows_f32 the fused step uses (a tag names a tensor: tensors of one step draw independent masks)
+DROPOUT_TAG_ITEM_STREAMS = 0      # the [I, S d] projected item-side streams (image, text, attributes): column = slice * d + j
+DROPOUT_TAG_USER_PROFILE = 1      # P_usr, the projected user profile
+
+
+def dropout_rows_(X: torch.Tensor, p: float, seed: int, step_dev: torch.Tensor, tag: int, ticket: Optional[torch.Tensor] = None):
+    """llmrec_dropout_rows_f32: inverted dropout of the 2-D fp32 view X IN PLACE (inner stride 1, any row stride) with the counter-based mask
+    of (seed, step_dev[0], tag, row, column) the header states. step_dev: one 64-bit integer on the device; ticket (int32[1], device, zero
+    before the first call): the launch also advances step_dev by 1 - without it the counter is only read. Returns X."""
+    _need_gpu(X, step_dev, ticket)
+    if X.dtype != torch.float32 or X.dim() != 2 or (X.shape[1] > 1 and X.stride(1) != 1) or (X.shape[0] > 1 and X.stride(0) < X.shape[1]):
+        raise RuntimeError("dropout_rows_: a 2-D fp32 view with inner stride 1 expected (the launch writes in place)")
+    if step_dev.dtype not in (torch.int64, torch.uint64) or step_dev.numel() < 1 or (ticket is not None and ticket.dtype != torch.int32):
+        raise RuntimeError("dropout_rows_: a 64-bit integer step counter and an int32 ticket expected")
+    _lib.call("llmrec_dropout_rows_f32", X.shape[0], X.shape[1], _p(X), _ld(X), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(tag),
+              _p(ticket), _stream())
+    return X
+
+
 def topk_metrics(idx: torch.Tensor, hits: torch.Tensor, query_users: torch.Tensor, test_rowptr: torch.Tensor, Ks) -> torch.Tensor:
     """Per-user [n, 4, len(Ks)] float64 (precision, recall, ndcg, hit_ratio) on the device (llmrec_topk_metrics)."""
     _need_gpu(idx, hits, query_users, test_rowptr)

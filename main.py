@@ -351,11 +351,14 @@ class Trainer(object):
     def _fused_step(self):
         """The fused step (llmrec_amd/fused.py) when the configuration allows it: no dropout, no
         --mask. LLMREC_FUSED=0 forces the modular autograd path; LLMREC_GRAPH=0 issues the fused step's
-        launches one by one instead of replaying the captured HIP graph."""
+        launches one by one instead of replaying the captured HIP graph. LLMREC_FUSED_DROPOUT=1 (opt-in) keeps
+        --drop_rate > 0 in the fused step: the masks are then the library's counter-based stream of
+        (--seed, step, tensor, row, column), not torch's."""
         if self._fused is None:
             # the reference masks user features whenever mask_rate > 0, with or without --mask (Models.py:139-142):
             # the fused path reads the unmasked features, so any of the three sends the step down the modular path
-            ok = (os.environ.get("LLMREC_FUSED", "1") == "1" and not args.mask and args.drop_rate == 0
+            fused_dropout = os.environ.get("LLMREC_FUSED_DROPOUT", "0") == "1"
+            ok = (os.environ.get("LLMREC_FUSED", "1") == "1" and not args.mask and (args.drop_rate == 0 or fused_dropout)
                   and args.mask_rate == 0 and device.type == "cuda")
             # the fused step's eight-problem loss launches stage the batch in LDS (LLMREC_BPR_MAX_B); a larger batch trains on the
             # modular path, whose ops.bpr_prune selects with the multi-block kernels
@@ -365,8 +368,9 @@ class Trainer(object):
                 from llmrec_amd.fused import FusedStep
                 graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(self.ui_graph),
                                        "iu": ops.operand_from_sparse_tensor(self.iu_graph)})
+                drop = dict(drop_rate=args.drop_rate, drop_seed=args.seed) if args.drop_rate != 0 else {}
                 self._fused = FusedStep(self.model_mm, graph, self.hyper,
-                                        (args.model_cat_rate, args.user_cat_rate, args.item_cat_rate), self.optimizer, b_max)
+                                        (args.model_cat_rate, args.user_cat_rate, args.item_cat_rate), self.optimizer, b_max, **drop)
             else:
                 self._fused = False
         return self._fused
