@@ -19,25 +19,25 @@ main.py:228-278); what changes is the organisation:
     scatter targets rides in the item table's AdamW launch;
   * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
 Falls outside its scope (use the modular path): the --mask branch, and dropout > 0 unless the step is built for it (drop_rate=: the
-project's own counter-based masks on the device, llmrec_dropout_rows_f32 - FusedStep.__init__, "DROPOUT").
+project's own counter-based masks on the device, llmrec_dropout_rows_f32 - step_options.resolve, "DROPOUT").
 Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 (the
 chain's first product in an SpMM group of its own launch) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
 FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
-gradients before AdamW).
+gradients before AdamW). Every switch is decided in ONE place, llmrec_amd/step_options.py (resolve(): a pure function of the variables,
+the shapes and the class switches, with each switch's rationale and measured figures); FusedStep.__init__ copies its record and allocates.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
 import gc
-import os
 from collections import namedtuple
 from itertools import zip_longest
 from typing import Callable, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, step_options
 from .engine import Hyper
 
 _p, _ld, _c = ops._p, ops._ld, ctypes
@@ -110,10 +110,7 @@ class FusedStep:
     def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int, drop_rate: float = 0.0, drop_seed: int = 0):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
         or any object with .ui/.iu SparseOperands; rates: (model_cat, user_cat, item_cat); drop_rate / drop_seed: dropout on the eight
-        projections inside the step (reference Models.py:145-150; below, "DROPOUT") - 0 = none: the step is what it is without the option."""
-        if not 0.0 <= float(drop_rate) < 1.0:                  # (false for a NaN)
-            raise ValueError("FusedStep: drop_rate %r outside [0, 1)" % (drop_rate,))
-        self.drop_rate, self.drop_seed = float(drop_rate), int(drop_seed)
+        projections inside the step (reference Models.py:145-150; step_options.resolve, "DROPOUT") - 0 = none: the step is what it is without the option."""
         self.m, self.hp, self.opt = model, hp, optimizer
         self.ui, self.iu = graph.ui, graph.iu
         self.U, self.I = model.n_users, model.n_items
@@ -123,6 +120,15 @@ class FusedStep:
         self.S = S = 2 + len(self.keys)                      # item-side streams: image, text, attributes
         self.c_m, self.c_u, self.c_a = rates
         self.b_max = b_max
+        # every switch of the step - multi_stream, gemm, preprop, wgrad_rows, inline_adamw, fold, bwd_mask, bwd_zero_skip, host_chain,
+        # check_zero and the validated drop_rate - is decided once, with its rationale, in step_options.resolve(); below: allocation only
+        opts = step_options.resolve(None, n_users=self.U, n_items=self.I, d=d, n_attr=len(self.keys), drop_rate=drop_rate,
+                                    wgrad_rows_default=self.WGRAD_ROWS, inline_adamw_default=self.INLINE_ADAMW, fold_default=self.FOLD,
+                                    bwd_nnz=self.iu.bwd.nnz, bwd_valued=self.iu.bwd.val is not None,
+                                    bwd_col_scaled=self.iu.bwd.col_scale is not None, latency_nnz=ops.SPMM_LATENCY_NNZ)
+        for name, value in opts._asdict().items():
+            setattr(self, name, value)
+        self.drop_seed = int(drop_seed)
         dev = model.item_id_embedding.weight.device
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         U, I = self.U, self.I
@@ -136,9 +142,7 @@ class FusedStep:
         # The loss backward scatters into buffers that are all-zero between steps - dE_u / dE_i and the sc_* sources of the fusion
         # backward - and clears exactly the rows it touched afterwards (llmrec_bpr_multi_zero_rows_f32); the fusion backward
         # writes d*_cat = source + its own term (llmrec_fuse_bwd_src_f32). No dense memset of the six gradient buffers (70 MB
-        # per step at the Netflix shape; measured -2.2 % of the step in round 2).
-        # LLMREC_CHECK_ZERO=1 (debug; synchronises, so not under capture): assert that invariant before every scatter
-        self.check_zero = os.environ.get("LLMREC_CHECK_ZERO", "0") == "1"
+        # per step at the Netflix shape; measured -2.2 % of the step in round 2). (check_zero asserts that invariant before every scatter.)
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.dE_u, self.dE_i = z(U, d), z(I, d)
         self.sc_U, self.sc_I, self.sc_prof = z(U, 2 * d), z(I, S * d), z(U, d)
@@ -146,7 +150,7 @@ class FusedStep:
         # cleared, no reader races a clean-up): the fusion backward writes the ~90 % of rows no sample touched (zero gradient, zero
         # sources) without reading them. (The same stamps offered to the transposed side product as a mask over ALL its slices, with the
         # mask bytes loaded at gather time, bought nothing in round 3; restricted to the attribute slices, read on the device and with
-        # the in-place skip they do: bwd_mask below.)
+        # the in-place skip they do: bwd_mask, step_options.resolve.)
         self.flag_u = torch.zeros(U, dtype=torch.uint8, device=dev)
         self.flag_i = torch.zeros(I, dtype=torch.uint8, device=dev)
         self.row_stamp = torch.zeros(1, dtype=torch.int32, device=dev)     # advanced by the scores launch (LLMREC_ROW_STAMP)
@@ -172,10 +176,6 @@ class FusedStep:
         self.ws_wgrad_b, self.ws_wgrad_c, self.ws_wgrad_d = wsq(model.user_feats), wsq(model.text_feats), wsq(model.image_feats)
         self.ws_wgrad_multi = None                           # sized at the first backward (needs the gradient tensors)
         self._partials = {}
-        # Independent chains (7-stream side features / LLM profile / ID embeddings / the logged scalars) can run on four HIP streams in forward
-        # and in backward (LLMREC_STREAMS=1), so that the latency-bound Netflix-scale SpMMs overlap the GEMMs in eager launches. The default
-        # is ONE stream: a captured step must be a single-branch graph (llmrec_amd/__init__.py).
-        self.multi_stream = os.environ.get("LLMREC_STREAMS", "0") == "1"
         self.s1, self.s2, self.s3 = (torch.cuda.Stream(device=dev) for _ in range(3))
         for p in model.parameters():
             if p.requires_grad and p.grad is None and p is not model.batch_norm.weight and p is not model.batch_norm.bias:
@@ -195,34 +195,7 @@ class FusedStep:
         # the step, the projection launch and the weight-gradient launches - the durations INSIDE a replayed graph, which cannot carry events
         self.stamps = None
         self.spmm_edge_units = 0.0                            # edge traversals (nnz x d / 64) of the SpMM launches of the last step built
-        # projection / weight-gradient arithmetic: "bf16x3" (default) = exact 3-term bf16 split of both operands, six bf16
-        # MFMAs, fp32-roundoff-class error (2e-6 measured); "f32" = the exact fp32 MFMA fma chain
-        self.gemm = os.environ.get("LLMREC_GEMM", "bf16x3")
-        # PRE-PROPAGATED item-side operands (LLMREC_PREPROPAGATE=0 restores the reference's order of operations). The features F_k
-        # and the adjacency are constants of a run, and projection followed by propagation is one product:
-        #     A_ui (F_k W^T + 1 b^T) = (A_ui F_k) W^T + (A_ui 1) b^T            (Models.py:145-157: image / text / the 5 attributes)
-        # so A_ui F_k [U, K] is formed ONCE here, the step projects IT (llmrec_linear_problem_t.bias_scale = the row sums of A_ui) straight
-        # into U_cat, and the backward takes dW = dU_cat^T (A_ui F_k), db = sum_u (A_ui 1)[u] dU_cat[u]. Per step this removes the two
-        # [.., 7 d] SpMMs through A_ui (forward and transposed) from the critical path and shrinks both GEMMs from I = 17 366 to
-        # U = 13 187 rows; every parameter-dependent product is still computed every step, only the order of the (associative)
-        # products changes: results agree with the other order to fp32 rounding (tests/test_gpu_step.py, the bench's parity gate).
-        # SHAPE-AWARE (VERDICT r03 next #4c): pre-propagation moves both GEMMs from I rows to U rows and takes the two [., 7 d] SpMMs off the
-        # critical path. It wins when the user side is the smaller one (Netflix shape, U / I = 0.76: 0.46 vs 0.62 ms per step) and loses
-        # when it is the larger one (MovieLens shape, U / I = 1.21: 0.49 vs 0.48 ms, measured with the row-listed weight gradient on):
-        # default = pre-propagate iff U <= I. LLMREC_PREPROPAGATE=1 / 0 forces either order.
-        want = os.environ.get("LLMREC_PREPROPAGATE", "auto")
-        self.preprop = d <= 64 and (want == "1" or (want not in ("0", "1") and U <= I))
-        # DROPOUT (drop_rate > 0; opt-in: main.py builds such a step under LLMREC_FUSED_DROPOUT=1 only). nn.Dropout acts on the projections
-        # F_k W^T + b BEFORE they are propagated, and A (drop(F W^T)) is not (A F) W^T: the step runs in the reference's order of operations
-        # (P_cat / dP_cat; the row-listed weight gradient, which needs the pre-propagated operands, is off with it). The masks are
-        # llmrec_dropout_rows_f32's - a function of (drop_seed, drop_step, tensor tag, row, column), not torch's stream: two launches on
-        # P_cat / P_usr behind the projection launch of a TRAINING forward, the same two masks on dP_cat / dP_usr ahead of the weight
-        # gradients. drop_step is device memory: the backward's second launch advances it (drop_ticket: its blocks' count-off), so a
-        # replayed graph draws a new mask every step with no host action. An evaluation's forward launches none and never touches the counter.
-        if self.drop_rate > 0:
-            if want == "1":
-                raise RuntimeError("FusedStep: drop_rate > 0 needs the reference's order of operations; LLMREC_PREPROPAGATE=1 cannot be honoured")
-            self.preprop = False
+        if self.drop_rate > 0:                               # the masks' step counter and its launch's count-off (step_options: DROPOUT)
             self.drop_step = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
             self.drop_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         if not self.preprop:
@@ -232,56 +205,16 @@ class FusedStep:
             self.AX = [self._propagate_constant(self.ui.fwd, x) for x in item_feats]
             self.a_rowsum = ops.spmm_raw(self.ui.fwd, torch.ones(I, 4, dtype=torch.float32, device=dev))[:, 0].contiguous()   # A_ui 1
             self.ws_colsum = torch.empty(_lib.query("llmrec_weighted_colsum_workspace_bytes", S * d), dtype=torch.uint8, device=dev)
-        # ROW-LISTED weight gradient (VERDICT r03 next #4a; LLMREC_WGRAD_ROWS=0: the dense launch). The gradient of the five attribute
-        # streams' projected features is EXACTLY ZERO outside the rows the batch reaches: an attribute stream meets the loss in the fused
-        # embeddings and BPR terms of the batch's rows only (Models.py:160-163,188-197; main.py:249-254), so dU_cat[:, attribute columns] is
-        # non-zero in the batch's users (fusion backward) and in the users adjacent to the batch's items (A_iu^T of the items' rows) - 43 %
-        # of the users at the Netflix shape. llmrec_batch_reach_rows lists those rows (beside the forward: _plan_reach_rider) and the
-        # weight-gradient launch streams the listed rows of dU_cat and A_ui F_k only (llmrec_wgrad_problem_t.row_list): the same sums
-        # without the terms that are zero. The image / text streams stay dense (the feature regulariser reads every row, main.py:151-156),
-        # and so does user_trans (its gradient is two hops wide: 66 % of the rows).
-        self.wgrad_rows = (self.WGRAD_ROWS and os.environ.get("LLMREC_WGRAD_ROWS", "1") == "1" and self.preprop
-                           and len(self.keys) > 0 and self.gemm == "bf16x3")     # (the exact-fp32 launches ignore the list: do not build it)
         if self.wgrad_rows:
             self.act_flags = torch.zeros(U + 16, dtype=torch.uint8, device=dev)[:U]   # all-zero between calls (readable in 16-byte words)
             self.act_rows = torch.zeros(U + 32, dtype=torch.int32, device=dev)
             self.act_n = torch.zeros(1, dtype=torch.int32, device=dev)
             self.act_expected = None      # rows the launch geometry is laid out for: set from the first step's count (capture() / step_eager())
-        # AdamW inside the step, in two launches: the embedding tables as soon as the ID chain's backward has produced their
-        # gradients (beside the weight-gradient GEMM), the four Linears right after the slab reduction of that GEMM - the
-        # step's tail is then one small launch instead of reduction -> cross-stream join -> a 1.96 M-parameter update.
-        # (Batch-sharded replicas all-reduce the gradients first and update afterwards: llmrec_amd/dp.py sets this to False.)
-        self.inline_adamw = self.INLINE_ADAMW
-        # FOLDED launches (round 5; LLMREC_FOLD=0 restores the separate launches): AdamW's counter advances inside the scores
-        # launch ("a new step begins": llmrec_bpr_multi_scores_step_f32), the feature regulariser's sum of squares comes out of the fusion launch
-        # as per-block partials (llmrec_fuse_fwd_multi_sumsq_f32: it holds those rows anyway) and is reduced by the ONE launch that also forms
-        # the loss values and assembles the logged scalars (llmrec_bpr_multi_losses_assemble_f32), the user table's AdamW reads inv * dE_u
-        # directly and stores it as the table's .grad on the way (no axpy), and the row-wise clean-up of the scatter targets rides in the item
-        # table's AdamW launch (llmrec_adamw_multi_zero_rows_f32): eight launches fewer, same arithmetic except the regulariser's summation tree.
-        self.fold = self.FOLD and os.environ.get("LLMREC_FOLD", "1") == "1" and self.inline_adamw
         if self.fold:
             self.ss_cap = 2 * 2048                                # >= the fusion launch's grid (two problems, <= 2048 blocks each)
             self.ss_partial = torch.zeros(self.ss_cap, dtype=torch.float32, device=dev)
             self.ss_n = 0
-        # MASKED side product of the backward (LLMREC_BWD_MASK=0: the dense calls; =spmm: the product's mask without the fusion backward's
-        # skip). dI_cat's attribute slices (2 ..) are exactly zero outside the rows of the batch's items - the argument of the row-listed
-        # weight gradient above, one product earlier - and the loss launch stamps those rows in flag_i. dU_cat += A_iu^T dI_cat then
-        # gathers, in the slices from 2 on, the stamped rows only and leaves user rows without a stamped neighbour untouched
-        # (llmrec_spmm_epilogue_t.x_mask_stamp: the stamp is read on the device, so a replayed graph follows it); the fusion backward in
-        # turn no longer writes the zeros nobody reads (llmrec_fuse_bwd_problem_t.zero_skip_from_term). Same bits as the dense calls.
-        # Needs the stamps (the folded loss launch), one 64-column slice per stream and exactly the product the mask is compiled for -
-        # latency-bound, pattern-only, weighted by col_scale (an adjacency that keeps its values runs the dense calls); dU_cat keeps
-        # its dense zeros (the dense weight-gradient fallbacks read every row).
-        want = os.environ.get("LLMREC_BWD_MASK", "1")
-        self.bwd_mask = (want != "0" and self.fold and d == 64 and len(self.keys) > 0 and self.iu.bwd.nnz < ops.SPMM_LATENCY_NNZ
-                         and self.iu.bwd.val is None and self.iu.bwd.col_scale is not None)
-        self.bwd_zero_skip = self.bwd_mask and want != "spmm"
         self._refuse_guests = False                           # tests: treat every guest launch as refused (the separate calls run)
-        # HOSTED ID chain (round 15; LLMREC_HOST_CHAIN=0: the chain's first product in the first SpMM group, as before). The chain's first
-        # product A_ui E_i needs nothing from the projection, and the grouped projection's last round of work units leaves block slots
-        # empty once the launch has more units than the device has slots: the product runs as trailing blocks of that launch
-        # (llmrec_linear_fwd_grouped_host_spmm_bf16x3) and the forward needs one SpMM group fewer. Same bits: every row keeps its tree.
-        self.host_chain = os.environ.get("LLMREC_HOST_CHAIN", "1") == "1"
         self._block_slots = 2 * torch.cuda.get_device_properties(dev).multi_processor_count     # the projection keeps >= 2 blocks per CU
         self._emb_params = [model.user_id_embedding.weight, model.item_id_embedding.weight]
         self._lin_params = [p for p in optimizer.params if p.grad is not None and all(p is not e for e in self._emb_params)]
@@ -457,13 +390,7 @@ class FusedStep:
 
     @staticmethod
     def _projection_problems(jobs):
-        arr = (ops.LinearProblem * len(jobs))()
-        for i, (X, lin, out, bscale) in enumerate(jobs):
-            arr[i].X, arr[i].ldx, arr[i].M, arr[i].K = X.data_ptr(), _ld(X), X.shape[0], X.shape[1]
-            arr[i].W, arr[i].ldw, arr[i].bias = lin.weight.data_ptr(), _ld(lin.weight), lin.bias.data_ptr()
-            arr[i].Y, arr[i].ldy = out.data_ptr(), _ld(out)
-            arr[i].bias_scale = bscale.data_ptr() if bscale is not None else None
-        return arr
+        return ops.linear_problems([(X, lin.weight, lin.bias, out, bscale) for X, lin, out, bscale in jobs])
 
     def _project_all_hosting(self, job) -> bool:
         """_project_all() with the independent product `job` (a, X, Y, kwargs of _spmm) as TRAILING blocks of the grouped launch
@@ -507,10 +434,6 @@ class FusedStep:
         cols = X.shape[1] if cols is None else cols
         _call("llmrec_axpy_f32", rows, cols, float(alpha), None, _p(X), _ld(X), _p(Y), _ld(Y), 1 if accumulate else 0)
 
-    @staticmethod
-    def _tables(ts):
-        return (_c.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), (_c.c_int64 * len(ts))(*[_ld(t) for t in ts])
-
     def _side(self, cat, s):
         return cat[:, s * self.d:(s + 1) * self.d]
 
@@ -546,8 +469,8 @@ class FusedStep:
 
         def problem(pr, out, base, layers, cat, prof):
             means, norms = [base] + layers, self._norm_terms(cat, prof)
-            mp, ml = self._tables(means)
-            npt, nl = self._tables(norms)
+            mp, ml = ops._ptr_table(means)
+            npt, nl = ops._ptr_table(norms)
             rates = self._rates()
             keep.extend((mp, ml, npt, nl, rates))
             pr.rows, pr.mean_scale, pr.n_mean, pr.n_norm = out.shape[0], 1.0 / len(means), len(means), len(norms)
@@ -801,8 +724,8 @@ class FusedStep:
 
         def problem(pr, dout, cat, prof, dcat, dprof, srcs, flags):
             norms, dnorms = self._norm_terms(cat, prof), self._norm_terms(dcat, dprof)
-            npt, nl = self._tables(norms)
-            dp, dl = self._tables(dnorms)
+            npt, nl = ops._ptr_table(norms)
+            dp, dl = ops._ptr_table(dnorms)
             # sources = what the loss backward scattered for this side (terms in _norm_terms order: image, text, profile, attributes);
             # the feature regulariser's gradient on the image / text streams (terms 0, 1) rides along: 2 coef x
             sp = (_c.c_void_p * len(srcs))(*[t.data_ptr() if t is not None else None for t in srcs])

@@ -786,6 +786,17 @@ WgradTarget = _lib.STRUCT["llmrec_wgrad_target_t"]
 WgradUpdate = _lib.STRUCT["llmrec_wgrad_update_t"]
 
 
+def _wgrad_problem(pr, pair):
+    """Fill one llmrec_wgrad_problem_t from (dY, X[, db_row_weight[, (row_list, n_rows, rows_expected)]]); row_list = the rows of dY that
+    can be non-zero (served by the bf16x3 128-wide organisation only, else refused)."""
+    dY, X = pair[:2]
+    _need_gpu(dY, X)
+    pr.dY, pr.lddy, pr.X, pr.ldx, pr.M = dY.data_ptr(), _ld(dY), X.data_ptr(), _ld(X), X.shape[0]
+    pr.db_row_weight = pair[2].data_ptr() if len(pair) > 2 and pair[2] is not None else None
+    if len(pair) > 3 and pair[3] is not None:
+        pr.row_list, pr.n_rows, pr.rows_expected = pair[3][0].data_ptr(), pair[3][1].data_ptr(), int(pair[3][2] or 0)
+
+
 def _wgrad_targets(targets, block_budget: int = 0):
     """targets: [(pairs, dW, db, accumulate)] -> (ctypes array, keep-alive list, N); block_budget: llmrec_wgrad_target_t.block_budget"""
     arr = (WgradTarget * len(targets))()
@@ -794,16 +805,12 @@ def _wgrad_targets(targets, block_budget: int = 0):
     N = targets[0][1].shape[0]
     for i, (pairs, dW, db, accumulate) in enumerate(targets):
         probs = (WgradProblem * len(pairs))()
-        for j, pair in enumerate(pairs):                       # (dY, X[, db_row_weight[, (row_list, n_rows, rows_expected)]])
-            dY, X = pair[:2]
-            _need_gpu(dY, X)
-            probs[j].dY, probs[j].lddy, probs[j].X, probs[j].ldx, probs[j].M = dY.data_ptr(), _ld(dY), X.data_ptr(), _ld(X), X.shape[0]
-            probs[j].db_row_weight = pair[2].data_ptr() if len(pair) > 2 and pair[2] is not None else None
-            if len(pair) > 3 and pair[3] is not None:          # the rows of dY that can be non-zero (llmrec_wgrad_problem_t.row_list)
-                rl, nr, expected = pair[3]
-                if rl.dtype != torch.int32 or nr.dtype != torch.int32 or rl.numel() < X.shape[0] + 32:
+        for j, pair in enumerate(pairs):
+            _wgrad_problem(probs[j], pair)
+            if len(pair) > 3 and pair[3] is not None:
+                rl, nr, _ = pair[3]
+                if rl.dtype != torch.int32 or nr.dtype != torch.int32 or rl.numel() < pair[1].shape[0] + 32:
                     raise RuntimeError("linear_wgrad_multi: row_list must be int32 with M + 32 entries, n_rows an int32 device scalar")
-                probs[j].row_list, probs[j].n_rows, probs[j].rows_expected = rl.data_ptr(), nr.data_ptr(), int(expected or 0)
                 keep.append((rl, nr))
         keep.append(probs)
         arr[i].n_problems, arr[i].problems, arr[i].K = len(pairs), _c.cast(probs, _c.c_void_p), dW.shape[1]
@@ -867,14 +874,9 @@ def linear_wgrad_grouped(pairs, dW, db, accumulate: bool, ws: Optional[torch.Ten
     precision "bf16x3": llmrec_linear_wgrad_grouped_bf16x3 (three-term bf16 split, fp32-class error)."""
     arr = (WgradProblem * len(pairs))()
     M_total = 0
-    for i, pair in enumerate(pairs):                           # (dY, X) or (dY, X, db_row_weight)
-        dY, X = pair[:2]
-        _need_gpu(dY, X)
-        arr[i].dY, arr[i].lddy, arr[i].X, arr[i].ldx, arr[i].M = dY.data_ptr(), _ld(dY), X.data_ptr(), _ld(X), X.shape[0]
-        arr[i].db_row_weight = pair[2].data_ptr() if len(pair) > 2 and pair[2] is not None else None
-        if len(pair) > 3 and pair[3] is not None:              # row list: served by the bf16x3 128-wide organisation only (else refused)
-            arr[i].row_list, arr[i].n_rows, arr[i].rows_expected = pair[3][0].data_ptr(), pair[3][1].data_ptr(), int(pair[3][2] or 0)
-        M_total += X.shape[0]
+    for i, pair in enumerate(pairs):
+        _wgrad_problem(arr[i], pair)
+        M_total += pair[1].shape[0]
     N, K = dW.shape
     need = _lib.query("llmrec_linear_wgrad_workspace_bytes", M_total, N, K)
     if ws is None or ws.numel() < need:
@@ -883,18 +885,24 @@ def linear_wgrad_grouped(pairs, dW, db, accumulate: bool, ws: Optional[torch.Ten
               len(pairs), arr, N, K, _p(dW), _ld(dW), _p(db), 1 if accumulate else 0, _p(ws), ws.numel(), _stream())
 
 
+def linear_problems(jobs):
+    """The llmrec_linear_problem_t array of [(X, W, bias, out, bias_scale)] (bias / bias_scale: a tensor or None)."""
+    arr = (LinearProblem * len(jobs))()
+    for i, (X, W, b, out, bscale) in enumerate(jobs):
+        arr[i].X, arr[i].ldx, arr[i].M, arr[i].K = X.data_ptr(), _ld(X), X.shape[0], X.shape[1]
+        arr[i].W, arr[i].ldw, arr[i].bias = W.data_ptr(), _ld(W), _ptr(b)
+        arr[i].Y, arr[i].ldy = out.data_ptr(), _ld(out)
+        arr[i].bias_scale = _ptr(bscale)
+    return arr
+
+
 def linear_fwd_grouped(jobs, N: int, precision: str = "f32"):
     """jobs: list of (X, W, bias, out) or (X, W, bias, out, bias_scale) - one launch. precision "f32": exact fp32 MFMA
     (llmrec_linear_fwd_grouped_f32); "bf16x3": three-term bf16 split, six bf16 MFMAs, fp32-class
     error (llmrec_linear_fwd_grouped_bf16x3). bias_scale [M]: out[r] = X[r] W^T + bias_scale[r] * bias."""
-    arr = (LinearProblem * len(jobs))()
-    for i, job in enumerate(jobs):
-        X, W, b, out = job[:4]
-        _need_gpu(X, W, b, out)
-        arr[i].bias_scale = job[4].data_ptr() if len(job) > 4 and job[4] is not None else None
-        arr[i].X, arr[i].ldx, arr[i].M, arr[i].K = X.data_ptr(), _ld(X), X.shape[0], X.shape[1]
-        arr[i].W, arr[i].ldw, arr[i].bias = W.data_ptr(), _ld(W), (b.data_ptr() if b is not None else None)
-        arr[i].Y, arr[i].ldy = out.data_ptr(), _ld(out)
+    for job in jobs:
+        _need_gpu(*job[:4])
+    arr = linear_problems([tuple(job[:4]) + (job[4] if len(job) > 4 else None,) for job in jobs])
     name = {"f32": "llmrec_linear_fwd_grouped_f32", "bf16x3": "llmrec_linear_fwd_grouped_bf16x3"}[precision]
     _lib.call(name, len(jobs), arr, N, _stream())
 

@@ -8,7 +8,7 @@ operands, the formulas of reference() and linear_bound - with ONE substitution: 
 The rounding is an input transformation, not an error of the kernel, so the bound keeps its (deg + 6) u: it does not widen by the
 2^-9 of a bf16 rounding, and that is what lets it tell a kernel that gathered the fp32 rows from one that gathered the bf16 ones.
 
-rn_bf16_bits restates the bit formula of the kernels (spmm_body.h: rn_bf16_bits, the idiom of topk.hip's tk_rn_bf16_bits):
+rn_bf16_bits restates the bit formula of the kernels (common.h: rn_bf16_bits, which spmm_body.h and topk.hip share):
     b = bits(x);  bf16 = (b + 0x7fff + ((b >> 16) & 1)) >> 16        (NaN -> 0x7fc0)
 """
 from __future__ import annotations

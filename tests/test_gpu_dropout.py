@@ -13,7 +13,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import _dropout_ref as R
-from tests._dropin import load_dropin, golden_argv
+from tests._dropin import golden_argv
+from tests._step_env import fused_trainer
 from tests.conftest import GoldenCase
 from tests.test_gpu_step import RTOL, TRAINABLE, rel
 
@@ -107,11 +108,10 @@ def test_counter_is_read_without_a_ticket_and_advanced_once_with_one():
         ops.dropout_rows_(torch.zeros(4, 4), p, seed, step, tag)         # a CPU tensor: no fallback
 
 
-def _trainer(extra, seed=None):
+def _trainer(monkeypatch, env, extra, seed=None):
     g = GoldenCase("nf_tiny")
-    m = load_dropin(golden_argv(g) + list(extra))
-    m.set_seed(g.args["seed"] if seed is None else seed)
-    return g, m, m.Trainer(data_config={})
+    m, tr, _, _ = fused_trainer(monkeypatch, golden_argv(g) + list(extra), env, seed=g.args["seed"] if seed is None else seed)
+    return g, m, tr
 
 
 def _batch(g, s):
@@ -141,8 +141,7 @@ def _autograd_with_injected_masks(monkeypatch, p, n_steps):
     call order of Models.forward: image = slice 0, text = slice 1, the user profile = tag 1, attribute k = slice 2 + k. Computed once."""
     if (p, n_steps) in _AUTOGRAD:
         return _AUTOGRAD[(p, n_steps)]
-    monkeypatch.setenv("LLMREC_FUSED", "0")
-    g, m, tr = _trainer(["--drop_rate", str(p)])
+    g, m, tr = _trainer(monkeypatch, {"LLMREC_FUSED": "0"}, ["--drop_rate", str(p)])
     assert tr._fused_step() is False
     model, seed = tr.model_mm, m.args.seed
     d, S = model.embedding_dim, 2 + len(model.item_feats)
@@ -178,12 +177,9 @@ def test_fused_step_matches_autograd_with_the_same_masks(path, monkeypatch):
     from llmrec_amd.fused import FusedStep
     p, n_steps = 0.5, 3
     want = _autograd_with_injected_masks(monkeypatch, p, n_steps)
-    monkeypatch.setenv("LLMREC_FUSED", "1")
-    monkeypatch.setenv("LLMREC_FUSED_DROPOUT", "1")
-    monkeypatch.setenv("LLMREC_GRAPH", "1" if path == "graph" else "0")
-    monkeypatch.setenv("LLMREC_GEMM", "f32" if path == "f32" else "bf16x3")
-    monkeypatch.setenv("LLMREC_STREAMS", "1" if path == "streams" else "0")
-    g, m, tr = _trainer(["--drop_rate", str(p)])
+    env = {"LLMREC_FUSED": "1", "LLMREC_FUSED_DROPOUT": "1", "LLMREC_GRAPH": "1" if path == "graph" else "0",
+           "LLMREC_GEMM": "f32" if path == "f32" else "bf16x3", "LLMREC_STREAMS": "1" if path == "streams" else "0"}
+    g, m, tr = _trainer(monkeypatch, env, ["--drop_rate", str(p)])
     fused = tr._fused_step()
     assert isinstance(fused, FusedStep) and fused.drop_rate == p and fused.drop_seed == m.args.seed and fused.preprop is False
     got = _run_steps(g, tr, n_steps)
@@ -202,15 +198,11 @@ def test_fused_step_matches_autograd_with_the_same_masks(path, monkeypatch):
     print("dropout step parity [%s]: worst relative error %.2e at %s" % (path, worst[0], worst[1]))
 
 
-def _step_object(monkeypatch, cls=None, preprop=None, **kw):
+def _step_object(monkeypatch, env=None, cls=None, preprop=None, **kw):
     """A fresh drop-in Trainer (seeded: identical initialisation) and a step object of the given class over its model."""
     from llmrec_amd import ops
     from llmrec_amd.fused import FusedStep
-    if preprop is None:
-        monkeypatch.delenv("LLMREC_PREPROPAGATE", raising=False)
-    else:
-        monkeypatch.setenv("LLMREC_PREPROPAGATE", preprop)
-    g, m, tr = _trainer([])
+    g, m, tr = _trainer(monkeypatch, dict(env or {}, **({} if preprop is None else {"LLMREC_PREPROPAGATE": preprop})), [])
     graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(tr.ui_graph), "iu": ops.operand_from_sparse_tensor(tr.iu_graph)})
     a = m.args
     b_max = max(g.z["step%d/users" % s].size for s in range(g.n_steps))
@@ -230,10 +222,10 @@ def _state(tr, step):
 def test_graph_replays_draw_new_masks_and_same_seed_runs_agree(monkeypatch):
     """One capture (its warm-up is a real step) + three replays = four eager steps of a second object in the same state: every parameter
     and both AdamW moments, torch.equal. The counter lives on the device: it reads 4 on both. Another drop_seed trains other parameters."""
-    monkeypatch.setenv("LLMREC_GRAPH", "1"); monkeypatch.setenv("LLMREC_STREAMS", "0")
-    g, _, tr_g, st_g = _step_object(monkeypatch, drop_rate=0.5, drop_seed=7)
-    _, _, tr_e, st_e = _step_object(monkeypatch, drop_rate=0.5, drop_seed=7)
-    _, _, tr_o, st_o = _step_object(monkeypatch, drop_rate=0.5, drop_seed=8)
+    env = {"LLMREC_GRAPH": "1", "LLMREC_STREAMS": "0"}
+    g, _, tr_g, st_g = _step_object(monkeypatch, env, drop_rate=0.5, drop_seed=7)
+    _, _, tr_e, st_e = _step_object(monkeypatch, env, drop_rate=0.5, drop_seed=7)
+    _, _, tr_o, st_o = _step_object(monkeypatch, env, drop_rate=0.5, drop_seed=8)
     tr_g.model_mm.train(); tr_e.model_mm.train(); tr_o.model_mm.train()
     batch = _batch(g, 0)
     st_g.capture(*batch)
@@ -279,11 +271,11 @@ def test_evaluation_is_dropout_free_and_leaves_the_counter(monkeypatch):
 def test_defaults_are_unchanged_and_unsupported_combinations_raise(monkeypatch):
     from llmrec_amd.dp import DataParallelStep
     from llmrec_amd.fused import FusedStep
-    monkeypatch.setenv("LLMREC_STREAMS", "0")
-    g, m, tr_a, plain = _step_object(monkeypatch)                        # the constructor as every caller wrote it so far
-    _, _, tr_b, zero = _step_object(monkeypatch, drop_rate=0.0)
-    _, _, tr_c, ref_order = _step_object(monkeypatch, preprop="0", drop_rate=0.0)
-    _, _, tr_d, half = _step_object(monkeypatch, drop_rate=0.5, drop_seed=1)
+    env = {"LLMREC_STREAMS": "0"}
+    g, m, tr_a, plain = _step_object(monkeypatch, env)                   # the constructor as every caller wrote it so far
+    _, _, tr_b, zero = _step_object(monkeypatch, env, drop_rate=0.0)
+    _, _, tr_c, ref_order = _step_object(monkeypatch, env, preprop="0", drop_rate=0.0)
+    _, _, tr_d, half = _step_object(monkeypatch, env, drop_rate=0.5, drop_seed=1)
     batch = _batch(g, 0)
     for tr, st in ((tr_a, plain), (tr_b, zero), (tr_c, ref_order), (tr_d, half)):
         tr.model_mm.train()
@@ -304,10 +296,8 @@ def test_defaults_are_unchanged_and_unsupported_combinations_raise(monkeypatch):
         FusedStep(*args, drop_rate=0.5)
     monkeypatch.delenv("LLMREC_PREPROPAGATE")
     # the drop-in: the switch alone changes nothing at --drop_rate 0, and --drop_rate > 0 without it leaves the fused step
-    monkeypatch.setenv("LLMREC_FUSED_DROPOUT", "1")
-    _, _, tr = _trainer(["--drop_rate", "0"], seed=3)
+    _, _, tr = _trainer(monkeypatch, {"LLMREC_STREAMS": "0", "LLMREC_FUSED_DROPOUT": "1"}, ["--drop_rate", "0"], seed=3)
     fused = tr._fused_step()
     assert isinstance(fused, FusedStep) and fused.drop_rate == 0.0 and fused.preprop == plain.preprop and not hasattr(fused, "drop_step")
-    monkeypatch.delenv("LLMREC_FUSED_DROPOUT")
-    _, _, tr = _trainer(["--drop_rate", "0.5"], seed=3)
+    _, _, tr = _trainer(monkeypatch, env, ["--drop_rate", "0.5"], seed=3)
     assert tr._fused_step() is False

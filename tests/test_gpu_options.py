@@ -9,22 +9,22 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests._dropin import load_dropin, golden_argv
+from tests._dropin import golden_argv
+from tests._step_env import fused_trainer
 from tests.conftest import GoldenCase
 
 
-def _trainer(extra, seed=3):
+def _trainer(monkeypatch, extra, seed=3):
     g = GoldenCase("nf_tiny")
-    m = load_dropin(golden_argv(g) + list(extra))
-    m.set_seed(seed)
-    return g, m, m.Trainer(data_config={})
+    m, tr, _, _ = fused_trainer(monkeypatch, golden_argv(g) + list(extra), {}, seed=seed)         # (no switch set: every default)
+    return g, m, tr
 
 
-def test_test_flag_full_gives_the_same_ranking_metrics_plus_auc():
-    g, m, tr = _trainer([])
+def test_test_flag_full_gives_the_same_ranking_metrics_plus_auc(monkeypatch):
+    g, m, tr = _trainer(monkeypatch, [])
     users = g.z["eval/users"].tolist()
     part = tr.test(users, is_val=False)
-    g2, m2, tr2 = _trainer(["--test_flag", "full"])
+    g2, m2, tr2 = _trainer(monkeypatch, ["--test_flag", "full"])
     full = tr2.test(users, is_val=False)
     for k in ("precision", "recall", "ndcg", "hit_ratio"):
         assert np.allclose(part[k], full[k], rtol=0, atol=1e-12), k
@@ -51,8 +51,8 @@ def test_test_flag_full_gives_the_same_ranking_metrics_plus_auc():
     assert 0.0 < full["auc"] < 1.0 and part["auc"] == 0.0
 
 
-def test_mask_branch_runs_on_the_modular_path_and_masks_rows():
-    g, m, tr = _trainer(["--mask", "True", "--mask_rate", "0.25", "--att_re_rate", "0.001"])
+def test_mask_branch_runs_on_the_modular_path_and_masks_rows(monkeypatch):
+    g, m, tr = _trainer(monkeypatch, ["--mask", "True", "--mask_rate", "0.25", "--att_re_rate", "0.001"])
     assert tr._fused_step() is False                                # the fused step steps aside
     model = tr.model_mm
     before_u = model.user_feats.clone()
@@ -69,13 +69,13 @@ def test_mask_branch_runs_on_the_modular_path_and_masks_rows():
     # the restoration loss reaches the model (loss differs from the unmasked step) but the decoder's optimizer never steps (reference main.py:276-278)
     for a, b in zip(dec_before, tr.decoder.parameters()):
         assert torch.equal(a, b.detach())
-    g0, m0, tr0 = _trainer([])
+    g0, m0, tr0 = _trainer(monkeypatch, [])
     loss0, _, _ = tr0.train_step(users, pos, neg)
     assert abs(float(loss) - float(loss0)) > 1e-7
 
 
-def test_mask_rate_without_mask_flag_still_masks_users_and_leaves_the_fused_step():
-    g, m, tr = _trainer(["--mask_rate", "0.2"])
+def test_mask_rate_without_mask_flag_still_masks_users_and_leaves_the_fused_step(monkeypatch):
+    g, m, tr = _trainer(monkeypatch, ["--mask_rate", "0.2"])
     assert tr._fused_step() is False                                # reference Models.py:139-142 masks users whenever mask_rate > 0
     before = tr.model_mm.user_feats.clone()
     users, pos, neg = (torch.tensor(g.z["step0/" + n]).cuda() for n in ("users", "pos", "neg"))
@@ -84,8 +84,8 @@ def test_mask_rate_without_mask_flag_still_masks_users_and_leaves_the_fused_step
     assert abs(int(changed.sum()) - int(0.2 * tr.model_mm.n_users)) <= 1
 
 
-def test_dropout_is_inverted_dropout_in_training_and_identity_in_eval():
-    g, m, tr = _trainer(["--drop_rate", "0.5"])
+def test_dropout_is_inverted_dropout_in_training_and_identity_in_eval(monkeypatch):
+    g, m, tr = _trainer(monkeypatch, ["--drop_rate", "0.5"])
     assert tr._fused_step() is False
     model = tr.model_mm
     model.eval()

@@ -19,7 +19,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests._dropin import load_dropin
+from tests._step_env import fused_trainer, snapshot
 from tests.conftest import GOLDEN
 from oracle import make_trajectory as MT
 
@@ -33,8 +33,6 @@ PATHS = {
     "modular": {"LLMREC_FUSED": "0", "LLMREC_GRAPH": "0"},
 }
 SAME_LAUNCHES = ("fused", "streams0", "graph")          # identical kernels on identical operands: bit-identical results
-_KNOBS = ("LLMREC_FUSED", "LLMREC_GRAPH", "LLMREC_STREAMS", "LLMREC_DEVICE_SAMPLER", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM",
-          "LLMREC_WGRAD_ROWS")
 
 
 @pytest.fixture(scope="module")
@@ -52,27 +50,12 @@ def datasets(tmp_path_factory):
 def _state_of_one_epoch(case, path, root, monkeypatch):
     """Train ONE epoch (and evaluate once) in a fresh Trainer; every tensor the step owns, on the host."""
     meta = json.load(open(os.path.join(GOLDEN, case, "meta.json")))
-    for k in _KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in PATHS[path].items():
-        monkeypatch.setenv(k, v)
     argv = ["--dataset", meta["config"]["dataset"], "--data_path", root + "/"] + meta["config"]["argv"] + ["--epoch", "1"]
-    m = load_dropin(argv)
+    m, tr, _, _ = fused_trainer(monkeypatch, argv, PATHS[path])
     m._progress = lambda it: it
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
-    tr.logger.logging = lambda s: None
     tr.train()
     torch.cuda.synchronize()
-    out = {}
-    for name, p in tr.model_mm.named_parameters():
-        out["p/" + name] = p.detach().cpu().clone()
-        st = tr.optimizer.state.get(p) if hasattr(tr.optimizer, "state") else None
-        if st is not None and isinstance(st, tuple):
-            out["m/" + name], out["v/" + name] = st[0].detach().cpu().clone(), st[1].detach().cpu().clone()
-    if tr._fused:
-        out["E_u"], out["E_i"] = tr._fused.E_u.detach().cpu().clone(), tr._fused.E_i.detach().cpu().clone()
-    return out
+    return snapshot(tr, tr._fused, ("E_u", "E_i") if tr._fused else (), grads=False, cpu=True)
 
 
 def _diff(a, b):

@@ -269,21 +269,13 @@ def test_refused_groups_launch_nothing(ops, graphs, sampler_world):
 
 # ---- the whole step --------------------------------------------------------------------------------------------------------------
 def _six_steps(root, refuse, graph, monkeypatch):
-    from tests._dropin import load_dropin
+    from tests._step_env import fused_trainer, snapshot
     from tests.conftest import GOLDEN
     from llmrec_amd.fused import FusedStep
     meta = json.load(open(os.path.join(GOLDEN, "nf_mid_lr", "meta.json")))
-    for k in ("LLMREC_STREAMS", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM", "LLMREC_WGRAD_ROWS"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1"}.items():
-        monkeypatch.setenv(k, v)
+    env = {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1"}
     argv = ["--dataset", meta["config"]["dataset"], "--data_path", root + "/"] + meta["config"]["argv"] + ["--epoch", "1"]
-    m = load_dropin(argv)
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
-    tr.logger.logging = lambda s: None
-    tr.model_mm.train()
-    step, batcher = tr._fused_step(), tr._device_batcher()
+    _, tr, step, batcher = fused_trainer(monkeypatch, argv, env, train=True, step=True, batcher=True)
     assert step and not step.multi_stream and step.fold and step.wgrad_rows
     step._refuse_guests = refuse
     batches, calls = [], []
@@ -303,14 +295,10 @@ def _six_steps(root, refuse, graph, monkeypatch):
             batches.append(step.static_block.clone())
         monkeypatch.setattr(_lib, "_invoke", invoke)
     torch.cuda.synchronize()
-    out = {"scal": step.scal.clone(), "batch": step.static_block.clone(), "step_dev": batcher.step_dev.clone(), "sums": step.epoch_sums.clone()}
+    out = snapshot(tr, step, ("scal", "static_block", "epoch_sums"), grads=False)
+    out["step_dev"] = batcher.step_dev.clone()
     for i, b in enumerate(batches):
         out["batch%d" % i] = b
-    for name, p in tr.model_mm.named_parameters():
-        out["p/" + name] = p.detach().clone()
-        stt = tr.optimizer.state.get(p)
-        if stt is not None and isinstance(stt, tuple):
-            out["m/" + name], out["v/" + name] = stt[0].detach().clone(), stt[1].detach().clone()
     return out, calls
 
 

@@ -8,12 +8,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests._dropin import load_dropin, golden_argv
+from tests._step_env import fused_trainer
 from llmrec_amd.synth import DATASET_KEYS
 
 TRAINABLE = ["image_trans.weight", "image_trans.bias", "text_trans.weight", "text_trans.bias",
              "user_trans.weight", "user_trans.bias", "item_trans.weight", "item_trans.bias",
              "user_id_embedding.weight", "item_id_embedding.weight"]
 RTOL = 1e-4          # north_star: loss / embeddings within 1e-4 relative
+IN_GRAPH_SAMPLER = {"LLMREC_DEVICE_SAMPLER": "1", "LLMREC_GRAPH": "1", "LLMREC_FUSED": "1"}
 
 
 def rel(a, b):
@@ -29,14 +31,10 @@ def test_training_steps_and_eval_match_reference(golden, path, monkeypatch):
     fused_reference_order = fused with projection then propagation, A (F W^T), as the reference orders them; *_unfolded = LLMREC_FOLD=0, the
     36-launch step of round 4 (separate sum-of-squares, AdamW-counter, loss-value, assembly, axpy and row clean-up launches)."""
     assert torch.cuda.is_available()
-    monkeypatch.setenv("LLMREC_FUSED", "0" if path == "modular" else "1")
-    monkeypatch.setenv("LLMREC_GRAPH", "1" if path.startswith("graph") else "0")
-    monkeypatch.setenv("LLMREC_FOLD", "0" if path.endswith("_unfolded") else "1")
-    monkeypatch.setenv("LLMREC_GEMM", "f32" if path == "fused_f32" else "bf16x3")
-    monkeypatch.setenv("LLMREC_PREPROPAGATE", "0" if path == "fused_reference_order" else "1")
-    m = load_dropin(golden_argv(golden))
-    m.set_seed(golden.args["seed"])
-    tr = m.Trainer(data_config={})
+    env = {"LLMREC_FUSED": "0" if path == "modular" else "1", "LLMREC_GRAPH": "1" if path.startswith("graph") else "0",
+           "LLMREC_FOLD": "0" if path.endswith("_unfolded") else "1", "LLMREC_GEMM": "f32" if path == "fused_f32" else "bf16x3",
+           "LLMREC_PREPROPAGATE": "0" if path == "fused_reference_order" else "1"}
+    m, tr, _, _ = fused_trainer(monkeypatch, golden_argv(golden), env, seed=golden.args["seed"])
     keys = DATASET_KEYS[golden.dataset]
     detail = set(golden.detail_steps())
     bpr_log = []
@@ -87,30 +85,20 @@ def test_training_steps_and_eval_match_reference(golden, path, monkeypatch):
         assert [int(x) for x in idx[row] if x >= 0] == [int(x) for x in gold[row] if x >= 0], row
 
 
-def test_device_sampler_epoch_runs(golden):
+def test_device_sampler_epoch_runs(golden, monkeypatch):
     """LLMREC_DEVICE_SAMPLER=1: one epoch trains and evaluates without the host sampler."""
-    import os
-    os.environ["LLMREC_DEVICE_SAMPLER"] = "1"
-    try:
-        m = load_dropin(golden_argv(golden))
-        m.set_seed(1)
-        tr = m.Trainer(data_config={})
-        u, p, n = tr.sample_batch()
-        assert u.is_cuda and u.numel() >= golden.args["batch_size"]
-        loss, _, _ = tr.train_step(u, p, n)
-        assert np.isfinite(float(loss))
-    finally:
-        os.environ.pop("LLMREC_DEVICE_SAMPLER", None)
+    _, tr, _, _ = fused_trainer(monkeypatch, golden_argv(golden), {"LLMREC_DEVICE_SAMPLER": "1"}, seed=1)
+    u, p, n = tr.sample_batch()
+    assert u.is_cuda and u.numel() >= golden.args["batch_size"]
+    loss, _, _ = tr.train_step(u, p, n)
+    assert np.isfinite(float(loss))
 
 
 def test_in_graph_sampler_steps_run_and_learn(golden, monkeypatch):
     """LLMREC_DEVICE_SAMPLER=1 + LLMREC_GRAPH=1: a step is one graph replay that samples its own batch
     (llmrec_sample_batch with the device step counter). Batches differ step to step, the loss is finite
     and the parameters move."""
-    monkeypatch.setenv("LLMREC_DEVICE_SAMPLER", "1"); monkeypatch.setenv("LLMREC_GRAPH", "1"); monkeypatch.setenv("LLMREC_FUSED", "1")
-    m = load_dropin(golden_argv(golden))
-    m.set_seed(1)
-    tr = m.Trainer(data_config={})
+    _, tr, _, _ = fused_trainer(monkeypatch, golden_argv(golden), IN_GRAPH_SAMPLER, seed=1)
     before = tr.model_mm.item_id_embedding.weight.detach().clone()
     seen = []
     for _ in range(4):
@@ -129,14 +117,11 @@ def test_in_graph_sampler_epoch_sums_on_the_device(golden, monkeypatch):
     """Trainer.train_epoch_sampled: n steps as graph replays (graphs of four + single steps) with the logged scalars summed in double
     inside the graph - equal to the sum of the per-step scalars of the same steps run one replay at a time (same seed: the same
     batches), and the device step counter advanced by exactly n."""
-    monkeypatch.setenv("LLMREC_DEVICE_SAMPLER", "1"); monkeypatch.setenv("LLMREC_GRAPH", "1"); monkeypatch.setenv("LLMREC_FUSED", "1")
     n = 7
-    m = load_dropin(golden_argv(golden)); m.set_seed(1)
-    tr = m.Trainer(data_config={})
+    _, tr, _, _ = fused_trainer(monkeypatch, golden_argv(golden), IN_GRAPH_SAMPLER, seed=1)
     sums = tr.train_epoch_sampled(n).cpu().numpy()
     assert int(tr._device_batcher().step_dev) == n and tr._fused_step().graph_unroll == 4
-    m2 = load_dropin(golden_argv(golden)); m2.set_seed(1)
-    tr2 = m2.Trainer(data_config={})
+    _, tr2, _, _ = fused_trainer(monkeypatch, golden_argv(golden), IN_GRAPH_SAMPLER, seed=1)
     ref = np.zeros(3)
     for _ in range(n):
         ref += np.array([float(x) for x in tr2.train_step_sampled()], dtype=np.float64)
@@ -346,10 +331,7 @@ def test_weight_gradient_geometry_is_relaid_and_the_graph_recaptured_without_an_
     """FusedStep.check_wgrad_geometry: when the row list's length has left the range the captured launch was laid out for, the
     launch is laid out again and the step graph RE-captured with no warm-up step - the trajectory goes on exactly where it was: every later
     step's 8 (mf, emb) pairs and the final parameters still match the reference's golden vectors."""
-    monkeypatch.setenv("LLMREC_FUSED", "1"); monkeypatch.setenv("LLMREC_GRAPH", "1")
-    m = load_dropin(golden_argv(golden))
-    m.set_seed(golden.args["seed"])
-    tr = m.Trainer(data_config={})
+    _, tr, _, _ = fused_trainer(monkeypatch, golden_argv(golden), {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1"}, seed=golden.args["seed"])
     bpr_log = []
     tr._on_bpr = lambda mf, emb: bpr_log.append((mf.detach(), emb.detach()))
     recaptured = 0

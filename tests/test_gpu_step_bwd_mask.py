@@ -13,8 +13,6 @@ pytestmark = pytest.mark.gpu
 
 from tests.test_gpu_reproducible import datasets          # noqa: F401  (the nf_mid_lr dataset fixture)
 
-_KNOBS = ("LLMREC_STREAMS", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM", "LLMREC_WGRAD_ROWS", "LLMREC_BWD_MASK", "LLMREC_CHECK_ZERO")
-
 
 def _valued(t, seed):
     """the sparse adjacency with every value scaled by its own factor: rows are no longer constant, the operand keeps val"""
@@ -25,25 +23,17 @@ def _valued(t, seed):
 
 
 def _steps(root, monkeypatch, mask, n, graph=False, streams=False, check_zero=False, valued=False):
-    from tests._dropin import load_dropin
+    from tests._step_env import fused_trainer, snapshot
     from tests.conftest import GOLDEN
     from llmrec_amd.fused import FusedStep
     meta = json.load(open(os.path.join(GOLDEN, "nf_mid_lr", "meta.json")))
-    for k in _KNOBS:
-        monkeypatch.delenv(k, raising=False)
     env = {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1", "LLMREC_BWD_MASK": mask,
            "LLMREC_STREAMS": "1" if streams else "0", "LLMREC_CHECK_ZERO": "1" if check_zero else "0"}
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     argv = ["--dataset", meta["config"]["dataset"], "--data_path", root + "/"] + meta["config"]["argv"] + ["--epoch", "1"]
-    m = load_dropin(argv)
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
-    tr.logger.logging = lambda s: None
-    tr.model_mm.train()
-    if valued:
+
+    def keep_values(tr):
         tr.ui_graph, tr.iu_graph = _valued(tr.ui_graph, 1), _valued(tr.iu_graph, 2)
-    step, batcher = tr._fused_step(), tr._device_batcher()
+    _, tr, step, batcher = fused_trainer(monkeypatch, argv, env, train=True, prepare=keep_values if valued else None, step=True, batcher=True)
     assert step and step.fold and step.multi_stream == streams
     if valued:
         assert step.iu.bwd.val is not None and not step.bwd_mask and not step.bwd_zero_skip
@@ -58,16 +48,7 @@ def _steps(root, monkeypatch, mask, n, graph=False, streams=False, check_zero=Fa
             step.step_eager(st["users"], st["pos"], st["neg"], st["n_valid"], sampler=FusedStep.sampler_of(batcher, st))
     torch.cuda.synchronize()
     assert int(batcher.step_dev) == n and int(step.row_stamp) >= n       # (the stamp advances once per step)
-    out = {"scal": step.scal.clone(), "out": step.out.clone(), "sums": step.epoch_sums.clone(), "batch": step.static_block.clone(),
-           "dU_cat": step.dU_cat.clone()}
-    for name, p in tr.model_mm.named_parameters():
-        out["p/" + name] = p.detach().clone()
-        if p.grad is not None:
-            out["g/" + name] = p.grad.detach().clone()
-        stt = tr.optimizer.state.get(p)
-        if stt is not None and isinstance(stt, tuple):
-            out["m/" + name], out["v/" + name] = stt[0].detach().clone(), stt[1].detach().clone()
-    return out
+    return snapshot(tr, step, ("scal", "out", "epoch_sums", "static_block", "dU_cat"))
 
 
 def _assert_equal(a, b):

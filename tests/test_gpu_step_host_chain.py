@@ -14,8 +14,6 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ENTRY = "llmrec_linear_fwd_grouped_host_spmm_bf16x3"
-_KNOBS = ("LLMREC_STREAMS", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM", "LLMREC_WGRAD_ROWS", "LLMREC_BWD_MASK", "LLMREC_CHECK_ZERO",
-          "LLMREC_HOST_CHAIN")
 DATASET = "netflix_valid_item"
 
 
@@ -29,22 +27,13 @@ def dataset(tmp_path_factory):
 
 
 def _steps(root, monkeypatch, host, graph):
-    from tests._dropin import load_dropin
+    from tests._step_env import fused_trainer, snapshot
     from llmrec_amd import _lib
     from llmrec_amd.fused import FusedStep
-    for k in _KNOBS:
-        monkeypatch.delenv(k, raising=False)
     env = {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1", "LLMREC_PREPROPAGATE": "1", "LLMREC_HOST_CHAIN": host}
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     argv = ["--dataset", DATASET, "--data_path", root + "/", "--batch_size", "256", "--seed", "2022", "--debug", "--lr", "0.001",
             "--layers", "2", "--embed_size", "64", "--epoch", "1"]
-    m = load_dropin(argv)
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
-    tr.logger.logging = lambda s: None
-    tr.model_mm.train()
-    step, batcher = tr._fused_step(), tr._device_batcher()
+    _, tr, step, batcher = fused_trainer(monkeypatch, argv, env, train=True, step=True, batcher=True)
     assert step and step.fold and step.preprop and not step.multi_stream and step.L == 2 and step.d == 64
     assert step.host_chain == (host == "1")
     assert sum(-(-j[0].shape[0] // 128) for j in step.projection_jobs()) > step._block_slots          # the size rule holds
@@ -64,15 +53,8 @@ def _steps(root, monkeypatch, host, graph):
         n = 4
     torch.cuda.synchronize()
     assert int(batcher.step_dev) == n
-    out = {"scal": step.scal.clone(), "out": step.out.clone(), "sums": step.epoch_sums.clone(), "batch": step.static_block.clone(),
-           "dU_cat": step.dU_cat.clone(), "U_1": step.Ul[0].clone()}
-    for name, p in tr.model_mm.named_parameters():
-        out["p/" + name] = p.detach().clone()
-        if p.grad is not None:
-            out["g/" + name] = p.grad.detach().clone()
-        stt = tr.optimizer.state.get(p)
-        if stt is not None and isinstance(stt, tuple):
-            out["m/" + name], out["v/" + name] = stt[0].detach().clone(), stt[1].detach().clone()
+    out = snapshot(tr, step, ("scal", "out", "epoch_sums", "static_block", "dU_cat"))
+    out["U_1"] = step.Ul[0].clone()
     return out, list(names)
 
 

@@ -19,14 +19,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests._dropin import load_dropin, golden_argv
+from tests._dropin import golden_argv
+from tests._step_env import fused_trainer, set_switches
 from tests.conftest import GoldenCase
 
 EXPECTED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "step_schedule_expected.json")
 WRITE_TO = os.environ.get("LLMREC_STEP_SCHEDULE_WRITE")
 GROUPED = re.compile(r"llmrec_(spmm_multi(_guest)?_f32|fuse_\w+_multi\w*|bpr_multi_\w+|linear_\w+_(grouped|multi)\w*)$")
-KNOBS = ("LLMREC_STREAMS", "LLMREC_FOLD", "LLMREC_PREPROPAGATE", "LLMREC_GEMM", "LLMREC_WGRAD_ROWS", "LLMREC_DEVICE_SAMPLER",
-         "LLMREC_CHECK_ZERO")
 VARIANTS = {
     "default": {},
     "streams": {"LLMREC_STREAMS": "1"},
@@ -89,13 +88,9 @@ def _batch(golden, s):
 
 def _record_second_step(golden, variant, monkeypatch):
     """(recorded list, the step object) of the SECOND training step: the first one sizes the row-listed weight gradient (one read-back)."""
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("LLMREC_FUSED", "1")
-    monkeypatch.setenv("LLMREC_GRAPH", "0")
-    for k, v in VARIANTS[variant].items():
-        monkeypatch.setenv(k, v)
+    env = dict(VARIANTS[variant], LLMREC_FUSED="1", LLMREC_GRAPH="0")
     if variant == "data_parallel":
+        set_switches(monkeypatch, env)
         # DataParallelStep on the same model, one replica, no communicator: _backward with bpr_bwd_done=False and inline_adamw=False
         from llmrec_amd.dp import DataParallelStep
         from tests.test_gpu_step import _dp_replica
@@ -108,10 +103,7 @@ def _record_second_step(golden, variant, monkeypatch):
             n_valid = torch.tensor([u.numel()], dtype=torch.int32, device="cuda")
             step.step_eager(torch.cat([u, pad]), torch.cat([p, pad]), torch.cat([n, pad]), n_valid)
     else:
-        m = load_dropin(golden_argv(golden))
-        m.set_seed(golden.args["seed"])
-        tr = m.Trainer(data_config={})
-        step = tr._fused_step()
+        _, tr, step, _ = fused_trainer(monkeypatch, golden_argv(golden), env, seed=golden.args["seed"], step=True)
         assert step, "the golden configuration runs the fused step"
         run = lambda s: tr.train_step(*_batch(golden, s))
         if variant.startswith("device_sampler"):

@@ -17,7 +17,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from tests._dropin import load_dropin
+from tests._step_env import fused_trainer
 from tests.conftest import GOLDEN
 from oracle import make_trajectory as MT
 
@@ -71,20 +71,14 @@ def test_training_trajectory_tracks_reference(case, path, datasets, monkeypatch)
         pytest.skip("the per-op autograd path runs the nf_mid_lr horizon only (same code, the faster-moving trajectory)")
     z = np.load(os.path.join(GOLDEN, case, "trajectory.npz"))
     meta = json.load(open(os.path.join(GOLDEN, case, "meta.json")))
-    monkeypatch.setenv("LLMREC_FUSED", "0" if path == "modular" else "1")
-    monkeypatch.setenv("LLMREC_GRAPH", "1" if path == "graph" else "0")
+    env = {"LLMREC_FUSED": "0" if path == "modular" else "1", "LLMREC_GRAPH": "1" if path == "graph" else "0"}
     # the order of the two constant products on the item side: forced either way on the two fused paths, LEFT TO THE SHAPE RULE on the graph path
     # (pre-propagated iff U <= I: the Netflix-shaped cases pre-propagate, the MovieLens-shaped one projects first)
-    if path == "graph":
-        monkeypatch.delenv("LLMREC_PREPROPAGATE", raising=False)
-    else:
-        monkeypatch.setenv("LLMREC_PREPROPAGATE", "0" if path == "fused_reference_order" else "1")
-    monkeypatch.delenv("LLMREC_DEVICE_SAMPLER", raising=False)            # host sampler = the reference's sample stream
+    if path != "graph":
+        env["LLMREC_PREPROPAGATE"] = "0" if path == "fused_reference_order" else "1"
     argv = ["--dataset", meta["config"]["dataset"], "--data_path", datasets[case] + "/"] + meta["config"]["argv"]
-    m = load_dropin(argv)
+    m, tr, _, _ = fused_trainer(monkeypatch, argv, env)                   # (no LLMREC_DEVICE_SAMPLER: host sampler = the reference's sample stream)
     m._progress = lambda it: it
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
     epochs, evals, lines = [], [], []
     tr._on_epoch = lambda ep, loss, mf, emb, ret, t: epochs.append((loss, mf, emb))
     orig_test = tr.test                                                   # (every evaluation of train() goes through Trainer.test; since round 6
@@ -94,8 +88,7 @@ def test_training_trajectory_tracks_reference(case, path, datasets, monkeypatch)
         evals.append(np.stack([np.asarray(res[k_], dtype=np.float64) for k_ in ("precision", "recall", "ndcg", "hit_ratio")]))
         return res
     tr.test = test_wrap
-    orig_log = tr.logger.logging
-    tr.logger.logging = lambda s: (lines.append(str(s)), orig_log(s))[1]
+    tr.logger.logging = lambda s: lines.append(str(s))
     best_recall, _ = tr.train()
 
     n_ep = int(z["n_epochs"])
@@ -132,12 +125,8 @@ def test_in_graph_sampler_path_tracks_the_oracle_over_many_steps(datasets, monke
     from llmrec_amd.synth import DATASET_KEYS
     case, n_steps = "nf_mid_lr", 120
     meta = json.load(open(os.path.join(GOLDEN, case, "meta.json")))
-    monkeypatch.setenv("LLMREC_FUSED", "1"); monkeypatch.setenv("LLMREC_GRAPH", "1"); monkeypatch.setenv("LLMREC_DEVICE_SAMPLER", "1")
-    monkeypatch.delenv("LLMREC_PREPROPAGATE", raising=False)
     argv = ["--dataset", meta["config"]["dataset"], "--data_path", datasets[case] + "/"] + meta["config"]["argv"]
-    m = load_dropin(argv)
-    m.set_seed(m.args.seed)
-    tr = m.Trainer(data_config={})
+    m, tr, _, _ = fused_trainer(monkeypatch, argv, {"LLMREC_FUSED": "1", "LLMREC_GRAPH": "1", "LLMREC_DEVICE_SAMPLER": "1"})
     keys = DATASET_KEYS[meta["config"]["dataset"]]
     cfg = O.Config.from_args(meta["args"], keys)
     data = O.load_dataset(os.path.join(datasets[case], meta["config"]["dataset"]), keys)

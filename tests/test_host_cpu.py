@@ -308,8 +308,10 @@ def test_captured_step_is_single_branch_by_default():
     """hipGraphLaunch of a multi-branch graph can fault on the host, so the fused step runs on ONE stream unless
     LLMREC_STREAMS=1 asks for more, and every stream capture passes that choice to the refusal below."""
     import re
-    src = open(os.path.join(os.path.dirname(_lib.HEADER), "..", "llmrec_amd", "fused.py")).read()
-    assert 'self.multi_stream = os.environ.get("LLMREC_STREAMS", "0") == "1"' in src
+    from tests.test_step_options_cpu import resolve
+    assert not resolve({}).multi_stream
+    assert not any(resolve({"LLMREC_STREAMS": v}).multi_stream for v in ("0", "", "true"))
+    assert resolve({"LLMREC_STREAMS": "1"}).multi_stream
     for f in ("fused.py", "dp.py"):
         src = open(os.path.join(os.path.dirname(_lib.HEADER), "..", "llmrec_amd", f)).read()
         calls = re.findall(r"with _capture_without_gc\(([^)]*)\)", src)
