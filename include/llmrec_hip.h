@@ -380,6 +380,23 @@ int llmrec_linear_wgrad_multi_adamw_bf16x3(int32_t n_targets, const llmrec_wgrad
                                            void* workspace, int64_t workspace_bytes, const llmrec_wgrad_update_t* updates_host,
                                            const float* state3, float lr, float beta1, float beta2, float eps, float weight_decay,
                                            llmrec_stream_t stream);
+/* llmrec_linear_wgrad_multi_adamw_bf16x3 hosting ONE independent SpMM (a problem as llmrec_spmm_multi_f32 takes it) in the CUs its
+ * weight-gradient launch leaves free: a block of that launch owns a whole CU, and a block_budget below the device's CU count lays it
+ * out for fewer blocks than CUs. The launch becomes n_cu blocks - the weight gradient's wg_blocks, unchanged and placed first, then
+ * n_guest = n_cu - wg_blocks guests that run the product's blocks persistently (guest g: blocks g, g + n_guest, ...); the reduction +
+ * AdamW launch follows unchanged. n_cu = the device's CU count, passed by the caller (no device query here). The product depends on
+ * nothing either launch computes and no block waits for another. Gradients, parameters, moments and the product's Y are bit-identical to
+ * llmrec_linear_wgrad_multi_adamw_bf16x3 and llmrec_spmm_f32 in either order: the slab length does not depend on the guest, and the
+ * product's 256-thread blocks keep every row's summation tree. Compiled for the 128-wide organisation (every K % 128 == 0) at N = 64 and
+ * the unmasked float4 product of 33..64 columns weighted by col_scale alone, with or without the init term alpha Z (LLMREC_SPMM_EPI_NONE),
+ * without val, slices, split rows, softmax epilogue, post_scale or row restriction. LLMREC_EUNSUPPORTED before anything is launched -
+ * the caller then issues the two separate calls - for anything else, when wg_blocks >= n_cu (no free CU), when the product's Y overlaps
+ * anything the two launches read or write (every dY, X, row list and count, the workspace, dW / db, parameters, moments, state3) and
+ * when the product's X or Z overlaps anything they write. */
+int llmrec_linear_wgrad_multi_adamw_host_spmm_bf16x3(int32_t n_targets, const llmrec_wgrad_target_t* targets_host, int32_t N,
+                                                     void* workspace, int64_t workspace_bytes, const llmrec_wgrad_update_t* updates_host,
+                                                     const float* state3, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                                     const llmrec_spmm_problem_t* spmm, int32_t n_cu, llmrec_stream_t stream);
 /* Same contract, split precision: each fp32 operand = exact sum of three bf16 numbers, product by the
  * six bf16 MFMAs (v_mfma_f32_16x16x32_bf16, fp32 accumulate) whose terms are >= 2^-24 relative.
  * fp32-roundoff-class error (not the bit-identical fma chain); 3/8 of the fp32 matrix time, so the

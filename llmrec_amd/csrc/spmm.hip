@@ -468,23 +468,31 @@ static bool bytes_overlap(const void* p, int64_t np, const void* q, int64_t nq) 
 }
 
 // One product for the launch of ANOTHER kernel that hosts it in blocks of `tpb` threads (spmm_body.h: spmm_hosted_body; dense.hip's
-// grouped projection): the checks of spmm_prepare, then the narrow shape the hosted body is compiled for, laid out from block 0.
+// grouped projection and multi-target weight gradient): the checks of spmm_prepare, then the two narrow shapes the hosted body is
+// compiled for, laid out from block 0 - the plain whole-row product without an epilogue, and the product weighted by col_scale alone
+// whose only epilogue is the init term alpha Z (finish_row applies it at run time). out.weighted says which; each host takes one.
 // LLMREC_EUNSUPPORTED for anything else - the caller has launched nothing yet.
 int spmm_prepare_hosted(const llmrec_spmm_problem_t& pr, int tpb, SpmmHosted& out) {
     SpmmPrepared pp;
     const int rc = spmm_prepare(pr, pp);
     if (rc != LLMREC_OK) return rc;
     const SpmmArgs& a = pp.a;
+    const bool weighted = pp.variant == SPMM_V_WEIGHTED;
     const char* why = pp.empty ? "the product is empty" : pp.family != 2 ? "not a float4 product of 33..64 columns" :
-                      pp.variant != SPMM_V_PLAIN ? "the operand has val, col_scale or a mask" : a.n_slices != 1 ? "column slices" :
-                      a.n_split_rows > 0 ? "the plan has split rows (a finalize pass)" :
-                      (a.epi_op != LLMREC_SPMM_EPI_NONE || a.Z || a.post_scale) ? "an epilogue (softmax, init term or post_scale)" :
+                      (pp.variant != SPMM_V_PLAIN && !weighted) ? "the operand has a mask" : a.val ? "the operand has val" :
+                      a.n_slices != 1 ? "column slices" : a.n_split_rows > 0 ? "the plan has split rows (a finalize pass)" :
+                      (a.epi_op != LLMREC_SPMM_EPI_NONE || a.post_scale) ? "an epilogue (softmax or post_scale)" :
+                      (!weighted && a.Z) ? "an init term on the unweighted product" :
                       (a.y_needed || a.listed_only) ? "a row restriction" : nullptr;
-    if (why) { set_error("spmm (hosted): compiled for the plain whole-row product without an epilogue: %s", why); return LLMREC_EUNSUPPORTED; }
+    if (why) {
+        set_error("spmm (hosted): compiled for the whole-row product, plain without an epilogue or weighted by col_scale with an init term: %s", why);
+        return LLMREC_EUNSUPPORTED;
+    }
     out.a = a;
+    out.weighted = weighted;
     out.blocks = spmm_layout(out.a, kSpmmFamilyLpr[pp.family], 0, tpb);
     if (out.blocks < 0) { set_error("spmm (hosted): too many rows for one launch"); return LLMREC_EUNSUPPORTED; }
-    out.bytes_x = pp.bytes_x; out.bytes_y = pp.bytes_y;
+    out.bytes_x = pp.bytes_x; out.bytes_y = pp.bytes_y; out.bytes_z = pp.bytes_z;
     return LLMREC_OK;
 }
 

@@ -832,10 +832,13 @@ __device__ __forceinline__ void spmm_hosted_body(const SpmmArgs& a, int32_t b, f
 }
 
 // host side of a hosted product (spmm.hip: spmm_prepare_hosted): the arguments laid out from block 0 for blocks of the host's size,
-// the block count, and the extents of what the product reads (X) and writes (Y) for the host's aliasing check
+// the block count, and the extents of what the product reads (X, Z) and writes (Y) for the host's aliasing check.
+// weighted: which of the two hosted shapes it is - false: the plain product (spmm_hosted_body<.., false, ..>: the projection's guest);
+// true: the product weighted by col_scale alone, with or without the init term alpha Z (<.., true, ..>: the weight gradient's guest).
 struct SpmmHosted {
     SpmmArgs a;
-    int64_t blocks, bytes_x, bytes_y;
+    int64_t blocks, bytes_x, bytes_y, bytes_z;
+    bool weighted;
 };
 int spmm_prepare_hosted(const llmrec_spmm_problem_t& pr, int tpb, SpmmHosted& out);
 

@@ -14,14 +14,15 @@ main.py:228-278); what changes is the organisation:
     gradients, row-listed, in one, with their AdamW in the reduction launch) in split-precision bf16x3 arithmetic (LLMREC_GEMM=f32: exact);
   * independent products share grouped SpMM launches on ONE stream - the sampler, the scatter plan with the reach marks and the loss
     values ride three of them as guests (_Rider), and the ID chain's first product rides the projection launch as its trailing blocks
-    (host_chain) - or run as chains on four HIP streams (LLMREC_STREAMS=1: fork/join = graph edges);
+    (host_chain), and the first product of its backward without a partner runs in the CUs the weight-gradient launch leaves free
+    (host_wgrad) - or run as chains on four HIP streams (LLMREC_STREAMS=1: fork/join = graph edges);
   * the embedding tables' AdamW reads its gradient where it is formed (the user table's is inv * dE_u) and the row-wise clean-up of the
     scatter targets rides in the item table's AdamW launch;
   * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
 Falls outside its scope (use the modular path): the --mask branch, and dropout > 0 unless the step is built for it (drop_rate=: the
 project's own counter-based masks on the device, llmrec_dropout_rows_f32 - step_options.resolve, "DROPOUT").
-Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 (the
-chain's first product in an SpMM group of its own launch) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
+Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 / fwd (no hosted
+product: the chain's products in SpMM launches of their own / the forward's hosted only) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
 FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
 gradients before AdamW). Every switch is decided in ONE place, llmrec_amd/step_options.py (resolve(): a pure function of the variables,
 the shapes and the class switches, with each switch's rationale and measured figures); FusedStep.__init__ copies its record and allocates.
@@ -103,7 +104,10 @@ class FusedStep:
     # resident blocks the weight-gradient launch is laid out for (llmrec_wgrad_target_t.block_budget; 0 = 256, one per CU). A block of
     # that launch owns its CU's whole register file, so a 256-block round starves whatever runs beside it: the ID chain's last SpMM took
     # 81 us beside it and 12 us alone and, once the row list had shortened the GEMM, had become the step's tail. 224 blocks leave 32 CUs
-    # to the other streams: 256 / 240 / 224 / 208 / 192 blocks -> 0.474 / 0.459 / 0.454 / 0.456 / 0.469 ms per step on one box.
+    # free: 256 / 240 / 224 / 208 / 192 blocks -> 0.474 / 0.459 / 0.454 / 0.456 / 0.469 ms per step on one box (measured on four streams,
+    # LLMREC_STREAMS=1, where the other streams' kernels use those CUs). On ONE stream - the default - nothing else is in flight, and
+    # the 32 CUs run the ID chain's hosted backward product inside the same launch (host_wgrad, _host_wgrad_applies). The budget cannot
+    # move without changing dW's bits: it sets the slab length (csrc/dense.hip: wgrad_multi_slab_rows), i.e. the summation partition.
     wgrad_blocks = 224
     WGRAD_ROWS = INLINE_ADAMW = FOLD = True      # schedule switches of the class: DataParallelStep (llmrec_amd/dp.py) turns all three off
 
@@ -121,7 +125,7 @@ class FusedStep:
         self.c_m, self.c_u, self.c_a = rates
         self.b_max = b_max
         # every switch of the step - multi_stream, gemm, preprop, wgrad_rows, inline_adamw, fold, bwd_mask, bwd_zero_skip, host_chain,
-        # check_zero and the validated drop_rate - is decided once, with its rationale, in step_options.resolve(); below: allocation only
+        # host_wgrad, check_zero and the validated drop_rate - is decided once, with its rationale, in step_options.resolve(); below: allocation only
         opts = step_options.resolve(None, n_users=self.U, n_items=self.I, d=d, n_attr=len(self.keys), drop_rate=drop_rate,
                                     wgrad_rows_default=self.WGRAD_ROWS, inline_adamw_default=self.INLINE_ADAMW, fold_default=self.FOLD,
                                     bwd_nnz=self.iu.bwd.nnz, bwd_valued=self.iu.bwd.val is not None,
@@ -693,10 +697,10 @@ class FusedStep:
         # dE_u / dE_i hold the scattered rows now. (Only the fused loss launch stamps the rows it touched; keep: alive until the launch.)
         fuse, keep = self._fuse_bwd_problems(hp.feat_reg_decay * 0.5 / self.I * replicated_scale, stamped=bpr_bwd_done)
         schedule = self._backward_streams if self.multi_stream else self._backward_one_stream
-        schedule(probs, (users, pos, neg, n_valid), fuse, side_work, masked=bpr_bwd_done and self.bwd_mask)
+        deferred = schedule(probs, (users, pos, neg, n_valid), fuse, side_work, masked=bpr_bwd_done and self.bwd_mask)
         if self.drop_rate > 0:
             self._dropout_backward()
-        self._weight_gradients(ev_reach)
+        self._weight_gradients(ev_reach, deferred)
         self._join(self.s2)
         if self.fold and side_work is not None:                          # (four streams: side_work ran on a stream of its own)
             self._join(self.s3)
@@ -853,19 +857,50 @@ class FusedStep:
         Where side_work carries a guest descriptor (loss_backward's rider), its loss-value launch rides the FIRST group's launch instead of
         running in the chain head. It reads `saved` (the scores and selection launches), the fusion launch's partial sums and n_valid; it
         writes out, the four totals of each problem in `saved`, scal and the epoch sums - read by the host after the step. Its host reads
-        tmpI, dE_u, U_L, dI_cat and dprof_u and writes tmpU, dU_cat and dprof_i: disjoint."""
+        tmpI, dE_u, U_L, dI_cat and dprof_u and writes tmpU, dU_cat and dprof_i: disjoint.
+        HOSTED (host_wgrad, _host_wgrad_applies): the groups that have a side or profile partner run here; the chain's first product
+        without one, the products behind it and the chain's tail are handed on - returned as (chain[k:], probs, batch) - and
+        _weight_gradients runs them in and behind its launch. Read / write sets of that product beside the launch: _weight_gradients."""
         if not self.fold:
             _call("llmrec_fuse_bwd_src_multi_f32", 2, fuse, self.d)
         rides = side_work is not None and side_work.guest is not None
         self._chain_head(None if rides else side_work, fuse if self.fold else None)
         chain, (side, prof) = self._chain_bwd_jobs(), self._side_bwd_jobs(masked)
         self._check_mask_promise(masked)
-        for k, jobs in enumerate(zip_longest(chain, side, prof)):
+        n_shared = max(len(side), len(prof))
+        hosting = len(chain) > n_shared and self._host_wgrad_applies(chain[n_shared])
+        for k, jobs in enumerate(zip_longest(chain[:n_shared] if hosting else chain, side, prof)):
             self._spmm_group(jobs, side_work if k == 0 and rides else None)
         self._check_mask_promise(masked, done=True)
         if self.gemm != "bf16x3" and not self.drop_rate > 0:             # (bf16x3: user_trans' gradient is in the multi-target launch; dropout: _dropout_backward)
             self._wgrad(self.dP_usr, self.m.user_feats, self.m.user_trans, False, ws=self.ws_wgrad_b)
+        if hosting:
+            return chain[n_shared:], probs, batch
         self._chain_tail(probs, batch)
+        return None
+
+    def _wgrad_multi_workspace(self, targets):
+        """The multi-target weight gradient's workspace, sized at the first backward (needs the gradient tensors); False: the targets are
+        outside that launch's fast path."""
+        if self.ws_wgrad_multi is None:
+            need = ops.linear_wgrad_multi_workspace(targets, self.wgrad_blocks)
+            self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=self.dU_cat.device) if need >= 0 else False
+        return self.ws_wgrad_multi
+
+    def _host_wgrad_applies(self, job) -> bool:
+        """Whether the chain product `job` (a, X, Y, kwargs of _spmm) is handed to the weight-gradient launch (host_wgrad). The mirror of
+        _project_all_hosting's gate: one stream, the folded step with the Linears' AdamW in the reduction launch (the hosting entry
+        point is that call's), bf16x3 at d = 64 without dropout (whose launches sit between the schedule and the weight gradients), a
+        latency-bound product, the multi-target fast path, and the forward host's size rule - more 128-row projection units than block
+        slots: below it the step is too small for the chip either way (and tests/step_schedule_expected.json's steps stay as recorded).
+        The library still has the last word (_weight_gradients: a refused pair runs the product by its own launch)."""
+        a = job[0]
+        if not (self.host_chain and self.host_wgrad and not self._refuse_guests and not self.multi_stream and self.fold and self.inline_adamw
+                and self.gemm == "bf16x3" and self.d == 64 and self.drop_rate == 0 and a.nnz < ops.SPMM_LATENCY_NNZ
+                and sum(-(-j[0].shape[0] // 128) for j in self.projection_jobs()) > self._block_slots):
+            return False
+        dY_cat = self.dU_cat if self.preprop else self.dP_cat
+        return self._wgrad_multi_workspace(self.wgrad_targets(dY_cat, self.dP_usr)) is not False
 
     def _backward_streams(self, probs, batch, fuse, side_work, masked=False):
         """The backward up to the weight gradients on four streams (LLMREC_STREAMS=1: the A/B reference of the one-stream schedule):
@@ -904,10 +939,18 @@ class FusedStep:
             self._spmm_jobs(side)
         self._check_mask_promise(masked, done=True)
 
-    def _weight_gradients(self, ev_reach=None):
+    def _weight_gradients(self, ev_reach=None, deferred=None):
         """The four Linears' gradients from dU_cat (pre-propagated; else dP_cat) and dP_usr, and - with inline_adamw - their update.
-        ev_reach: four streams - the event behind the row list (step_eager's record)."""
+        ev_reach: four streams - the event behind the row list (step_eager's record).
+        deferred: (chain[k:], probs, batch) handed on by _backward_one_stream (host_wgrad) - chain[k] runs INSIDE the weight-gradient
+        launch, in the CUs its 224-block layout leaves free; chain[k + 1:] and the chain's tail follow the reduction launch. Read / write sets:
+          hosted product  reads bufI (the chain's previous product, earlier in stream order), dE_u (the loss backward; cleared by the
+                    tail, which now runs behind this launch), the adjacency and its column scale; writes bufU, read first by chain[k + 1].
+          its host  reads dU_cat, dP_usr, the constant operands and the row list; writes its workspace - then the reduction launch the
+                    Linears' gradients, parameters and moments. Disjoint (the library checks the extents and refuses an overlap).
+        A refused pair: chain[k] by its own launch right ahead of the weight gradient, then the same order. Bit-identical either way."""
         m, S, d = self.m, self.S, self.d
+        hosted = deferred[0][0] if deferred is not None else None
         dY_cat = self.dU_cat if self.preprop else self.dP_cat
         targets = self.wgrad_targets(dY_cat, self.dP_usr)
         item_pairs, text_pairs, image_pairs = targets[0][0], targets[2][0], targets[3][0]
@@ -919,16 +962,26 @@ class FusedStep:
             # operands nothing separates the two launches in time any more, and side by side each ran at half speed (the chip is
             # power-bound here: profiles/experiments/r03_wgrad.md). The bias gradients (row-weighted when pre-propagated) come out of it too.
             self._join(self.s1)                                          # dP_usr (the profile chain is long done by now)
-            if self.ws_wgrad_multi is None:
-                need = ops.linear_wgrad_multi_workspace(targets, self.wgrad_blocks)
-                self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=dY_cat.device) if need >= 0 else False
-            if self.ws_wgrad_multi is not False:
+            if self._wgrad_multi_workspace(targets) is not False:
                 self._stamp(3)
                 if ev_reach is not None:                                 # (four streams: the row list was built behind the ID chain)
                     torch.cuda.current_stream().wait_event(ev_reach)
                 lins = (m.item_trans, m.user_trans, m.text_trans, m.image_trans)              # (wgrad_targets' order)
                 if self.inline_adamw:                                  # the four Linears' AdamW rides in the slab-reduction launch
-                    ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, update=(self.opt, [(l.weight, l.bias) for l in lins]), block_budget=self.wgrad_blocks)
+                    update = (self.opt, [(l.weight, l.bias) for l in lins])
+                    accepted = False
+                    if hosted is not None:                               # (_host_wgrad_applies: inline_adamw and this fast path)
+                        probs, keep = self._spmm_problems([hosted])
+                        accepted = ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, update=update, block_budget=self.wgrad_blocks,
+                                                          host_spmm=(probs[0], self._block_slots // 2))     # (2 block slots per CU)
+                        del keep
+                        if accepted:
+                            self.spmm_edge_units += hosted[0].nnz * (hosted[1].shape[1] / 64.0)
+                        else:                                            # refused, nothing launched: the product by its own launch
+                            self._spmm_jobs([hosted])
+                        hosted = None
+                    if not accepted:
+                        ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, update=update, block_budget=self.wgrad_blocks)
                     updated = [p_ for l in lins for p_ in (l.weight, l.bias)]
                 else:
                     ops.linear_wgrad_multi(targets, self.ws_wgrad_multi, block_budget=self.wgrad_blocks)
@@ -948,6 +1001,11 @@ class FusedStep:
             ops.linear_wgrad_grouped(strip(item_pairs), m.item_trans.weight.grad, bias(m.item_trans), False, self.ws_wgrad, precision=self.gemm)
             ops.linear_wgrad_grouped(strip(text_pairs), m.text_trans.weight.grad, bias(m.text_trans), False, self.ws_wgrad_c, precision=self.gemm)
             ops.linear_wgrad_grouped(strip(image_pairs), m.image_trans.weight.grad, bias(m.image_trans), False, self.ws_wgrad_d, precision=self.gemm)
+        if deferred is not None:                                         # the rest of the ID chain, then its tail (one stream)
+            rest, probs_bpr, batch = deferred
+            for job in rest if hosted is not None else rest[1:]:         # (hosted still set: no launch above took the first product)
+                self._spmm_group([job])
+            self._chain_tail(probs_bpr, batch)
         self._join(self.s1)                                              # user_trans' gradient
         if self.inline_adamw:                                            # whatever the reduction launch did not update (all four Linears on
             self.opt.step_params([p_ for p_ in self._lin_params if all(p_ is not q for q in updated)])   # the per-target fallback paths)

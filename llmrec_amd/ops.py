@@ -836,18 +836,23 @@ def linear_wgrad_multi_workspace(targets, block_budget: int = 0) -> int:
     return _lib.query("llmrec_linear_wgrad_multi_workspace_bytes", len(targets), arr, N)
 
 
-def linear_wgrad_multi(targets, ws: Optional[torch.Tensor] = None, update=None, block_budget: int = 0):
+def linear_wgrad_multi(targets, ws: Optional[torch.Tensor] = None, update=None, block_budget: int = 0, host_spmm=None):
     """The bf16x3 weight gradients of several Linears in one launch + one reduction launch (llmrec_linear_wgrad_multi_bf16x3).
     targets: [(pairs, dW, db, accumulate)], pairs = [(dY, X)] as in linear_wgrad_grouped; all dW have N rows.
     update = (FusedAdamW, [(W, b)] per target): the AdamW update of those parameters rides in the reduction launch
     (llmrec_linear_wgrad_multi_adamw_bf16x3; the optimizer's step counter has been advanced already).
-    block_budget: resident blocks per round the launch is laid out for (0 = 256: one per CU)."""
+    block_budget: resident blocks per round the launch is laid out for (0 = 256: one per CU).
+    host_spmm = (llmrec_spmm_problem_t, the device's CU count), with update only: the independent product runs in the CUs the launch
+    leaves free (llmrec_linear_wgrad_multi_adamw_host_spmm_bf16x3). Returns whether the pair was accepted; False: NOTHING was launched,
+    and the caller issues the product and this call without it. (Without host_spmm: None.)"""
     arr, keep, N = _wgrad_targets(targets, block_budget)
     need = _lib.query("llmrec_linear_wgrad_multi_workspace_bytes", len(targets), arr, N)
     if need < 0:
         raise RuntimeError("linear_wgrad_multi: shapes outside the fast path (use linear_wgrad_grouped per target)")
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=targets[0][1].device)
+    if host_spmm is not None and update is None:
+        raise RuntimeError("linear_wgrad_multi: host_spmm needs update (the hosting entry point carries the AdamW update)")
     if update is None:
         _lib.call("llmrec_linear_wgrad_multi_bf16x3", len(targets), arr, N, _p(ws), ws.numel(), _stream())
         return
@@ -865,6 +870,11 @@ def linear_wgrad_multi(targets, ws: Optional[torch.Tensor] = None, update=None, 
         if b is not None and float(opt.grad_scale.get(b, 1.0)) != gs:
             raise RuntimeError("linear_wgrad_multi: W and b of one target need the same grad_scale")
         upd[i].g_scale = gs
+    if host_spmm is not None:
+        problem, n_cu = host_spmm
+        return _lib.call_unless_unsupported("llmrec_linear_wgrad_multi_adamw_host_spmm_bf16x3", len(targets), arr, N, _p(ws), ws.numel(), upd,
+                                            _p(opt.dev_state), opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.wd, _c.byref(problem),
+                                            int(n_cu), _stream())
     _lib.call("llmrec_linear_wgrad_multi_adamw_bf16x3", len(targets), arr, N, _p(ws), ws.numel(), upd, _p(opt.dev_state), opt.lr, opt.betas[0],
               opt.betas[1], opt.eps, opt.wd, _stream())
 

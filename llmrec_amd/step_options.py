@@ -30,6 +30,7 @@ class StepOptions(NamedTuple):
     bwd_mask: bool
     bwd_zero_skip: bool
     host_chain: bool
+    host_wgrad: bool = True
 
 
 def resolve(env: Optional[Mapping[str, str]], *, n_users: int, n_items: int, d: int, n_attr: int, drop_rate: float, wgrad_rows_default: bool,
@@ -116,6 +117,16 @@ def resolve(env: Optional[Mapping[str, str]], *, n_users: int, n_items: int, d: 
     # product A_ui E_i needs nothing from the projection, and the grouped projection's last round of work units leaves block slots
     # empty once the launch has more units than the device has slots: the product runs as trailing blocks of that launch
     # (llmrec_linear_fwd_grouped_host_spmm_bf16x3) and the forward needs one SpMM group fewer. Same bits: every row keeps its tree.
-    host_chain = env.get("LLMREC_HOST_CHAIN", "1") == "1"
+    # HOSTED backward product (round 16; the same variable's third value, LLMREC_HOST_CHAIN=fwd: the forward hosting only - round 15's
+    # step, the A/B reference). The weight-gradient launch is laid out for FusedStep.wgrad_blocks = 224 blocks, each of which owns a CU,
+    # and the one-stream step has nothing else to run on the other CUs for the launch's ~100 us. The first product of the ID chain's
+    # backward that has no side or profile partner left to share a group with (iu.bwd: bufI -> bufU) is independent of that launch:
+    # it runs there, as persistent blocks behind the weight gradient's (llmrec_linear_wgrad_multi_adamw_host_spmm_bf16x3), and the
+    # chain's remaining product and tail follow the launch instead of preceding it. Same bits: the slab length, and with it dW's
+    # summation, depends on the block budget alone, and every row of the product keeps its tree. FusedStep applies it where its gate
+    # holds (_host_wgrad_applies). Any value but "0" / "fwd" is the default: both hostings.
+    want = env.get("LLMREC_HOST_CHAIN", "1")
+    host_chain = want != "0"
+    host_wgrad = want != "fwd"
     return StepOptions(drop_rate, check_zero, multi_stream, gemm, preprop, wgrad_rows, inline_adamw, fold, bwd_mask, bwd_zero_skip,
-                       host_chain)
+                       host_chain, host_wgrad)

@@ -31,7 +31,7 @@ def assembly(side, tmp):
         return {os.path.basename(p)[:-2]: open(p).read() for p in sorted(glob.glob(os.path.join(side, "*.s")))}
     csrc = os.path.join(side, "llmrec_amd", "csrc")
     if os.path.isdir(csrc):
-        srcs = [os.path.join(csrc, s) for s in build.SOURCES]
+        srcs = [os.path.join(csrc, s) for s in build.SOURCES if os.path.exists(os.path.join(csrc, s))]   # (a file one side lacks: "only in")
     else:
         srcs = sorted(glob.glob(os.path.join(side, "*.hip")))
 
