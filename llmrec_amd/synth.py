@@ -186,7 +186,8 @@ def split_train_test(rows: np.ndarray, cols: np.ndarray, n_users: int, seed: int
 def write_dataset(path: str, n_users: int, n_items: int, n_edges: int, seed: int = 0,
                   image_dim: int = 512, text_dim: int = 768, llm_dim: int = 1536,
                   keys=NETFLIX_KEYS, feat_dtype=np.float32, aug_out_of_range: float = 0.05,
-                  max_deg: int = 10_000, n_communities: int = 0, min_deg: int = 1, attr_rows_as_arrays: bool = False) -> dict:
+                  max_deg: int = 10_000, n_communities: int = 0, min_deg: int = 1, attr_rows_as_arrays: bool = False,
+                  p_in: float = 0.85) -> dict:
     """Write a complete Stage-2 dataset directory (every file of SURVEY.md Appendix A).
 
     ``n_edges`` counts all interactions; users with >= 3 give one to val and one to test."""
@@ -194,7 +195,8 @@ def write_dataset(path: str, n_users: int, n_items: int, n_edges: int, seed: int
 
     os.makedirs(path, exist_ok=True)
     rng = np.random.default_rng(seed + 7)
-    rows, cols = bipartite_edges(n_users, n_items, n_edges, seed=seed, max_deg=max_deg, n_communities=n_communities, min_deg=min_deg)
+    rows, cols = bipartite_edges(n_users, n_items, n_edges, seed=seed, max_deg=max_deg, n_communities=n_communities, min_deg=min_deg,
+                                 p_in=p_in)
     rows, cols, role = split_train_test(rows, cols, n_users, seed)
 
     def as_dict(mask):
