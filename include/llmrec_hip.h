@@ -560,7 +560,8 @@ int llmrec_bpr_prune_fwd_sharded_f32(const float* Eu, int64_t ldu, const float* 
  *                                       my_offset; out2[0] is this rank's share. n_valid_dev bounds the LOCAL samples only.
  * workspace: llmrec_bpr_prune_wide_workspace_bytes(global_B, or B_local for a local batch) bytes, 4-byte aligned; the entry point's
  * own launches initialise it. Too small: LLMREC_EWORKSPACE; a size above LLMREC_BPR_WIDE_MAX_B: LLMREC_EUNSUPPORTED (the query: -1).
- * The multi-problem entry points below (FusedStep, DataParallelStep) stay capped at LLMREC_BPR_MAX_B. */
+ * The multi-problem entry points below stay capped at LLMREC_BPR_MAX_B (DataParallelStep, the default FusedStep); their *_wide twins
+ * further down carry the eight-problem loss segment up to LLMREC_BPR_WIDE_MAX_B. */
 #define LLMREC_BPR_WIDE_MAX_B (1 << 22)
 int64_t llmrec_bpr_prune_wide_workspace_bytes(int64_t global_B);
 int llmrec_bpr_prune_fwd_wide_f32(const float* Eu, int64_t ldu, const float* Ei, int64_t ldi, int32_t d,
@@ -676,6 +677,48 @@ int llmrec_bpr_multi_losses_assemble_f32(int32_t n_problems, int32_t B_max, cons
 int llmrec_bpr_multi_zero_rows_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
                                    const int64_t* users, const int64_t* pos, const int64_t* neg,
                                    int32_t B_max, const int32_t* n_valid_dev, llmrec_stream_t stream);
+/* The eight-problem loss segment of ONE LOCAL batch for B_max up to LLMREC_BPR_WIDE_MAX_B (additive: the entry points above keep
+ * refusing B_max > LLMREC_BPR_MAX_B). Same `saved` / `plan` layouts; wherever both forms exist (B_max <= LLMREC_BPR_MAX_B) `plan`,
+ * `saved`, `out`, `scal4`, the row flags and every gradient row carry the capped entry points' BITS. All hipGraph-capturable: the launch
+ * sequence depends on the host arguments alone, integer atomics only, no host synchronisation, no allocation; every refusal is decided
+ * before the first launch: a NULL or too-small workspace LLMREC_EWORKSPACE, B_max > LLMREC_BPR_WIDE_MAX_B LLMREC_EUNSUPPORTED (the
+ * workspace queries: -1), a bad problem table or n_problems > LLMREC_BPR_MAX_PROBLEMS LLMREC_EINVAL.
+ *   llmrec_bpr_scatter_plan_wide          llmrec_bpr_scatter_plan's LLMREC_BPR_PLAN_WORDS(B_max) words, word for word: the keys of both sides
+ *                                         in one launch, one multi-block radix sort per side over the whole (distinct) keys - the sort of
+ *                                         llmrec_scatter_rows_f32, between two buffers of the workspace -, then one launch that writes the
+ *                                         sorted keys and the run lengths (an upper-bound binary search per run head). workspace:
+ *                                         llmrec_bpr_scatter_plan_wide_workspace_bytes(B_max) bytes, 256-byte aligned.
+ *   llmrec_bpr_multi_scores_wide_f32      llmrec_bpr_multi_scores_step_f32's launch (adamw_state3 == NULL: the row stamp only).
+ *   llmrec_bpr_multi_select_bwd_wide_f32  llmrec_bpr_multi_select_bwd_f32 with llmrec_bpr_prune_fwd_wide_f32's exact radix select in place of
+ *                                         rank counting in LDS: problem p owns block p of the workspace (histograms, state, eq[]), which
+ *                                         the entry point's own launches initialise. Launches: init, four histogram passes, the ties'
+ *                                         count, the write pass (coefficient -> saved[b], kept m_b or 0 -> slot 1, zeros for
+ *                                         n_valid <= b < B_max, problem 0 stamps the rows; one more block per problem: the squared
+ *                                         norms' sums and k into saved[B_max .. B_max + 3]), then the backward rows through `plan`.
+ *                                         workspace: llmrec_bpr_multi_wide_workspace_bytes(n_problems, B_max) bytes, 4-byte aligned.
+ *   llmrec_bpr_multi_losses_wide_f32      llmrec_bpr_multi_losses_assemble_f32's single-block launch; scal4 == NULL: the loss values only
+ *                                         (out, saved[B_max .. B_max + 3]: llmrec_bpr_multi_losses_f32's bits), w_mf_host / sumsq_partial /
+ *                                         running_sums3 are then not read.
+ * Known limit: the backward gives one 16-lane group to each destination row, so at batches of 10^5 and more a popular item is one
+ * long serial run of n_problems * (its count) rows - exact and deterministic, its time unmeasured. */
+int64_t llmrec_bpr_scatter_plan_wide_workspace_bytes(int64_t B_max);
+int llmrec_bpr_scatter_plan_wide(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B_max, const int32_t* n_valid_dev,
+                                 uint64_t* plan, void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
+int llmrec_bpr_multi_scores_wide_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
+                                     const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                     int32_t B_max, const int32_t* n_valid_dev, float* saved, int32_t* row_stamp,
+                                     float* adamw_state3, float lr, float beta1, float beta2, llmrec_stream_t stream);
+int64_t llmrec_bpr_multi_wide_workspace_bytes(int32_t n_problems, int64_t B_max);
+int llmrec_bpr_multi_select_bwd_wide_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
+                                         const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                         int32_t B_max, const int32_t* n_valid_dev, double remember_rate, float decay,
+                                         float batch_size_flag, float* saved, uint8_t* user_row_flags, uint8_t* item_row_flags,
+                                         const int32_t* row_stamp, const uint64_t* plan,
+                                         void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
+int llmrec_bpr_multi_losses_wide_f32(int32_t n_problems, int32_t B_max, const int32_t* n_valid_dev, double remember_rate, float decay,
+                                     float batch_size_flag, float* out, float* saved, const float* w_mf_host,
+                                     const float* sumsq_partial, int32_t n_partial, float feat_reg_coef,
+                                     float* scal4, double* running_sums3, llmrec_stream_t stream);
 /* dEu[u_b] += g_mf * ds_b * (Ei[p_b] - Ei[q_b]) + g_emb * c_u * Eu[u_b]   (deterministic scatter-add through `plan`, see above)
  * dEi[p_b] += g_mf * ds_b * Eu[u_b] + g_emb * c_p * Ei[p_b] ; dEi[q_b] likewise with -ds_b, c_q
  * g_mf / g_emb are upstream gradients read from device memory (grads2[0], grads2[1]). dEu and dEi are distinct buffers. */

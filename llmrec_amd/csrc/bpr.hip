@@ -5,6 +5,7 @@
 // device->host->device round trip per bpr_loss call (8 per step, main.py:159).
 #include "common.h"
 #include "guests.h"
+#include <hipcub/hipcub.hpp>
 
 namespace llmrec {
 
@@ -447,6 +448,26 @@ __global__ __launch_bounds__(256) void bpr_bwd_runs_kernel(BprTables t, int n_pr
     }
 }
 
+// the norm block of a selection launch (256 threads): thread t of bpr_reduce_kernel's 1024 is emulated by the four slots t, t + 256, ... of
+// this block's threads, then the same pairwise tree over 1024 LDS slots, three columns at once -> saved[B_max .. B_max + 2]; k -> [B_max + 3]
+__device__ __forceinline__ void sel_norm_block(float* __restrict__ saved, int B, int B_max, int k, float (*red)[BPR_THREADS]) {
+    const float* sc = saved + B_max + 4;
+    for (int v = threadIdx.x; v < BPR_THREADS; v += 256) {        // the partial sums of bpr_reduce_kernel's thread v
+        float su = 0.f, sp = 0.f, sq = 0.f;
+        for (int b = v; b < B; b += BPR_THREADS) { su += sc[2 * B_max + b]; sp += sc[3 * B_max + b]; sq += sc[4 * B_max + b]; }
+        red[0][v] = su; red[1][v] = sp; red[2][v] = sq;
+    }
+    __syncthreads();
+    for (int off = BPR_THREADS / 2; off > 0; off >>= 1) {         // block_tree_sum's tree, three columns at once
+        for (int i = threadIdx.x; i < off; i += 256) {
+            red[0][i] += red[0][i + off]; red[1][i] += red[1][i + off]; red[2][i] += red[2][i + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) saved[B_max + threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x == 3) saved[B_max + 3] = (float)k;
+}
+
 // selection of a LOCAL batch (first launch of llmrec_bpr_multi_select_bwd_f32): grid = (ceil(B_max / 16) + 1, problems).
 // Blocks [0, ceil(B_max / 16)): stage the batch's log-sigmoids in LDS and rank their 16 samples as bpr_rank_kernel does (kept
 // coefficient -> saved[b], kept value -> slot 1), stamp the rows the batch touches. The LAST block of a problem sums the three
@@ -467,21 +488,7 @@ __global__ __launch_bounds__(256) void bpr_select_kernel(const int64_t* __restri
     float* sc = saved + B_max + 4;
     const int k = (int)(remember_rate * (double)B);
     if (blockIdx.x == gridDim.x - 1) {
-        float (*red)[BPR_THREADS] = reinterpret_cast<float (*)[BPR_THREADS]>(smem);
-        for (int v = threadIdx.x; v < BPR_THREADS; v += 256) {        // the partial sums of bpr_reduce_kernel's thread v
-            float su = 0.f, sp = 0.f, sq = 0.f;
-            for (int b = v; b < B; b += BPR_THREADS) { su += sc[2 * B_max + b]; sp += sc[3 * B_max + b]; sq += sc[4 * B_max + b]; }
-            red[0][v] = su; red[1][v] = sp; red[2][v] = sq;
-        }
-        __syncthreads();
-        for (int off = BPR_THREADS / 2; off > 0; off >>= 1) {         // block_tree_sum's tree, three columns at once
-            for (int i = threadIdx.x; i < off; i += 256) {
-                red[0][i] += red[0][i + off]; red[1][i] += red[1][i + off]; red[2][i] += red[2][i + off];
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x < 3) saved[B_max + threadIdx.x] = red[threadIdx.x][0];
-        if (threadIdx.x == 3) saved[B_max + 3] = (float)k;
+        sel_norm_block(saved, B, B_max, k, reinterpret_cast<float (*)[BPR_THREADS]>(smem));
         return;
     }
     for (int j = threadIdx.x; j < B; j += 256) m_s[j] = sc[j];
@@ -670,7 +677,23 @@ struct SelArgs {
     float* saved;
     int my_offset;                     // global index of this rank's sample 0
     uint32_t* ws;
+    // the multi-problem form (llmrec_bpr_multi_select_bwd_wide_f32): problem blockIdx.y owns saved + y * saved_stride and ws + y * ws_stride
+    int64_t saved_stride, ws_stride;   // floats / words between two problems' blocks (a single problem: gridDim.y = 1)
+    int norm_block;                    // the write launch has one more block per problem: sel_norm_block
+    const int64_t* users;              // the write launch of problem 0 stamps the batch's rows (any of the three may be absent)
+    const int64_t* pos;
+    const int64_t* neg;
+    uint8_t* flag_u;
+    uint8_t* flag_i;
+    const int32_t* row_stamp;
 };
+
+// the arguments of the block's own problem
+__device__ __forceinline__ SelArgs sel_mine(SelArgs a) {
+    a.saved += (int64_t)blockIdx.y * a.saved_stride;
+    a.ws += (int64_t)blockIdx.y * a.ws_stride;
+    return a;
+}
 
 struct SelProblem { const float* list; int Bg, k; bool active; };      // active: 0 < k < Bg, a threshold has to be found
 __device__ __forceinline__ SelProblem sel_problem(const SelArgs& a) {
@@ -720,11 +743,13 @@ __device__ __forceinline__ uint2 sel_state(const uint32_t* ws, int p, int k, uin
     return make_uint2(pick[0], pick[1]);
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_init_kernel(uint32_t* __restrict__ ws) {
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_init_kernel(uint32_t* __restrict__ ws, int64_t ws_stride) {
+    ws += (int64_t)blockIdx.y * ws_stride;
     for (int i = threadIdx.x; i < SEL_WS_STATE; i += SEL_THREADS) ws[i] = 0u;
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_hist_kernel(SelArgs a, int p) {
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_hist_kernel(SelArgs a_, int p) {
+    const SelArgs a = sel_mine(a_);
     __shared__ uint32_t scan[SEL_THREADS];
     __shared__ uint32_t h[256];
     __shared__ uint32_t pick[2];
@@ -750,7 +775,8 @@ __global__ __launch_bounds__(SEL_THREADS) void bpr_sel_hist_kernel(SelArgs a, in
     if (c) atomicAdd(&a.ws[p * 256 + threadIdx.x], c);
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_count_kernel(SelArgs a) {
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_count_kernel(SelArgs a_) {
+    const SelArgs a = sel_mine(a_);
     __shared__ uint32_t scan[SEL_THREADS];
     __shared__ uint32_t pick[2];
     __shared__ uint32_t cnt;
@@ -775,11 +801,17 @@ __global__ __launch_bounds__(SEL_THREADS) void bpr_sel_count_kernel(SelArgs a) {
     if (threadIdx.x == 0) a.ws[SEL_WS_EQ + blockIdx.x] = cnt;
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_write_kernel(SelArgs a) {
+__global__ __launch_bounds__(SEL_THREADS) void bpr_sel_write_kernel(SelArgs a_) {
+    const SelArgs a = sel_mine(a_);
     __shared__ uint32_t scan[SEL_THREADS];
     __shared__ uint32_t before_s;
     const SelProblem s = sel_problem(a);
     const int B = bpr_batch(a.n_valid_dev, a.B_max);
+    if (a.norm_block && blockIdx.x == gridDim.x - 1) {                 // (block-uniform) the squared norms' sums, as bpr_select_kernel's last block
+        __shared__ float red[3][BPR_THREADS];
+        sel_norm_block(a.saved, B, a.B_max, s.k, red);
+        return;
+    }
     const int base = (int)blockIdx.x * SEL_CHUNK;
     if (base + SEL_CHUNK <= a.my_offset || base >= a.my_offset + a.B_max) return;   // none of this rank's samples in the chunk (block-uniform)
     float* sc = a.saved + a.B_max + 4;
@@ -815,7 +847,58 @@ __global__ __launch_bounds__(SEL_THREADS) void bpr_sel_write_kernel(SelArgs a) {
         const float mb = sc[b];
         a.saved[b] = keep ? (-1.0f / (float)s.k) * sc[a.B_max + b] : 0.f;
         sc[a.B_max + b] = keep ? mb : 0.f;
+        if (blockIdx.y == 0) {                                         // rows this batch touches (same rows for every problem)
+            const uint8_t stamp = a.row_stamp ? LLMREC_ROW_STAMP(a.row_stamp[0]) : (uint8_t)1;
+            if (a.flag_u) a.flag_u[a.users[b]] = stamp;
+            if (a.flag_i) { a.flag_i[a.pos[b]] = stamp; a.flag_i[a.neg[b]] = stamp; }
+        }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The scatter plan of a batch of ANY size (llmrec_bpr_scatter_plan_wide): bpr_plan_kernel stages a side's keys in LDS (64 KB at
+// B_max = 4096) and counts ranks, O(B^2). Here: the keys  id << 32 | slot  of both sides (one launch), one multi-block radix sort per
+// side over the whole 64-bit key (the keys are distinct; the sort llmrec_scatter_rows_f32 issues, between two buffers of the
+// workspace), then one launch that copies the sorted keys into the plan and writes the run lengths: a position is a head iff its id
+// differs from its predecessor's, and the run ends at the upper bound of its id - a binary search, not a walk (a hub item is ONE run
+// of up to 2 B positions).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bpr_plan_keys_kernel(const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+                                                            const int64_t* __restrict__ neg, int B_max,
+                                                            const int32_t* __restrict__ n_valid_dev, uint64_t* __restrict__ keys) {
+    const int B = bpr_batch(n_valid_dev, B_max);
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;          // [0, B_max): the user side; [B_max, 3 B_max): the item side
+    if (j >= 3 * (int64_t)B_max) return;
+    const bool items = j >= B_max;
+    const int i = (int)(items ? j - B_max : j);                        // the slot within the side
+    const int b = (items && i >= B_max) ? i - B_max : i;
+    uint64_t id = PLAN_NO_ID;
+    if (b < B) id = (uint64_t)(items ? (i >= B_max ? neg[b] : pos[b]) : users[b]);
+    keys[j] = (id << 32) | (uint64_t)(uint32_t)i;
+}
+
+// sorted_u / sorted_i: the sides' sorted keys (B_max / 2 B_max of them, outside the plan)
+__global__ __launch_bounds__(256) void bpr_plan_runs_kernel(int B_max, const uint64_t* __restrict__ sorted_u, const uint64_t* __restrict__ sorted_i,
+                                                            uint64_t* __restrict__ plan) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= 3 * (int64_t)B_max) return;
+    const bool items = j >= B_max;
+    const uint64_t* k = items ? sorted_i : sorted_u;
+    const int n = items ? 2 * B_max : B_max;
+    const int i = (int)(items ? j - B_max : j);
+    const uint64_t me = k[i];
+    const uint32_t id = (uint32_t)(me >> 32);
+    plan[j] = me;
+    int len = 0;
+    if (id != PLAN_NO_ID && (i == 0 || (uint32_t)(k[i - 1] >> 32) != id)) {
+        int lo = i + 1, hi = n;                                        // the first position in (i, n] whose id is above this one's
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if ((uint32_t)(k[mid] >> 32) > id) hi = mid; else lo = mid + 1;
+        }
+        len = lo - i;
+    }
+    reinterpret_cast<int32_t*>(plan + 3 * (int64_t)B_max)[j] = len;
 }
 
 }  // namespace llmrec
@@ -928,13 +1011,15 @@ int llmrec_bpr_prune_fwd_wide_f32(const float* Eu, int64_t ldu, const float* Ei,
     }
     BprGather ga = {};
     if (!local) { ga.g = global_m; ga.n_ranks = 1; ga.stride = 0; ga.cap = global_B; ga.n_prob = 1; ga.my_offset = my_offset; ga.has_tail = 0; }
-    const SelArgs a = {global_m, slots, B_local, n_valid_dev, remember_rate, saved, my_offset, (uint32_t*)workspace};
+    SelArgs a = {};
+    a.list = global_m; a.slots = slots; a.B_max = B_local; a.n_valid_dev = n_valid_dev; a.remember_rate = remember_rate; a.saved = saved;
+    a.my_offset = my_offset; a.ws = (uint32_t*)workspace;
     const unsigned chunks = (unsigned)ceil_div(slots > 0 ? slots : 1, SEL_CHUNK);
     // a list length the host knows (no device batch count) settles k here: k <= 0 or k >= Bg needs no threshold
     const bool host_len = !local || !n_valid_dev;
     const int k_host = (int)(remember_rate * (double)slots);
     if (!(host_len && (k_host <= 0 || k_host >= slots))) {
-        bpr_sel_init_kernel<<<1, SEL_THREADS, 0, stream>>>(a.ws);
+        bpr_sel_init_kernel<<<1, SEL_THREADS, 0, stream>>>(a.ws, 0);
         LLMREC_LAUNCH_CHECK();
         for (int p = 0; p < SEL_PASSES; ++p) {
             bpr_sel_hist_kernel<<<chunks, SEL_THREADS, 0, stream>>>(a, p);
@@ -1147,6 +1232,137 @@ int llmrec_bpr_multi_zero_rows_f32(int32_t n_problems, const llmrec_bpr_problem_
     LLMREC_CHECK_ARG(!fill_tables(t, n_problems, problems_host, d, true), "bpr_multi_zero_rows: bad problem table");
     dim3 grid((unsigned)ceil_div(B_max, 16), (unsigned)n_problems);
     bpr_zero_rows_kernel<<<grid, 256, 0, (hipStream_t)stream_>>>(t, d, users, pos, neg, B_max, n_valid_dev);
+    LLMREC_LAUNCH_CHECK();
+    return LLMREC_OK;
+}
+
+// ---- the eight-problem loss segment beyond LLMREC_BPR_MAX_B (FusedStep above FusedStep.WIDE_FROM) ----
+static int wide_refused(const char* who, int64_t B_max) {
+    if (B_max <= LLMREC_BPR_WIDE_MAX_B) return 0;
+    set_error("%s: B_max %lld > %d", who, (long long)B_max, LLMREC_BPR_WIDE_MAX_B);
+    return 1;
+}
+
+// plan workspace: the 3 B_max keys | the sort's second key buffer | its temporary storage (llmrec_scatter_rows_workspace_bytes' bound)
+static int64_t plan_wide_keys_bytes(int64_t B_max) { return align_up(8 * 3 * B_max, 256); }
+static int64_t plan_wide_temp_bytes(int64_t B_max) { return align_up(2 * B_max + (32ll << 20), 256); }
+
+int64_t llmrec_bpr_scatter_plan_wide_workspace_bytes(int64_t B_max) {
+    if (B_max < 0 || B_max > LLMREC_BPR_WIDE_MAX_B) return -1;
+    return 2 * plan_wide_keys_bytes(B_max) + plan_wide_temp_bytes(B_max);
+}
+
+int llmrec_bpr_scatter_plan_wide(const int64_t* users, const int64_t* pos, const int64_t* neg, int32_t B_max, const int32_t* n_valid_dev,
+                                 uint64_t* plan, void* workspace, int64_t workspace_bytes, llmrec_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LLMREC_CHECK_ARG(B_max >= 0, "bpr_scatter_plan_wide: bad argument");
+    if (wide_refused("bpr_scatter_plan_wide", B_max)) return LLMREC_EUNSUPPORTED;
+    if (B_max == 0) return LLMREC_OK;
+    LLMREC_CHECK_ARG(users && pos && neg && plan, "bpr_scatter_plan_wide: null pointer");
+    const int64_t need_ws = llmrec_bpr_scatter_plan_wide_workspace_bytes(B_max);
+    if (!workspace || workspace_bytes < need_ws) {
+        set_error("bpr_scatter_plan_wide: workspace %lld < %lld", (long long)workspace_bytes, (long long)need_ws);
+        return LLMREC_EWORKSPACE;
+    }
+    uint64_t* keys = (uint64_t*)workspace;
+    uint64_t* alt = (uint64_t*)((char*)workspace + plan_wide_keys_bytes(B_max));
+    void* temp = (char*)workspace + 2 * plan_wide_keys_bytes(B_max);
+    const size_t temp_avail = (size_t)plan_wide_temp_bytes(B_max);
+    hipcub::DoubleBuffer<uint64_t> ubuf(keys, alt), ibuf(keys + B_max, alt + B_max);
+    size_t need_u = 0, need_i = 0;                                      // (both queries before the first launch)
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need_u, ubuf, B_max, 0, 64, stream));
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need_i, ibuf, 2 * B_max, 0, 64, stream));
+    if (need_u > temp_avail || need_i > temp_avail) {
+        set_error("bpr_scatter_plan_wide: the sort needs %zu B of temporary storage > %zu", need_u > need_i ? need_u : need_i, temp_avail);
+        return LLMREC_EWORKSPACE;
+    }
+    const unsigned blocks = (unsigned)ceil_div(3 * (int64_t)B_max, 256);
+    bpr_plan_keys_kernel<<<blocks, 256, 0, stream>>>(users, pos, neg, B_max, n_valid_dev, keys);
+    LLMREC_LAUNCH_CHECK();
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(temp, need_u, ubuf, B_max, 0, 64, stream));
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(temp, need_i, ibuf, 2 * B_max, 0, 64, stream));
+    bpr_plan_runs_kernel<<<blocks, 256, 0, stream>>>(B_max, ubuf.Current(), ibuf.Current(), plan);   // (which buffer: settled on the host)
+    LLMREC_LAUNCH_CHECK();
+    return LLMREC_OK;
+}
+
+int llmrec_bpr_multi_scores_wide_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
+                                     const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                     int32_t B_max, const int32_t* n_valid_dev, float* saved, int32_t* row_stamp,
+                                     float* adamw_state3, float lr, float beta1, float beta2, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= LLMREC_BPR_MAX_PROBLEMS && problems_host && d > 0 && saved, "bpr_multi_scores_wide: bad argument");
+    if (wide_refused("bpr_multi_scores_wide", B_max)) return LLMREC_EUNSUPPORTED;
+    LLMREC_CHECK_ARG(B_max > 0 && users && pos && neg, "bpr_multi_scores_wide: empty batch capacity or null index pointer (the launch carries the step's counters)");
+    BprTables t = {};
+    LLMREC_CHECK_ARG(!fill_tables(t, n_problems, problems_host, d, false), "bpr_multi_scores_wide: bad problem table");
+    StepBegin sb = {};
+    sb.row_stamp = row_stamp; sb.adamw_state = adamw_state3; sb.lr = lr; sb.b1 = beta1; sb.b2 = beta2;
+    return launch_bpr_fwd(t, n_problems, d, users, pos, neg, B_max, n_valid_dev, 0.0, 0.f, 1.f, nullptr, saved, BprGather{}, true, false,
+                          nullptr, (hipStream_t)stream_, sb);
+}
+
+// per problem: hist[4][256] | state | eq[chunks], a whole number of 256-byte lines
+static int64_t sel_problem_words(int64_t B_max) { return align_up(4 * (SEL_WS_EQ + ceil_div(B_max > 0 ? B_max : 1, SEL_CHUNK)), 256) / 4; }
+
+int64_t llmrec_bpr_multi_wide_workspace_bytes(int32_t n_problems, int64_t B_max) {
+    if (n_problems < 1 || n_problems > LLMREC_BPR_MAX_PROBLEMS || B_max < 0 || B_max > LLMREC_BPR_WIDE_MAX_B) return -1;
+    return 4 * n_problems * sel_problem_words(B_max);
+}
+
+int llmrec_bpr_multi_select_bwd_wide_f32(int32_t n_problems, const llmrec_bpr_problem_t* problems_host, int32_t d,
+                                         const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                         int32_t B_max, const int32_t* n_valid_dev, double remember_rate, float decay,
+                                         float batch_size_flag, float* saved, uint8_t* user_row_flags, uint8_t* item_row_flags,
+                                         const int32_t* row_stamp, const uint64_t* plan,
+                                         void* workspace, int64_t workspace_bytes, llmrec_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= LLMREC_BPR_MAX_PROBLEMS && problems_host && d > 0 && saved, "bpr_multi_select_bwd_wide: bad argument");
+    if (wide_refused("bpr_multi_select_bwd_wide", B_max)) return LLMREC_EUNSUPPORTED;
+    if (B_max == 0) return LLMREC_OK;
+    LLMREC_CHECK_ARG(B_max > 0 && users && pos && neg && plan, "bpr_multi_select_bwd_wide: null index pointer or no scatter plan (llmrec_bpr_scatter_plan_wide)");
+    BprTables t = {};
+    LLMREC_CHECK_ARG(!fill_tables(t, n_problems, problems_host, d, true), "bpr_multi_select_bwd_wide: bad problem table");
+    const int64_t need = llmrec_bpr_multi_wide_workspace_bytes(n_problems, B_max);
+    if (!workspace || workspace_bytes < need) {
+        set_error("bpr_multi_select_bwd_wide: workspace %lld < %lld", (long long)workspace_bytes, (long long)need);
+        return LLMREC_EWORKSPACE;
+    }
+    SelArgs a = {};
+    a.slots = B_max; a.B_max = B_max; a.n_valid_dev = n_valid_dev; a.remember_rate = remember_rate; a.saved = saved;
+    a.ws = (uint32_t*)workspace; a.saved_stride = LLMREC_BPR_SAVED_FLOATS(B_max); a.ws_stride = sel_problem_words(B_max);
+    a.norm_block = 1; a.users = users; a.pos = pos; a.neg = neg; a.flag_u = user_row_flags; a.flag_i = item_row_flags; a.row_stamp = row_stamp;
+    const unsigned chunks = (unsigned)ceil_div(B_max, SEL_CHUNK);
+    const dim3 grid(chunks, (unsigned)n_problems);
+    // a batch size the host knows (no device count) settles k here: k <= 0 or k >= B needs no threshold
+    const int k_host = (int)(remember_rate * (double)B_max);
+    if (n_valid_dev || (k_host > 0 && k_host < B_max)) {
+        bpr_sel_init_kernel<<<dim3(1, (unsigned)n_problems), SEL_THREADS, 0, stream>>>(a.ws, a.ws_stride);
+        LLMREC_LAUNCH_CHECK();
+        for (int p = 0; p < SEL_PASSES; ++p) {
+            bpr_sel_hist_kernel<<<grid, SEL_THREADS, 0, stream>>>(a, p);
+            LLMREC_LAUNCH_CHECK();
+        }
+        bpr_sel_count_kernel<<<grid, SEL_THREADS, 0, stream>>>(a);
+        LLMREC_LAUNCH_CHECK();
+    }
+    bpr_sel_write_kernel<<<dim3(chunks + 1u, (unsigned)n_problems), SEL_THREADS, 0, stream>>>(a);   // (+ 1: the norm block)
+    LLMREC_LAUNCH_CHECK();
+    return launch_bwd_runs(t, n_problems, d, users, pos, neg, B_max, decay, batch_size_flag, saved, plan, nullptr, stream);
+}
+
+int llmrec_bpr_multi_losses_wide_f32(int32_t n_problems, int32_t B_max, const int32_t* n_valid_dev, double remember_rate, float decay,
+                                     float batch_size_flag, float* out, float* saved, const float* w_mf_host,
+                                     const float* sumsq_partial, int32_t n_partial, float feat_reg_coef,
+                                     float* scal4, double* running_sums3, llmrec_stream_t stream_) {
+    LLMREC_CHECK_ARG(n_problems >= 1 && n_problems <= LLMREC_BPR_MAX_PROBLEMS && B_max >= 0 && out && saved && (w_mf_host || !scal4),
+                     "bpr_multi_losses_wide: bad argument");
+    LLMREC_CHECK_ARG(n_partial >= 0 && (n_partial == 0 || (sumsq_partial && scal4)), "bpr_multi_losses_wide: partial sums without a buffer");
+    if (wide_refused("bpr_multi_losses_wide", B_max)) return LLMREC_EUNSUPPORTED;
+    LossW w = {};
+    for (int i = 0; i < n_problems && w_mf_host; ++i) w.w[i] = w_mf_host[i];
+    const LossesArgs a = {n_problems, B_max, n_valid_dev, remember_rate, decay, batch_size_flag, out, saved, (int)LLMREC_BPR_SAVED_FLOATS(B_max), w,
+                          n_partial > 0 ? sumsq_partial : nullptr, n_partial, feat_reg_coef, scal4, scal4 ? running_sums3 : nullptr};
+    bpr_losses_assemble_kernel<<<1, BPR_THREADS, 0, (hipStream_t)stream_>>>(a);   // scal4 == NULL: the loss values only
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }

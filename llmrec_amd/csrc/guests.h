@@ -379,7 +379,7 @@ __device__ __forceinline__ void guest_block(const LossesArgs& a, int, char*) {
     float outs[LLMREC_BPR_MAX_PROBLEMS][2];
 #pragma unroll
     for (int p = 0; p < LLMREC_BPR_MAX_PROBLEMS; ++p) { outs[p][0] = __shfl(mf, p, 64); outs[p][1] = __shfl(emb, p, 64); }
-    if (lane != 0) return;
+    if (lane != 0 || !a.scal) return;                                   // (no scal: the loss values only, llmrec_bpr_multi_losses_wide_f32)
     float* scal = a.scal;
     float feat = scal[0];                                              // no partial sums: whatever llmrec_sumsq_f32 left there
     if (partial) feat = a.reg_coef * tot_s[4 * n_prob];

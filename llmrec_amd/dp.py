@@ -63,6 +63,9 @@ class DataParallelStep(FusedStep):
             # (the replicas would have to draw ONE mask for the replicated projections and advance one counter across three phases)
             raise RuntimeError("DataParallelStep: drop_rate = %r is not supported; dropout inside the step is FusedStep's (single replica) only"
                                % (drop_rate,))
+        if b_max > _lib.CONST["LLMREC_BPR_MAX_B"]:               # (the batch-sharded loss launches stage a rank's batch in LDS; FusedStep's
+            raise RuntimeError("DataParallelStep: b_max %d exceeds LLMREC_BPR_MAX_B = %d (the wide loss segment is FusedStep's only)"   # wide route is not theirs)
+                               % (b_max, _lib.CONST["LLMREC_BPR_MAX_B"]))
         self.bucket, self.n_grad = bucket_gradients(model)
         super().__init__(model, graph, hp, rates, optimizer, b_max)
         self.comm = comm

@@ -110,6 +110,13 @@ class FusedStep:
     # move without changing dW's bits: it sets the slab length (csrc/dense.hip: wgrad_multi_slab_rows), i.e. the summation partition.
     wgrad_blocks = 224
     WGRAD_ROWS = INLINE_ADAMW = FOLD = True      # schedule switches of the class: DataParallelStep (llmrec_amd/dp.py) turns all three off
+    # A step whose batch capacity b_max is ABOVE this takes the WIDE loss segment (llmrec_bpr_*_wide*: the scatter plan by a multi-block
+    # sort, the selection by the exact multi-block radix select, each problem in a workspace block of its own) instead of the launches
+    # that stage the batch in LDS and refuse b_max > LLMREC_BPR_MAX_B. The route depends on b_max alone, not on any process-wide switch
+    # (main.py builds such a step under LLMREC_FUSED=wide only: step_options.route); up to LLMREC_BPR_MAX_B both segments leave the same
+    # bits everywhere (tests lower WIDE_FROM to run the wide one at a small batch). The wide selection is 8 launches (init, four
+    # histogram passes, the ties' count, the write pass, the backward rows) against 2, its plan 4 (keys, two sorts, run lengths) against 1.
+    WIDE_FROM = _lib.CONST["LLMREC_BPR_MAX_B"]
 
     def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int, drop_rate: float = 0.0, drop_seed: int = 0):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
@@ -124,6 +131,9 @@ class FusedStep:
         self.S = S = 2 + len(self.keys)                      # item-side streams: image, text, attributes
         self.c_m, self.c_u, self.c_a = rates
         self.b_max = b_max
+        self.wide = b_max > self.WIDE_FROM                 # the loss segment's route: b_max alone
+        if b_max > _lib.CONST["LLMREC_BPR_WIDE_MAX_B"]:
+            raise RuntimeError("FusedStep: b_max %d exceeds LLMREC_BPR_WIDE_MAX_B = %d" % (b_max, _lib.CONST["LLMREC_BPR_WIDE_MAX_B"]))
         # every switch of the step - multi_stream, gemm, preprop, wgrad_rows, inline_adamw, fold, bwd_mask, bwd_zero_skip, host_chain,
         # host_wgrad, check_zero and the validated drop_rate - is decided once, with its rationale, in step_options.resolve(); below: allocation only
         opts = step_options.resolve(None, n_users=self.U, n_items=self.I, d=d, n_attr=len(self.keys), drop_rate=drop_rate,
@@ -170,6 +180,9 @@ class FusedStep:
         self.out = f(8, 2)
         self.saved = f(8 * ops.bpr_saved_floats(b_max))
         self.scal = f(4)                                     # [feat_reg, loss, mf, emb]
+        if self.wide:                                        # the wide loss segment's workspaces (its own launches initialise them)
+            self.ws_plan_wide = ops.bpr_plan_wide_workspace(b_max, dev)
+            self.ws_sel_wide = ops.bpr_multi_wide_workspace(1 + S, b_max, dev)
         self.ws_sumsq = torch.empty(_lib.query("llmrec_sumsq_workspace_bytes", 0, 0), dtype=torch.uint8, device=dev)
         feats = [model.image_feats, model.text_feats, model.user_feats] + [model.item_feats[k] for k in self.keys]
         ws = max(_lib.query("llmrec_linear_wgrad_workspace_bytes", x.shape[0] * (len(self.keys) if i >= 3 else 1), d, x.shape[1])
@@ -635,15 +648,22 @@ class FusedStep:
             torch.cuda.current_stream().wait_event(step.ev_plan)
         # the scores launch begins the step (row stamp; folded: AdamW's counter too), the selection stamps the batch's rows
         scores = (self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(self.saved), _p(self.row_stamp))
+        select = (self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), remember, float(hp.decay), float(hp.batch_size),
+                  _p(self.saved), _p(self.flag_u), _p(self.flag_i), _p(self.row_stamp), _p(self.bpr_plan))
         if self.fold:
             o = self.opt
             if o.dev_state is None:
                 o.dev_state = torch.zeros(3, dtype=torch.float32, device=self.E_u.device)
-            _call("llmrec_bpr_multi_scores_step_f32", *scores, _p(o.dev_state), o.lr, o.betas[0], o.betas[1])
+            _call("llmrec_bpr_multi_scores_wide_f32" if self.wide else "llmrec_bpr_multi_scores_step_f32", *scores, _p(o.dev_state), o.lr,
+                  o.betas[0], o.betas[1])
+        elif self.wide:
+            _call("llmrec_bpr_multi_scores_wide_f32", *scores, None, 0.0, 0.0, 0.0)         # (the row stamp only)
         else:
             _call("llmrec_bpr_multi_scores_f32", *scores)
-        _call("llmrec_bpr_multi_select_bwd_f32", self.n_prob, probs, self.d, _p(users), _p(pos), _p(neg), B, _p(n_valid), remember,
-              float(hp.decay), float(hp.batch_size), _p(self.saved), _p(self.flag_u), _p(self.flag_i), _p(self.row_stamp), _p(self.bpr_plan))
+        if self.wide:
+            _call("llmrec_bpr_multi_select_bwd_wide_f32", *select, _p(self.ws_sel_wide), self.ws_sel_wide.numel())
+        else:
+            _call("llmrec_bpr_multi_select_bwd_f32", *select)
         # The loss values and the logged scalars, on the ID chain's stream (_backward places them: a branch of their own right behind the BPR
         # launches - the graph ran it as the step's tail). Folded: ONE launch - loss values + regulariser (the fusion launch's partial sums) +
         # assembly - and, where the step's riders apply, the same launch as a guest of the backward's first SpMM group (_backward_one_stream).
@@ -651,10 +671,14 @@ class FusedStep:
         reg = (self.ss_partial, self.ss_n, float(hp.feat_reg_decay * 0.5 / self.I), self.scal, self.epoch_sums) if self.fold else None
 
         def folded():
-            _call("llmrec_bpr_multi_losses_assemble_f32", *_raw(losses), (_c.c_float * self.n_prob)(*self.w_mf), *_raw(reg))
+            _call("llmrec_bpr_multi_losses_wide_f32" if self.wide else "llmrec_bpr_multi_losses_assemble_f32", *_raw(losses),
+                  (_c.c_float * self.n_prob)(*self.w_mf), *_raw(reg))
 
         def unfolded():
-            _call("llmrec_bpr_multi_losses_f32", *_raw(losses))
+            if self.wide:
+                _call("llmrec_bpr_multi_losses_wide_f32", *_raw(losses), None, None, 0, 0.0, None, None)   # (the loss values only)
+            else:
+                _call("llmrec_bpr_multi_losses_f32", *_raw(losses))
             self._join(self.s3)                  # the regulariser's value (s3, during the forward)
             self._assemble_loss(0)               # loss = sum_p w_mf[p] * mf_p + emb_0 + feat_reg
         values = _Rider(folded, (lambda: ops.guest_losses(*losses, self.w_mf, *reg)) if step.ride else None) if self.fold else _Rider(unfolded)
@@ -1014,7 +1038,11 @@ class FusedStep:
         """llmrec_bpr_scatter_plan of this batch into the step's plan buffer (one launch; step_eager does it behind the sampler - callers
         that drive forward() / loss_backward() themselves call it once per batch, any time before the loss backward)."""
         self._check_batch(users.numel())
-        _call("llmrec_bpr_scatter_plan", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid), _p(self.bpr_plan))
+        if self.wide:
+            _call("llmrec_bpr_scatter_plan_wide", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid), _p(self.bpr_plan),
+                  _p(self.ws_plan_wide), self.ws_plan_wide.numel())
+        else:
+            _call("llmrec_bpr_scatter_plan", _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid), _p(self.bpr_plan))
 
     def reset_scatter_targets(self):
         """Dense clear of the scatter targets, which the step keeps all-zero between steps by clearing the rows it touched (set-up,
@@ -1056,8 +1084,10 @@ class FusedStep:
         if sampler is not None and not isinstance(sampler, _Rider):
             sampler = _Rider(sampler)
         # riders (the sampler, the plan + reach marks and the loss values in SpMM launches: three launches fewer) apply on one stream with a
-        # device sampler in the step, a reach list to build and the folded loss-value launch
-        step = _TrainStep(ride=bool(self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream))
+        # device sampler in the step, a reach list to build and the folded loss-value launch - and not on the wide route: the plan and
+        # the loss values have no guest form above LLMREC_BPR_MAX_B (decided here, once, not by a refused call per step), so the
+        # sampler, the plan and llmrec_batch_reach_rows' two launches (rung 3 of _plan_reach_rider's ladder) run on their own
+        step = _TrainStep(ride=bool(self.wgrad_rows and sampler is not None and self.fold and not self.multi_stream and not self.wide))
         if step.ride:
             self._check_batch(users.numel())
         batch_lists = self._plan_reach_rider(step, (users, pos, neg, n_valid))

@@ -952,6 +952,57 @@ def bpr_wide_workspace(global_B: int, device) -> torch.Tensor:
     return torch.empty(need, dtype=torch.uint8, device=device)
 
 
+def bpr_plan_wide_workspace(B_max: int, device) -> torch.Tensor:
+    """A workspace of llmrec_bpr_scatter_plan_wide_workspace_bytes(B_max) bytes for llmrec_bpr_scatter_plan_wide (uninitialised)."""
+    need = _lib.query("llmrec_bpr_scatter_plan_wide_workspace_bytes", int(B_max))
+    if need < 0:
+        raise RuntimeError("bpr_plan_wide_workspace: batch of %d exceeds LLMREC_BPR_WIDE_MAX_B" % B_max)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def bpr_multi_wide_workspace(n_problems: int, B_max: int, device) -> torch.Tensor:
+    """A workspace of llmrec_bpr_multi_wide_workspace_bytes(n_problems, B_max) bytes for llmrec_bpr_multi_select_bwd_wide_f32
+    (uninitialised: the entry point's own launches initialise it)."""
+    need = _lib.query("llmrec_bpr_multi_wide_workspace_bytes", int(n_problems), int(B_max))
+    if need < 0:
+        raise RuntimeError("bpr_multi_wide_workspace: %d problems / a batch of %d exceed LLMREC_BPR_MAX_PROBLEMS / LLMREC_BPR_WIDE_MAX_B"
+                           % (n_problems, B_max))
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def bpr_scatter_plan_wide(users, pos, neg, n_valid, out: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """llmrec_bpr_scatter_plan_wide: bpr_scatter_plan's words for a batch of any size up to LLMREC_BPR_WIDE_MAX_B (ws: bpr_plan_wide_workspace)."""
+    _need_gpu(users, pos, neg, out, ws)
+    B = users.numel()
+    if out.numel() < bpr_plan_words(B) or out.dtype != torch.int64:
+        raise RuntimeError("bpr_scatter_plan_wide: plan buffer needs %d int64 words" % bpr_plan_words(B))
+    _lib.call("llmrec_bpr_scatter_plan_wide", _p(users), _p(pos), _p(neg), B, _p(n_valid), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def bpr_multi_scores_wide(problems, d: int, users, pos, neg, n_valid, saved, row_stamp=None, adamw_state=None, lr: float = 0.0,
+                          beta1: float = 0.0, beta2: float = 0.0):
+    """llmrec_bpr_multi_scores_wide_f32 over a ctypes array of BprProblem (adamw_state None: the row stamp only)."""
+    _lib.call("llmrec_bpr_multi_scores_wide_f32", len(problems), problems, d, _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid), _p(saved),
+              _p(row_stamp), _p(adamw_state), float(lr), float(beta1), float(beta2), _stream())
+
+
+def bpr_multi_select_bwd_wide(problems, d: int, users, pos, neg, n_valid, remember_rate: float, decay: float, batch_size_flag: float, saved,
+                              flag_u, flag_i, row_stamp, plan, ws):
+    """llmrec_bpr_multi_select_bwd_wide_f32 (ws: bpr_multi_wide_workspace; plan: bpr_scatter_plan_wide or, up to the cap, bpr_scatter_plan)."""
+    _lib.call("llmrec_bpr_multi_select_bwd_wide_f32", len(problems), problems, d, _p(users), _p(pos), _p(neg), users.numel(), _p(n_valid),
+              float(remember_rate), float(decay), float(batch_size_flag), _p(saved), _p(flag_u), _p(flag_i), _p(row_stamp), _p(plan),
+              _p(ws), 0 if ws is None else ws.numel(), _stream())
+
+
+def bpr_multi_losses_wide(n_problems: int, B_max: int, n_valid, remember_rate: float, decay: float, batch_size_flag: float, out, saved,
+                          w_mf=None, partial=None, n_partial: int = 0, reg_coef: float = 0.0, scal=None, running=None):
+    """llmrec_bpr_multi_losses_wide_f32 (scal None: the loss values only)."""
+    w = None if w_mf is None else (_c.c_float * n_problems)(*w_mf)
+    _lib.call("llmrec_bpr_multi_losses_wide_f32", n_problems, B_max, _p(n_valid), float(remember_rate), float(decay), float(batch_size_flag),
+              _p(out), _p(saved), w, _p(partial), int(n_partial), float(reg_coef), _p(scal), _p(running), _stream())
+
+
 _scatter_ws = {}                                                   # device -> the sorted scatter's workspace (grown, never shrunk)
 
 

@@ -17,6 +17,24 @@ ENV_SWITCHES = ("LLMREC_STREAMS", "LLMREC_GEMM", "LLMREC_PREPROPAGATE", "LLMREC_
 TRAINER_SWITCHES = ("LLMREC_FUSED", "LLMREC_GRAPH", "LLMREC_DEVICE_SAMPLER", "LLMREC_FUSED_DROPOUT", "LLMREC_EVAL_GRAPH")
 
 
+def route(fused: Optional[str], fused_dropout: Optional[str], *, mask, mask_rate: float, drop_rate: float, b_max: int, cap: int,
+          wide_cap: int) -> str:
+    """Which path trains a step: "fused" (FusedStep, the capped loss segment), "fused_wide" (FusedStep above its WIDE_FROM: the wide loss
+    segment) or "modular" (the per-op autograd path). Pure: main.py reads the environment and the device itself.
+    fused / fused_dropout: the values of LLMREC_FUSED / LLMREC_FUSED_DROPOUT (None: unset); mask / mask_rate / drop_rate: the trainer's
+    flags; b_max: the step's batch capacity (batch_size + its augmented share); cap / wide_cap: LLMREC_BPR_MAX_B / LLMREC_BPR_WIDE_MAX_B.
+    LLMREC_FUSED: unset or "1" - the fused step up to `cap`, the modular path above it; "wide" (opt-in) - the same step up to `cap` and
+    the wide loss segment up to `wide_cap`; anything else - the modular path. The reference masks user features whenever
+    mask_rate > 0, with or without --mask, and the fused step reads the unmasked features; --drop_rate > 0 stays fused under
+    LLMREC_FUSED_DROPOUT=1 only."""
+    fused = "1" if fused is None else fused
+    if fused not in ("1", "wide") or mask or mask_rate != 0 or not (drop_rate == 0 or fused_dropout == "1"):
+        return "modular"
+    if b_max <= cap:
+        return "fused"
+    return "fused_wide" if fused == "wide" and b_max <= wide_cap else "modular"
+
+
 class StepOptions(NamedTuple):
     """The resolved switches of one step: FusedStep's attributes of the same names."""
     drop_rate: float

@@ -357,14 +357,15 @@ class Trainer(object):
         if self._fused is None:
             # the reference masks user features whenever mask_rate > 0, with or without --mask (Models.py:139-142):
             # the fused path reads the unmasked features, so any of the three sends the step down the modular path
-            fused_dropout = os.environ.get("LLMREC_FUSED_DROPOUT", "0") == "1"
-            ok = (os.environ.get("LLMREC_FUSED", "1") == "1" and not args.mask and (args.drop_rate == 0 or fused_dropout)
-                  and args.mask_rate == 0 and device.type == "cuda")
             # the fused step's eight-problem loss launches stage the batch in LDS (LLMREC_BPR_MAX_B); a larger batch trains on the
-            # modular path, whose ops.bpr_prune selects with the multi-block kernels
+            # modular path, whose ops.bpr_prune selects with the multi-block kernels - or, under LLMREC_FUSED=wide (opt-in), in the
+            # fused step's wide loss segment (FusedStep.WIDE_FROM). The predicate: step_options.route
+            from llmrec_amd import step_options
             b_max = self.batch_size + int(self.batch_size * args.aug_sample_rate)
-            ok = ok and b_max <= ops.CONST["LLMREC_BPR_MAX_B"]
-            if ok:
+            path = step_options.route(os.environ.get("LLMREC_FUSED"), os.environ.get("LLMREC_FUSED_DROPOUT"), mask=args.mask,
+                                      mask_rate=args.mask_rate, drop_rate=args.drop_rate, b_max=b_max,
+                                      cap=ops.CONST["LLMREC_BPR_MAX_B"], wide_cap=ops.CONST["LLMREC_BPR_WIDE_MAX_B"])
+            if path != "modular" and device.type == "cuda":
                 from llmrec_amd.fused import FusedStep
                 graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(self.ui_graph),
                                        "iu": ops.operand_from_sparse_tensor(self.iu_graph)})
