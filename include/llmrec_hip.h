@@ -1051,6 +1051,88 @@ int llmrec_dropout_rows_f32(int64_t rows, int32_t cols, float* X, int64_t ldx, f
                             int32_t* ticket /* NULL: do not advance */, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * R13  feature masking and attribute restoration   replaces MM_Model's in-place masking (reference
+ *                                        Models.py:130-142) and the restoration term of the loss
+ *                                        (main.py:258-273) in the fused step (opt-in).
+ * The node lists are NOT torch.randperm's: they are the pure function below of (seed, round, side).
+ *
+ * llmrec_mask_nodes: nodes[j] = keyed_perm(j, N) for j < m - m distinct ids below N.
+ *   keyed_perm  the sampler's keyed bijection of [0, N) (R11): a 4-round balanced Feistel network on 2 h bits, h the smallest
+ *               h >= 1 with 4^h >= N; round r's function = the low h bits of the 64-bit word o[1] << 32 | o[0] of Philox4x32-10 at
+ *               the counter (R low word, R high word ^ (0xA5A50000 + r), w low word, w high word); cycle-walk while the image is >= N.
+ *   key         k = seed ^ 0x6A09E667F3BCC908 (key words: k low, k high) - beside the sampler's seed and
+ *               seed ^ 0x9E3779B97F4A7C15 and the dropout's seed ^ 0xD1B54A32D192ED03.
+ *   w           (2 s + side) mod 2^64, s = *step_dev as the launch reads it (the mask round); side = LLMREC_MASK_SIDE_USERS (0) or
+ *               LLMREC_MASK_SIDE_ITEMS (1).
+ *   ticket      NULL: the launch only READS *step_dev. Else one int32 of device memory, ZERO before the first call: the count-off of
+ *               llmrec_sample_batch_wide - the block that draws the last ticket adds 1 to *step_dev and puts the ticket back to 0. The
+ *               caller orders the ticketed launch behind the round's other reader. m == 0 with a ticket still advances the counter.
+ * LLMREC_EINVAL before any HIP call: N < 1 or N >= 2^40; m < 0 or m > N; another side; a null step_dev; a null nodes with m > 0.
+ *
+ * llmrec_col_sums_f64 / llmrec_mask_rows_f32 act on n_tensors (1 .. LLMREC_MASK_MAX_TENSORS) row-major [N, cols] fp32 views with ONE
+ * ldx >= cols (columns [cols, ldx) are never read or written; 64-bit element offsets) and one fp64 array sums[cols] each. X_host /
+ * sums_host are HOST arrays of device pointers, read during the call.
+ *   col_sums    sums[c] = the sum of column c in this tree, whatever the grid: row lane j (j < LLMREC_MASK_ROW_LANES = 8) adds rows
+ *               j, j + 8, j + 16, ... in ascending order, in fp64, from +0.0; then ((((((l0 + l1) + l2) + l3) + l4) + l5) + l6) + l7.
+ *   mask_rows   one round, per tensor and column c, every operation in fp64 rounded once (no fused multiply-add):
+ *                 mean = (float) (sums[c] / (double) N)               [round to nearest even]
+ *                 old  = the sum of X[nodes[i]][c] over i < m in col_sums' tree over the LIST POSITIONS i (lane j: i = j, j + 8, ...)
+ *                 X[nodes[i]][c] = mean for every i < m
+ *                 sums[c] = sums[c] + ((double) m * (double) mean - old)
+ *               The nodes are read from device memory and must be distinct ids in [0, N) (llmrec_mask_nodes' are); nothing checks
+ *               them. m == 0 succeeds without a launch.
+ * LLMREC_EINVAL before any HIP call: n_tensors outside [1, 8]; N < 1; cols < 1; ldx < cols; m < 0 or m > N; a null array or entry;
+ * a tensor base that is not 4-byte aligned or sums that are not 8-byte aligned; a null nodes with m > 0.
+ *
+ * llmrec_restore_loss_f32: n_streams (1 .. 8) streams share the node list, the decoder y = W x + b (W [F, d] row-major with ldw,
+ * b [F]; LeakyReLU(True) has slope 1: the identity) and the loss. Stream s reads the rows x_r = X_host[s][nodes[r]][0 .. d) and the
+ * targets t_r = T_host[s][nodes[r]][0 .. F), r < m, and returns
+ *   row_loss[s m + r]   LLMREC_RESTORE_SCE: (1 - cos_r)^alpha;   LLMREC_RESTORE_MSE: (yy / ny^2 + tt / nt^2 - 2 cos_r) / F
+ *                       with yy = y.y, yt = y.t, tt = t.t, ny = max(sqrt(yy), 1e-12f), nt = max(sqrt(tt), 1e-12f) (F.normalize's eps),
+ *                       cos_r = yt / (ny nt);
+ *   loss_out[s]         the 1024-slot tree of llmrec_bpr_multi_losses_assemble_f32 over row_loss[s m ..], divided by (float) m:
+ *                       mean_r (1 - cos)^alpha, resp. F.mse_loss(normalize(y), normalize(t));
+ *   dX_host != NULL     dX_host[s][nodes[r]][k] += scale * (cb p[k] + ca q[k]),  p = W^T y_r, q = W^T t_r  (= scale * dL_s / dx_r):
+ *                         SCE  g = alpha (1 - cos)^(alpha - 1) / m;  ca = -g / (ny nt);  cb = g cos / ny^2, or 0 where sqrt(yy) < 1e-12f
+ *                         MSE  g = 2 / (m F);                        ca = -g / (ny nt);  cb = g cos / ny^2, or g / ny^2 there
+ *                       The node list must be duplicate-free (each destination row is read and written by one wavefront).
+ *                       NULL: value only, nothing but row_loss / loss_out (and the flags) is written.
+ *   row_flags           with row_stamp (both or neither): row_flags[nodes[r]] = LLMREC_ROW_STAMP(*row_stamp) - the rows join the
+ *                       step's stamped rows, so llmrec_fuse_bwd_src_multi_f32 reads their sources.
+ * Arithmetic: exact fp32, v_mfma_f32_16x16x4_f32 fma chains, no [rows, F] intermediate in memory. y[f] is the chain over
+ * k = 16 j + 4 q + c in the order j, c, q (dense.hip's) plus b[f]; yy / yt / tt are, per lane, an fma chain over f = 16 n + 4 l + i
+ * (n, then i, ascending) for l = 0 .. 3, combined (l0 + l1) + (l2 + l3); p[k] and q[k] are fma chains over f in the order n, i, l.
+ * alpha 1, 2, 3 are products, any other value powf.
+ * LLMREC_EINVAL before any HIP call: n_streams outside [1, 8]; m < 1 (the mean over an empty list is the reference's NaN: such a
+ * step is not the library's) or m >= 2^31; F < 1; d < 1; another loss_type; alpha outside [1, 64] or NaN; a null nodes, W, b, row_loss,
+ * loss_out, X_host, T_host or entry; one of row_flags / row_stamp without the other; ldx < d, ldt < F, ldw < d, lddx < d; a base that
+ * is not 4-byte aligned. LLMREC_EUNSUPPORTED (nothing launched): d != 64.
+ *
+ * llmrec_restore_finish_f32: ONE launch behind the step's readers of both. (1) with n_values > 0: tot = ((v0 + v1) + ...) in fp32,
+ * add = rate * tot; scal4[1] += add and running_sums3[0] += (double) add (either may be NULL). (2) with n_views > 0 and m > 0:
+ * columns [0, cols) of the rows nodes[0 .. m) of every view (one ld) become +0.0f. LLMREC_EINVAL: n_values outside [0, 16] or
+ * without values; n_views outside [0, 8]; m < 0; with views to clear, a null pointer, cols < 1 or ld < cols.
+ * ------------------------------------------------------------------------------------------ */
+#define LLMREC_MASK_ROW_LANES 8
+#define LLMREC_MASK_MAX_TENSORS 8
+#define LLMREC_MASK_SIDE_USERS 0
+#define LLMREC_MASK_SIDE_ITEMS 1
+#define LLMREC_RESTORE_SCE 0
+#define LLMREC_RESTORE_MSE 1
+int llmrec_mask_nodes(int64_t N, int64_t m, uint64_t seed, uint64_t* step_dev, int32_t side, int64_t* nodes,
+                      int32_t* ticket /* NULL: do not advance */, llmrec_stream_t stream);
+int llmrec_col_sums_f64(int32_t n_tensors, const float* const* X_host, int64_t ldx, double* const* sums_host, int64_t N, int32_t cols,
+                        llmrec_stream_t stream);
+int llmrec_mask_rows_f32(int32_t n_tensors, float* const* X_host, int64_t ldx, double* const* sums_host, int64_t N, int32_t cols,
+                         const int64_t* nodes, int64_t m, llmrec_stream_t stream);
+int llmrec_restore_loss_f32(int32_t n_streams, const float* const* X_host, int64_t ldx, const float* const* T_host, int64_t ldt,
+                            float* const* dX_host /* NULL: value only */, int64_t lddx, const int64_t* nodes, int64_t m,
+                            int32_t d, int32_t F, const float* W, int64_t ldw, const float* b, int32_t loss_type, float alpha, float scale,
+                            float* row_loss, float* loss_out, uint8_t* row_flags, const int32_t* row_stamp, llmrec_stream_t stream);
+int llmrec_restore_finish_f32(int32_t n_values, const float* values, float rate, float* scal4, double* running_sums3, int32_t n_views,
+                              float* const* views_host, int64_t ld, int32_t cols, const int64_t* nodes, int64_t m, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`; nothing on the product path calls it). One single-lane launch that
  * stores the device's constant-rate real-time counter (s_memrealtime) into *slot when the stream reaches it.
  * A captured HIP graph cannot carry event-record nodes for external events; a pair of these around a launch

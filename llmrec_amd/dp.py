@@ -58,7 +58,12 @@ class DataParallelStep(FusedStep):
     replica or a loop-back harness that moves the two exchange buffers itself (rank=, world=)."""
 
     def __init__(self, model, graph, hp, rates, optimizer, b_max: int, comm=None, rank: int = None, world: int = None,
-                 drop_rate: float = 0.0, drop_seed: int = 0):
+                 drop_rate: float = 0.0, drop_seed: int = 0, **mask_options):
+        if mask_options:
+            # (mask_rate, mask_items, mask_seed, decoder, ...: the replicas would have to mask the replicated features with ONE list and
+            # advance one round counter across three phases)
+            raise RuntimeError("DataParallelStep: %s not supported; feature masking inside the step is FusedStep's (single replica) only"
+                               % ", ".join(sorted(mask_options)))
         if drop_rate != 0:
             # (the replicas would have to draw ONE mask for the replicated projections and advance one counter across three phases)
             raise RuntimeError("DataParallelStep: drop_rate = %r is not supported; dropout inside the step is FusedStep's (single replica) only"

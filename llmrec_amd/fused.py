@@ -19,8 +19,9 @@ main.py:228-278); what changes is the organisation:
   * the embedding tables' AdamW reads its gradient where it is formed (the user table's is inv * dE_u) and the row-wise clean-up of the
     scatter targets rides in the item table's AdamW launch;
   * nothing allocates or synchronises, so the step replays from a HIP graph (``capture()``): no per-launch host cost, which dominates here.
-Falls outside its scope (use the modular path): the --mask branch, and dropout > 0 unless the step is built for it (drop_rate=: the
-project's own counter-based masks on the device, llmrec_dropout_rows_f32 - step_options.resolve, "DROPOUT").
+Falls outside its scope (use the modular path) unless the step is built for it: dropout > 0 (drop_rate=: the project's own counter-based
+masks on the device, llmrec_dropout_rows_f32 - step_options.resolve, "DROPOUT") and --mask / --mask_rate > 0 (mask_rate=, mask_items=, the
+decoder and targets: llmrec_mask_nodes' lists, running column sums, the restoration launches - _mask_round, _restore).
 Schedule switches that remain: LLMREC_STREAMS=1 (four streams), LLMREC_FOLD=0 (the separate small launches) and LLMREC_HOST_CHAIN=0 / fwd (no hosted
 product: the chain's products in SpMM launches of their own / the forward's hosted only) are the A/B references of the default schedule; LLMREC_PREPROPAGATE, LLMREC_GEMM and LLMREC_WGRAD_ROWS choose the arithmetic's organisation. The class switches
 FOLD = False, INLINE_ADAMW = False and WGRAD_ROWS = False are DataParallelStep's (llmrec_amd/dp.py: its replicas all-reduce the
@@ -118,10 +119,18 @@ class FusedStep:
     # histogram passes, the ties' count, the write pass, the backward rows) against 2, its plan 4 (keys, two sorts, run lengths) against 1.
     WIDE_FROM = _lib.CONST["LLMREC_BPR_MAX_B"]
 
-    def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int, drop_rate: float = 0.0, drop_seed: int = 0):
+    def __init__(self, model, graph, hp: Hyper, rates, optimizer: ops.FusedAdamW, b_max: int, drop_rate: float = 0.0, drop_seed: int = 0,
+                 mask_rate: float = 0.0, mask_items: bool = False, mask_seed: int = 0, decoder=None, user_targets=None, item_targets=None,
+                 att_re_rate: float = 0.0, feat_loss_type: str = "sce", alpha_l: float = 2.0):
         """model: Models.MM_Model (parameters + constant feature tensors); graph: ops.BipartiteGraph
         or any object with .ui/.iu SparseOperands; rates: (model_cat, user_cat, item_cat); drop_rate / drop_seed: dropout on the eight
-        projections inside the step (reference Models.py:145-150; step_options.resolve, "DROPOUT") - 0 = none: the step is what it is without the option."""
+        projections inside the step (reference Models.py:145-150; step_options.resolve, "DROPOUT") - 0 = none: the step is what it is without the option.
+        mask_rate / mask_items / mask_seed: feature masking inside the step (reference Models.py:130-142; _mask_round) - every forward
+        overwrites int(mask_rate * n_users) rows of model.user_feats and, with mask_items (--mask), int(mask_rate * n_items) rows of every
+        attribute feature matrix with the column mean, in place and cumulatively; the lists are llmrec_mask_nodes' stream of
+        (mask_seed, round, side), not torch.randperm's. decoder (Models.Decoder), user_targets [U, F] / item_targets {key: [I, F]} (the
+        unmasked embeddings), att_re_rate, feat_loss_type ("sce" / "mse") and alpha_l: the restoration term of main.py:258-273, added
+        with mask_items and att_re_rate != 0 (_restore). The defaults leave the step exactly what it is."""
         self.m, self.hp, self.opt = model, hp, optimizer
         self.ui, self.iu = graph.ui, graph.iu
         self.U, self.I = model.n_users, model.n_items
@@ -136,10 +145,23 @@ class FusedStep:
             raise RuntimeError("FusedStep: b_max %d exceeds LLMREC_BPR_WIDE_MAX_B = %d" % (b_max, _lib.CONST["LLMREC_BPR_WIDE_MAX_B"]))
         # every switch of the step - multi_stream, gemm, preprop, wgrad_rows, inline_adamw, fold, bwd_mask, bwd_zero_skip, host_chain,
         # host_wgrad, check_zero and the validated drop_rate - is decided once, with its rationale, in step_options.resolve(); below: allocation only
+        self.mask_rate, self.mask_items, self.mask_seed = float(mask_rate), bool(mask_items), int(mask_seed)
+        if not 0.0 <= self.mask_rate <= 1.0 or (self.mask_items and self.mask_rate == 0):      # (false for a NaN)
+            raise ValueError("FusedStep: mask_rate %r outside [0, 1], or mask_items without a rate" % (mask_rate,))
+        if self.mask_rate > 0 and drop_rate != 0:
+            raise RuntimeError("FusedStep: feature masking and dropout inside one step are not supported")
+        self.m_users = int(self.mask_rate * self.U)
+        self.m_items = int(self.mask_rate * self.I) if self.mask_items else 0
+        if self.mask_items and (self.m_users == 0 or self.m_items == 0 or not self.keys):
+            # (the reference's restoration loss is then the mean over no rows, NaN: the per-op path's to produce - step_options.route)
+            raise RuntimeError("FusedStep: mask_items with an empty user or item list")
+        self.att_re_rate = float(att_re_rate)
+        self.restore = self.mask_items and self.att_re_rate != 0
         opts = step_options.resolve(None, n_users=self.U, n_items=self.I, d=d, n_attr=len(self.keys), drop_rate=drop_rate,
                                     wgrad_rows_default=self.WGRAD_ROWS, inline_adamw_default=self.INLINE_ADAMW, fold_default=self.FOLD,
                                     bwd_nnz=self.iu.bwd.nnz, bwd_valued=self.iu.bwd.val is not None,
-                                    bwd_col_scaled=self.iu.bwd.col_scale is not None, latency_nnz=ops.SPMM_LATENCY_NNZ)
+                                    bwd_col_scaled=self.iu.bwd.col_scale is not None, latency_nnz=ops.SPMM_LATENCY_NNZ,
+                                    mask_items=self.mask_items, restore=self.restore)
         for name, value in opts._asdict().items():
             setattr(self, name, value)
         self.drop_seed = int(drop_seed)
@@ -215,6 +237,28 @@ class FusedStep:
         if self.drop_rate > 0:                               # the masks' step counter and its launch's count-off (step_options: DROPOUT)
             self.drop_step = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
             self.drop_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.mask_rate > 0:
+            # the masking round's counter with its launch's count-off, the round's node lists (read again by the restoration launches)
+            # and one fp64 running column sum per masked tensor (_mask_round)
+            self.mask_step = torch.zeros(1, dtype=torch.int64, device=dev).view(torch.uint64)
+            self.mask_ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.mask_nodes_u = torch.zeros(max(self.m_users, 1), dtype=torch.int64, device=dev)[:self.m_users]
+            self.mask_nodes_i = torch.zeros(max(self.m_items, 1), dtype=torch.int64, device=dev)[:self.m_items]
+            self._masked_user, self._masked_items = [model.user_feats], [model.item_feats[k] for k in self.keys] if self.mask_items else []
+            self.user_sums = [torch.zeros(model.user_feats.shape[1], dtype=torch.float64, device=dev)]
+            self.item_sums = [torch.zeros(x.shape[1], dtype=torch.float64, device=dev) for x in self._masked_items]
+            self.refresh_feature_sums()
+        if self.restore:
+            if decoder is None or user_targets is None or item_targets is None or feat_loss_type not in ops.RESTORE_LOSS_TYPES:
+                raise RuntimeError("FusedStep: the restoration term needs the decoder, both target sets and feat_loss_type sce or mse")
+            if d != 64 or S > 2 + _lib.CONST["LLMREC_MASK_MAX_TENSORS"]:
+                raise RuntimeError("FusedStep: the restoration launches are compiled for d = 64 and at most %d attribute streams"
+                                   % _lib.CONST["LLMREC_MASK_MAX_TENSORS"])
+            as_target = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=torch.float32).contiguous()
+            self.decoder, self.feat_loss_type, self.alpha_l = decoder, feat_loss_type, float(alpha_l)
+            self.user_targets, self.item_targets = as_target(user_targets), [as_target(item_targets[k]) for k in self.keys]
+            self.re_rows_u, self.re_rows_i = f(self.m_users), f(len(self.keys) * self.m_items)     # the per-row terms (scratch)
+            self.re_vals = z(1 + len(self.keys))                                                   # [user, attribute k ...] stream losses
         if not self.preprop:
             self.P_cat, self.dP_cat = f(I, S * d), f(I, S * d)        # the projected features and their gradient (reference order)
         else:
@@ -443,6 +487,61 @@ class FusedStep:
         ops.dropout_rows_(usr, self.drop_rate, self.drop_seed, self.drop_step, ops.DROPOUT_TAG_USER_PROFILE,
                           ticket=self.drop_ticket if backward else None)
 
+    def refresh_feature_sums(self):
+        """The running column sums of the masked feature tensors from scratch (llmrec_col_sums_f64): at set-up, and after anything but
+        the step itself has written model.user_feats / model.item_feats."""
+        if self.mask_rate > 0:
+            ops.col_sums(self._masked_user, self.user_sums)
+            if self._masked_items:
+                ops.col_sums(self._masked_items, self.item_sums)
+
+    def _mask_round(self):
+        """One masking round ahead of a forward, training and evaluation alike (reference Models.py:131-142): the round's node lists,
+        then the listed rows of user_feats - and, with mask_items, of the attribute matrices (one launch for all of them: they share
+        the list) - become the column mean of the tensor as it stood before this round (llmrec_mask_rows_f32: no re-read of the
+        matrices). Read / write sets:
+          node launches  read the round counter; write the lists. The LAST one carries the ticket and advances the counter, so a
+                    replayed graph draws new lists with no host action. The lists' previous readers (the last step's restoration
+                    and clean-up launches) precede them in stream order.
+          row launches   read the lists and the running sums; write the listed rows and the sums. Their first reader is the
+                    projection launch, behind them on the same stream; no pre-propagated operand holds a masked tensor
+                    (step_options.resolve, MASKING)."""
+        ops.mask_nodes(self.U, self.m_users, self.mask_seed, self.mask_step, ops.MASK_SIDE_USERS, out=self.mask_nodes_u,
+                       ticket=None if self.mask_items else self.mask_ticket)
+        if self.mask_items:
+            ops.mask_nodes(self.I, self.m_items, self.mask_seed, self.mask_step, ops.MASK_SIDE_ITEMS, out=self.mask_nodes_i, ticket=self.mask_ticket)
+        if self.m_users:
+            ops.mask_rows_(self._masked_user, self.user_sums, self.mask_nodes_u)
+        if self.mask_items:
+            ops.mask_rows_(self._masked_items, self.item_sums, self.mask_nodes_i)
+
+    def _att_slices(self, cat):
+        return [self._side(cat, 2 + k) for k in range(len(self.keys))]
+
+    def _restore(self):
+        """The restoration term (reference main.py:258-271; restore = mask_items and att_re_rate != 0), behind the loss backward's
+        scatter and ahead of the fusion backward: the user stream for its value only (the reference detaches its input), the
+        attribute streams in one launch whose gradient rows go into the scatter source of dI_cat's attribute slices. Read / write sets:
+          user launch   reads prof_u, the user targets, decoder.u_net and the user list; writes re_rows_u and re_vals[0].
+          attribute launch   reads I_cat's attribute slices, the item targets, decoder.i_net and the item list; adds att_re_rate x the
+                    gradient into rows `list` of sc_I's attribute slices - behind the selection launch's scatter into the same buffer
+                    (stream order), ahead of their one reader, the fusion backward - and stamps those rows in flag_i with the step's
+                    stamp (the scores launch advanced it), so that the fusion backward reads them; writes re_rows_i and re_vals[1:].
+        What the step otherwise assumes about these rows is off: bwd_mask / bwd_zero_skip / wgrad_rows (step_options.resolve,
+        RESTORATION); _restore_finish clears them."""
+        u_net, i_net = self.decoder.u_net[0], self.decoder.i_net[0]
+        ops.restore_loss([self.prof_u], [self.user_targets], self.mask_nodes_u, u_net.weight.detach(), u_net.bias.detach(), self.feat_loss_type,
+                         self.alpha_l, self.re_rows_u, self.re_vals[:1])
+        ops.restore_loss(self._att_slices(self.I_cat), self.item_targets, self.mask_nodes_i, i_net.weight.detach(), i_net.bias.detach(),
+                         self.feat_loss_type, self.alpha_l, self.re_rows_i, self.re_vals[1:], dXs=self._att_slices(self.sc_I),
+                         scale=self.att_re_rate, row_flags=self.flag_i, row_stamp=self.row_stamp)
+
+    def _restore_finish(self):
+        """The restoration term's tail, ONE launch behind everything else of the step: att_re_rate x the stream losses joins the logged
+        loss (scal[1], epoch_sums[0] - written by the loss-value launch, earlier on this stream or joined), and the list's rows of
+        sc_I's attribute slices, read by the fusion backward, go back to zero: the scatter targets stay all-zero between steps."""
+        ops.restore_finish(self.re_vals, self.att_re_rate, self.scal, self.epoch_sums, views=[self.sc_I[:, 2 * self.d:]], nodes=self.mask_nodes_i)
+
     def _softmax_bwd(self, Y, dY, dZ, alpha: float = 1.0):
         _call("llmrec_softmax_rows_bwd_scaled_f32", Y.shape[0], self.d, float(alpha), _p(Y), _ld(Y), _p(dY), _ld(dY), _p(dZ), _ld(dZ))
 
@@ -463,19 +562,22 @@ class FusedStep:
         return (_c.c_float * len(r))(*r)
 
     # -- forward ----------------------------------------------------------------------------------
-    def forward(self, profile_on_main: bool = False):
-        """The evaluation's forward (no training step: it advances and consumes nothing). profile_on_main: the profile chain stays on the
-        current stream (the evaluation's graph, see eval_topk)."""
-        self._forward(None, profile_on_main=profile_on_main)
+    def forward(self, profile_on_main: bool = False, mask: bool = True):
+        """The evaluation's forward (no training step: it advances and consumes nothing - but, with mask_rate > 0, it is one masking
+        round, as the reference's). profile_on_main: the profile chain stays on the current stream (the evaluation's graph, see
+        eval_topk); mask=False: without the masking launches (the warm-up run ahead of an evaluation's capture)."""
+        self._forward(None, profile_on_main=profile_on_main, mask=mask)
 
     def _train_forward(self, sampler: Optional[_Rider] = None, after_chain: Optional[_Rider] = None, step: Optional[_TrainStep] = None):
         """The forward of a training step (step_eager's riders and record; DataParallelStep, which runs its own backward, passes none)."""
         self._forward(step if step is not None else _TrainStep(), sampler, after_chain)
 
-    def _forward(self, step: Optional[_TrainStep], sampler=None, after_chain=None, profile_on_main: bool = False):
+    def _forward(self, step: Optional[_TrainStep], sampler=None, after_chain=None, profile_on_main: bool = False, mask: bool = True):
         """step: the training step this forward belongs to, None = evaluation. sampler / after_chain: launches for the ID chain's stream,
-        ahead of / behind its SpMMs (the batch and what is derived from it)."""
+        ahead of / behind its SpMMs (the batch and what is derived from it). mask: with mask_rate > 0, begin with the masking round."""
         m, d = self.m, self.d
+        if mask and self.mask_rate > 0:
+            self._mask_round()
         if self.multi_stream:
             self._forward_streams(step, sampler, after_chain, profile_on_main)
         else:
@@ -664,6 +766,8 @@ class FusedStep:
             _call("llmrec_bpr_multi_select_bwd_wide_f32", *select, _p(self.ws_sel_wide), self.ws_sel_wide.numel())
         else:
             _call("llmrec_bpr_multi_select_bwd_f32", *select)
+        if self.restore:
+            self._restore()
         # The loss values and the logged scalars, on the ID chain's stream (_backward places them: a branch of their own right behind the BPR
         # launches - the graph ran it as the step's tail). Folded: ONE launch - loss values + regulariser (the fusion launch's partial sums) +
         # assembly - and, where the step's riders apply, the same launch as a guest of the backward's first SpMM group (_backward_one_stream).
@@ -685,6 +789,8 @@ class FusedStep:
         self._backward(probs, users, pos, neg, n_valid, bpr_bwd_done=True, side_work=values, ev_reach=step.ev_reach)
         if not self.fold:
             self._join(self.s3)
+        if self.restore:
+            self._restore_finish()
 
     def _assemble_loss(self, mode: int, tail=None, inv_world: float = 1.0):
         """Logged scalars (main.py:273,280-283) from the 8 BPR results + the regulariser: one single-wave launch."""
@@ -1188,11 +1294,11 @@ class FusedStep:
             scoring = (n, _p(q), _p(self.E_u), _ld(self.E_u), _p(self.E_i), _ld(self.E_i), self.I, self.d,
                        _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None)
 
-            def run():
+            def run(mask=True):
                 # the evaluation's graph has TWO branches (the ID chain beside the projection; the profile chain stays on the main stream):
                 # 0.572 ms per replay back to back / 0.599 one at a time, against 0.73 - 0.76 / 0.595 with the training forward's three
                 # side branches - successive launches of a many-branch graph pay for their cross-queue joins (tools/eval_probe.py, round 6)
-                self.forward(profile_on_main=True)
+                self.forward(profile_on_main=True, mask=mask)
                 if wide:
                     _call("llmrec_score_topk_wide_f32", *scoring, K, _p(idx), _p(sc), _p(ws), ws.numel(), ops.topk_wide_mode(None, self.I, self.d, K), nnz)
                 else:
@@ -1206,7 +1312,7 @@ class FusedStep:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                run()
+                run(mask=False)                                # (one eval_topk call is ONE masking round: the replay below)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()

@@ -1462,6 +1462,96 @@ def dropout_rows_(X: torch.Tensor, p: float, seed: int, step_dev: torch.Tensor, 
     return X
 
 
+# R13: feature masking and attribute restoration (include/llmrec_hip.h states every contract)
+K_MASK = 0x6A09E667F3BCC908           # the node lists' key: seed ^ K_MASK
+MASK_SIDE_USERS, MASK_SIDE_ITEMS = CONST["LLMREC_MASK_SIDE_USERS"], CONST["LLMREC_MASK_SIDE_ITEMS"]
+MASK_ROW_LANES = CONST["LLMREC_MASK_ROW_LANES"]
+RESTORE_LOSS_TYPES = {"sce": CONST["LLMREC_RESTORE_SCE"], "mse": CONST["LLMREC_RESTORE_MSE"]}
+
+
+def _views(ts: Sequence[torch.Tensor], what: str, width: Optional[int] = None):
+    """(host array of the views' addresses, their common leading dimension): 2-D fp32 GPU views of one shape with inner stride 1."""
+    _need_gpu(*ts)
+    t0 = ts[0]
+    for t in ts:
+        if (t.dtype != torch.float32 or t.dim() != 2 or t.shape != t0.shape or (t.shape[1] > 1 and t.stride(1) != 1) or _ld(t) != _ld(t0)
+                or (width is not None and t.shape[1] != width)):
+            raise RuntimeError("%s: 2-D fp32 views of one shape and row stride with inner stride 1 expected" % what)
+    return (_c.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), _ld(t0)
+
+
+def mask_nodes(N: int, m: int, seed: int, step_dev: torch.Tensor, side: int, out: Optional[torch.Tensor] = None,
+               ticket: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """llmrec_mask_nodes: the m distinct masked ids of [0, N) of round step_dev[0] and `side` as int64 [m]; with a ticket (int32[1],
+    zero before the first call) the launch also advances the round."""
+    _need_gpu(step_dev, out, ticket)
+    if step_dev.dtype not in (torch.int64, torch.uint64) or (ticket is not None and ticket.dtype != torch.int32):
+        raise RuntimeError("mask_nodes: a 64-bit integer round counter and an int32 ticket expected")
+    if out is None:
+        out = torch.empty(max(int(m), 1), dtype=torch.int64, device=step_dev.device)
+    if out.dtype != torch.int64 or out.numel() < m or not out.is_contiguous():
+        raise RuntimeError("mask_nodes: a contiguous int64 buffer of at least m entries expected")
+    _lib.call("llmrec_mask_nodes", int(N), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(step_dev), int(side), _p(out), _p(ticket), _stream())
+    return out[:m]
+
+
+def _sums_table(sums: Sequence[torch.Tensor], cols: int, what: str):
+    _need_gpu(*sums)
+    if any(s.dtype != torch.float64 or s.numel() != cols or not s.is_contiguous() for s in sums):
+        raise RuntimeError("%s: one contiguous float64 [cols] tensor of sums per view expected" % what)
+    return (_c.c_void_p * len(sums))(*[s.data_ptr() for s in sums])
+
+
+def col_sums(Xs: Sequence[torch.Tensor], sums: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """llmrec_col_sums_f64: the fp64 column sums of the equally shaped views Xs, from scratch, by the header's fixed tree."""
+    xp, ldx = _views(Xs, "col_sums")
+    N, cols = Xs[0].shape
+    if sums is None:
+        sums = [torch.empty(cols, dtype=torch.float64, device=Xs[0].device) for _ in Xs]
+    _lib.call("llmrec_col_sums_f64", len(Xs), xp, ldx, _sums_table(sums, cols, "col_sums"), N, cols, _stream())
+    return list(sums)
+
+
+def mask_rows_(Xs: Sequence[torch.Tensor], sums: Sequence[torch.Tensor], nodes: torch.Tensor):
+    """llmrec_mask_rows_f32: one masking round IN PLACE - rows `nodes` (int64, distinct, device) of every view become the column mean
+    taken from the running sums, which follow."""
+    xp, ldx = _views(Xs, "mask_rows_")
+    N, cols = Xs[0].shape
+    _need_gpu(nodes)
+    if nodes.dtype != torch.int64 or not nodes.is_contiguous() or len(sums) != len(Xs):
+        raise RuntimeError("mask_rows_: a contiguous int64 node list and one sums tensor per view expected")
+    _lib.call("llmrec_mask_rows_f32", len(Xs), xp, ldx, _sums_table(sums, cols, "mask_rows_"), N, cols, _p(nodes), nodes.numel(), _stream())
+
+
+def restore_loss(Xs: Sequence[torch.Tensor], Ts: Sequence[torch.Tensor], nodes: torch.Tensor, W: torch.Tensor, b: torch.Tensor,
+                 loss_type: str, alpha: float, row_loss: torch.Tensor, loss_out: torch.Tensor, dXs: Optional[Sequence[torch.Tensor]] = None,
+                 scale: float = 1.0, row_flags: Optional[torch.Tensor] = None, row_stamp: Optional[torch.Tensor] = None):
+    """llmrec_restore_loss_f32: per stream s, loss_out[s] = the restoration loss of decoder(Xs[s][nodes]) against Ts[s][nodes] and, with
+    dXs, dXs[s][nodes] += scale * its gradient. row_loss: fp32 [len(Xs) * len(nodes)] scratch (the per-row terms stay readable)."""
+    d, F = W.shape[1], W.shape[0]
+    xp, ldx = _views(Xs, "restore_loss", d)
+    tp, ldt = _views(Ts, "restore_loss", F)
+    dp, lddx = _views(dXs, "restore_loss", d) if dXs is not None else (None, 0)
+    _need_gpu(nodes, W, b, row_loss, loss_out, row_flags, row_stamp)
+    m, n = nodes.numel(), len(Xs)
+    if (len(Ts) != n or (dXs is not None and len(dXs) != n) or nodes.dtype != torch.int64 or not nodes.is_contiguous()
+            or W.dtype != torch.float32 or W.stride(1) != 1 or b.dtype != torch.float32 or b.numel() != F or not b.is_contiguous()
+            or row_loss.dtype != torch.float32 or row_loss.numel() < n * m or loss_out.dtype != torch.float32 or loss_out.numel() < n
+            or not row_loss.is_contiguous() or not loss_out.is_contiguous()):
+        raise RuntimeError("restore_loss: mismatched streams, node list, decoder or output buffers")
+    _lib.call("llmrec_restore_loss_f32", n, xp, ldx, tp, ldt, dp, lddx, _p(nodes), m, d, F, _p(W), _ld(W), _p(b), RESTORE_LOSS_TYPES[loss_type],
+              float(alpha), float(scale), _p(row_loss), _p(loss_out), _p(row_flags), _p(row_stamp), _stream())
+
+
+def restore_finish(values: Optional[torch.Tensor], rate: float, scal: Optional[torch.Tensor], running: Optional[torch.Tensor],
+                   views: Sequence[torch.Tensor] = (), nodes: Optional[torch.Tensor] = None):
+    """llmrec_restore_finish_f32: scal[1] += rate * sum(values) (and running[0], in double); rows `nodes` of `views` become zero."""
+    vp, ld = _views(views, "restore_finish") if len(views) else (None, 0)
+    _need_gpu(values, scal, running, nodes)
+    _lib.call("llmrec_restore_finish_f32", 0 if values is None else values.numel(), _p(values), float(rate), _p(scal), _p(running), len(views), vp,
+              ld, views[0].shape[1] if len(views) else 0, _p(nodes), nodes.numel() if nodes is not None else 0, _stream())
+
+
 def topk_metrics(idx: torch.Tensor, hits: torch.Tensor, query_users: torch.Tensor, test_rowptr: torch.Tensor, Ks) -> torch.Tensor:
     """Per-user [n, 4, len(Ks)] float64 (precision, recall, ndcg, hit_ratio) on the device (llmrec_topk_metrics)."""
     _need_gpu(idx, hits, query_users, test_rowptr)

@@ -18,16 +18,30 @@ TRAINER_SWITCHES = ("LLMREC_FUSED", "LLMREC_GRAPH", "LLMREC_DEVICE_SAMPLER", "LL
 
 
 def route(fused: Optional[str], fused_dropout: Optional[str], *, mask, mask_rate: float, drop_rate: float, b_max: int, cap: int,
-          wide_cap: int) -> str:
+          wide_cap: int, n_users: int = 0, n_items: int = 0) -> str:
     """Which path trains a step: "fused" (FusedStep, the capped loss segment), "fused_wide" (FusedStep above its WIDE_FROM: the wide loss
     segment) or "modular" (the per-op autograd path). Pure: main.py reads the environment and the device itself.
     fused / fused_dropout: the values of LLMREC_FUSED / LLMREC_FUSED_DROPOUT (None: unset); mask / mask_rate / drop_rate: the trainer's
     flags; b_max: the step's batch capacity (batch_size + its augmented share); cap / wide_cap: LLMREC_BPR_MAX_B / LLMREC_BPR_WIDE_MAX_B.
     LLMREC_FUSED: unset or "1" - the fused step up to `cap`, the modular path above it; "wide" (opt-in) - the same step up to `cap` and
-    the wide loss segment up to `wide_cap`; anything else - the modular path. The reference masks user features whenever
-    mask_rate > 0, with or without --mask, and the fused step reads the unmasked features; --drop_rate > 0 stays fused under
-    LLMREC_FUSED_DROPOUT=1 only."""
+    the wide loss segment up to `wide_cap`; "mask" (opt-in) - as "1", and --mask / --mask_rate > 0 stay in the fused step (below);
+    anything else - the modular path. The reference masks user features whenever mask_rate > 0, with or without --mask, and the
+    default fused step reads the unmasked features; --drop_rate > 0 stays fused under LLMREC_FUSED_DROPOUT=1 only.
+    LLMREC_FUSED=mask with --mask or --mask_rate != 0 (FusedStep(mask_rate=, mask_items=, ...): the library's node lists, not
+    torch.randperm's) still goes to the modular path for: a batch above `cap` (no wide segment with masking); --drop_rate > 0
+    (no fused dropout with masking, whatever LLMREC_FUSED_DROPOUT says); a mask_rate outside (0, 1]; --mask with an empty user or item
+    list, int(mask_rate * n_users) == 0 or int(mask_rate * n_items) == 0 - the reference's loss is then NaN (the mean over no rows),
+    which stays the per-op path's to produce. n_users / n_items (keywords; 0 = unknown, so --mask is refused): the graph's sizes."""
     fused = "1" if fused is None else fused
+    if fused == "mask":
+        if not mask and mask_rate == 0:
+            fused = "1"                                    # nothing to mask: the default step
+        else:
+            if b_max > cap or drop_rate != 0 or not 0.0 < mask_rate <= 1.0:
+                return "modular"
+            if mask and (int(mask_rate * n_users) == 0 or int(mask_rate * n_items) == 0):
+                return "modular"
+            return "fused"
     if fused not in ("1", "wide") or mask or mask_rate != 0 or not (drop_rate == 0 or fused_dropout == "1"):
         return "modular"
     if b_max <= cap:
@@ -53,10 +67,12 @@ class StepOptions(NamedTuple):
 
 def resolve(env: Optional[Mapping[str, str]], *, n_users: int, n_items: int, d: int, n_attr: int, drop_rate: float, wgrad_rows_default: bool,
             inline_adamw_default: bool, fold_default: bool, bwd_nnz: int, bwd_valued: bool, bwd_col_scaled: bool,
-            latency_nnz: int) -> StepOptions:
+            latency_nnz: int, mask_items: bool = False, restore: bool = False) -> StepOptions:
     """env: the environment (None: the process's own); n_users / n_items / d: the shapes; n_attr: the number of attribute streams; the
     three class defaults; bwd_*: the backward's side product (iu.bwd) - its nnz, whether it keeps values, whether it has a column
-    scale; latency_nnz: ops.SPMM_LATENCY_NNZ, the nnz below which a product is latency-bound."""
+    scale; latency_nnz: ops.SPMM_LATENCY_NNZ, the nnz below which a product is latency-bound; mask_items: the step masks the attribute
+    features every forward (--mask); restore: it also adds the restoration term's gradient (--mask with att_re_rate != 0) - both move
+    existing fields only (MASKING below)."""
     if not 0.0 <= float(drop_rate) < 1.0:                  # (false for a NaN)
         raise ValueError("FusedStep: drop_rate %r outside [0, 1)" % (drop_rate,))
     drop_rate = float(drop_rate)
@@ -97,6 +113,14 @@ def resolve(env: Optional[Mapping[str, str]], *, n_users: int, n_items: int, d: 
         if want == "1":
             raise RuntimeError("FusedStep: drop_rate > 0 needs the reference's order of operations; LLMREC_PREPROPAGATE=1 cannot be honoured")
         preprop = False
+    # MASKING (mask_items; opt-in: main.py builds such a step under LLMREC_FUSED=mask only). The reference overwrites mask_rate of the rows
+    # of the five attribute feature matrices with the column mean at EVERY forward (Models.py:131-138), so A_ui F_k is no constant of the
+    # run: the step runs in the reference's order of operations, as with dropout. User-feature masking alone (mask_rate > 0 without
+    # --mask) changes user_feats only, which no pre-propagated operand holds: that step keeps the default schedule.
+    if mask_items:
+        if want == "1":
+            raise RuntimeError("FusedStep: mask_items needs the reference's order of operations; LLMREC_PREPROPAGATE=1 cannot be honoured")
+        preprop = False
     # ROW-LISTED weight gradient (VERDICT r03 next #4a; LLMREC_WGRAD_ROWS=0: the dense launch). The gradient of the five attribute
     # streams' projected features is EXACTLY ZERO outside the rows the batch reaches: an attribute stream meets the loss in the fused
     # embeddings and BPR terms of the batch's rows only (Models.py:160-163,188-197; main.py:249-254), so dU_cat[:, attribute columns] is
@@ -130,6 +154,11 @@ def resolve(env: Optional[Mapping[str, str]], *, n_users: int, n_items: int, d: 
     # its dense zeros (the dense weight-gradient fallbacks read every row).
     want = env.get("LLMREC_BWD_MASK", "1")
     bwd_mask = bool(want != "0" and fold and d == 64 and n_attr > 0 and bwd_nnz < latency_nnz and not bwd_valued and bwd_col_scaled)
+    # RESTORATION (restore): the term's gradient lands in the mask nodes' rows of dI_cat's attribute slices - rows the batch need not
+    # reach. The masked side product and the fusion backward's skip both rest on "zero outside the batch's rows": off. (So does the
+    # row-listed weight gradient, which is off already: mask_items has taken the pre-propagated operands away.)
+    if restore:
+        bwd_mask = False
     bwd_zero_skip = bwd_mask and want != "spmm"
     # HOSTED ID chain (round 15; LLMREC_HOST_CHAIN=0: the chain's first product in the first SpMM group, as before). The chain's first
     # product A_ui E_i needs nothing from the projection, and the grouped projection's last round of work units leaves block slots

@@ -353,7 +353,9 @@ class Trainer(object):
         --mask. LLMREC_FUSED=0 forces the modular autograd path; LLMREC_GRAPH=0 issues the fused step's
         launches one by one instead of replaying the captured HIP graph. LLMREC_FUSED_DROPOUT=1 (opt-in) keeps
         --drop_rate > 0 in the fused step: the masks are then the library's counter-based stream of
-        (--seed, step, tensor, row, column), not torch's."""
+        (--seed, step, tensor, row, column), not torch's. LLMREC_FUSED=mask (opt-in) keeps --mask / --mask_rate > 0 in the fused step:
+        the masked rows are then the library's lists of (--seed, round, side), not torch.randperm's (step_options.route names what
+        still leaves it)."""
         if self._fused is None:
             # the reference masks user features whenever mask_rate > 0, with or without --mask (Models.py:139-142):
             # the fused path reads the unmasked features, so any of the three sends the step down the modular path
@@ -364,12 +366,18 @@ class Trainer(object):
             b_max = self.batch_size + int(self.batch_size * args.aug_sample_rate)
             path = step_options.route(os.environ.get("LLMREC_FUSED"), os.environ.get("LLMREC_FUSED_DROPOUT"), mask=args.mask,
                                       mask_rate=args.mask_rate, drop_rate=args.drop_rate, b_max=b_max,
-                                      cap=ops.CONST["LLMREC_BPR_MAX_B"], wide_cap=ops.CONST["LLMREC_BPR_WIDE_MAX_B"])
+                                      cap=ops.CONST["LLMREC_BPR_MAX_B"], wide_cap=ops.CONST["LLMREC_BPR_WIDE_MAX_B"],
+                                      n_users=self.n_users, n_items=self.n_items)
             if path != "modular" and device.type == "cuda":
                 from llmrec_amd.fused import FusedStep
                 graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(self.ui_graph),
                                        "iu": ops.operand_from_sparse_tensor(self.iu_graph)})
                 drop = dict(drop_rate=args.drop_rate, drop_seed=args.seed) if args.drop_rate != 0 else {}
+                if args.mask or args.mask_rate != 0:             # (LLMREC_FUSED=mask: route() keeps no other value here)
+                    drop = dict(mask_rate=args.mask_rate, mask_items=bool(args.mask), mask_seed=args.seed)
+                    if args.mask:
+                        drop.update(decoder=self.decoder, user_targets=self.user_init_embedding, item_targets=self.item_attribute_embedding,
+                                    att_re_rate=args.att_re_rate, feat_loss_type="mse" if args.feat_loss_type == "mse" else "sce", alpha_l=args.alpha_l)
                 self._fused = FusedStep(self.model_mm, graph, self.hyper,
                                         (args.model_cat_rate, args.user_cat_rate, args.item_cat_rate), self.optimizer, b_max, **drop)
             else:
