@@ -92,16 +92,19 @@ def normalized_graphs(train_mat, dtype=torch.float32):
 # --------------------------------------------------------------------------------------------
 # R2-R6 - forward: reference Models.py:127-199
 # --------------------------------------------------------------------------------------------
-def forward(params: Dict[str, torch.Tensor], feats: Dict[str, torch.Tensor], a_ui, a_iu, cfg: Config):
+def forward(params: Dict[str, torch.Tensor], feats: Dict[str, torch.Tensor], a_ui, a_iu, cfg: Config, drop=None):
     """params: image_trans.{weight,bias}, text_trans.*, user_trans.*, item_trans.*,
     user_id_embedding.weight, item_id_embedding.weight.  feats: image, text, user, attr/<key>.
+    drop: None, or {feature name: callable} - the dropout of Models.py:145-150 on that feature's projection
+    (the caller supplies the masks; the returned P_usr is then the dropped tensor).
     Returns a dict with the tensors of the reference's 14-tuple (Models.py:199)."""
     spmm = torch.sparse.mm
-    lin = lambda x, name: F.linear(x, params[name + ".weight"], params[name + ".bias"])  # Models.py:145-150
-    p_img = lin(feats["image"], "image_trans")
-    p_txt = lin(feats["text"], "text_trans")
-    p_usr = lin(feats["user"], "user_trans")
-    p_att = {k: lin(feats["attr/" + k], "item_trans") for k in cfg.keys}          # ONE shared item_trans
+    dropped = (lambda y, feat: y) if drop is None else (lambda y, feat: drop[feat](y))
+    lin = lambda x, name, feat: dropped(F.linear(x, params[name + ".weight"], params[name + ".bias"]), feat)  # Models.py:145-150
+    p_img = lin(feats["image"], "image_trans", "image")
+    p_txt = lin(feats["text"], "text_trans", "text")
+    p_usr = lin(feats["user"], "user_trans", "user")
+    p_att = {k: lin(feats["attr/" + k], "item_trans", "attr/" + k) for k in cfg.keys}   # ONE shared item_trans
 
     img_u = spmm(a_ui, p_img); img_i = spmm(a_iu, img_u)                          # Models.py:153-154
     txt_u = spmm(a_ui, p_txt); txt_i = spmm(a_iu, txt_u)                          # Models.py:156-157

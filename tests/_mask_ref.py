@@ -17,6 +17,8 @@ BOUNDS (u = 2^-24 for fp32, 2^-53 for fp64), each derived from the kernel's own 
                  by mag, and each operation rounds once: error <= adds x u x mag to first order; adds x u < 2^-30 here, so the second
                  order is below 2^-30 of the bound, covered by counting N for N - 1.) The fp32 mean adds nothing: the sum follows the
                  rounded value it stores. RunningBound keeps both numbers.
+  stored mean    fp32(fp64(sum / N)) of a running sum within its bound b of the exact one: |stored - exact mean| <= b / N +
+                 (2^-24 + 2 x 2^-53)(|exact mean| + b / N) - the sum's error, the quotient's rounding, the store's (stored_mean_bound).
   restoration    exact fp32 MFMA chains (v_mfma_f32_16x16x4_f32 = an fma chain, one rounding per product: dense.hip / _dense_ref.py):
                  an fma chain of n terms started from 0 has |error| <= n u sum|a_i b_i| to first order. Err below carries (value, absolute
                  error bound) through the kernel's formulas: + - * propagate both operands' bounds INCLUDING the second-order product
@@ -90,6 +92,13 @@ class RunningBound:
 
     def bound(self):
         return self.adds * U64 * self.mag
+
+    def stored_mean_bound(self, N, mean):
+        """|stored fp32 mean - mean| per column for the round that reads the sums as they stand (call it BEFORE round()); mean = the exact
+        column mean of the tensor. The stored value is fp32(fp64(sum / N)) of a running sum within bound() of the exact one: the sum's
+        error over N, then one fp64 rounding (the quotient) and one fp32 rounding (the store) of a value of at most |mean| + bound() / N."""
+        e = self.bound() / N
+        return e + (U32 + 2.0 * U64) * (np.abs(np.asarray(mean, dtype=np.float64)) + e)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

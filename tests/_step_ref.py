@@ -13,6 +13,12 @@ oracle_step(params, feats, R, batch, cfg, dtype)
   identical data, only the arithmetic differs. Returns float64 numpy arrays: fwd {name: [rows, d]} (the tensors of the 14-tuple,
   att_u/<key> and att_i/<key> included), bpr [8, 2] (mf, emb), loss, grad {name}, maxi [8][B] (the per-sample log-sigmoids the prune
   selection orders) and keep (the number of samples the prune keeps).
+  THE OPT-IN MODES (tests/test_gpu_step_rows_modes.py). drop=Dropout(...): the projections times tests/_dropout_ref.keep_mask's masks and
+  the fp32 quotient _dropout_ref.scale(p), in Models.forward's layout; P_usr is the dropped tensor. restore=Restoration(...): the
+  attribute-restoration term of main.py:258-273 with autograd (the user stream detached, the decoder's weights constants), returned as
+  re_vals - the 1 + len(keys) stream losses - and inside loss. Masking is NOT restated: the oracle is handed the device's own feature
+  tensors as they stand after the step's masking round, bit copies - the principle of restarting from the device's own parameters; the
+  round itself is checked on its own. Both default to None, which changes nothing.
 
 row_check(got, want64, ref32, M)
   s_r = max_c |want64[r, c]|. A row with s_r == 0 must be exactly zero in got (-0.0 is zero). Else err_r(X) = max_c |X - want64| / s_r,
@@ -92,14 +98,118 @@ def bpr_tables(fw, keys):
     return [(fw["E_u"], fw["E_i"]), (fw["img_u"], fw["img_i"]), (fw["txt_u"], fw["txt_i"])] + [(fw["prof_u"], fw["att_i"][k]) for k in keys]
 
 
-def oracle_step(params, feats, R, batch, cfg: O.Config, dtype):
+class _MaskMul(torch.autograd.Function):
+    """y = x * fwd, dx = dy * bwd: dropout whose backward factor can be stated apart from the forward's (they are the same tensor in a
+    correct step; tests/test_step_ref_cpu.py plants the faults of a backward that reads another one)"""
+
+    @staticmethod
+    def forward(ctx, x, fwd, bwd):
+        ctx.save_for_backward(bwd)
+        return x * fwd
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy * ctx.saved_tensors[0], None, None
+
+
+class Dropout:
+    """The fused step's dropout at device counter `step` for oracle_step(drop=): the keep masks are tests/_dropout_ref.keep_mask's, laid
+    out as Models.forward lays the projections out - image = slice 0, text = slice 1, attribute k = slice 2 + k of the [n_items, S d]
+    tensor under TAG_ITEM_STREAMS, the user profile [n_users, d] under TAG_USER_PROFILE - and the factor of a kept element is the fp32
+    quotient _dropout_ref.scale(p), widened to the oracle's dtype."""
+
+    def __init__(self, p, seed, step, n_users, n_items, d, keys):
+        self.p, self.seed, self.step, self.U, self.I, self.d, self.keys = float(p), int(seed), int(step), n_users, n_items, d, tuple(keys)
+        self._keep = {}
+
+    def slice_of(self, name):
+        return {"image": 0, "text": 1}.get(name, 2 + self.keys.index(name[5:]) if name.startswith("attr/") else None)
+
+    def keep(self, step=None):
+        """{feature name: bool [rows, d]} of the masks of counter value `step` (None: the step's own)"""
+        from tests import _dropout_ref as DR
+        step = self.step if step is None else step
+        if step not in self._keep:
+            S = 2 + len(self.keys)
+            cat = DR.keep_mask(self.I, S * self.d, self.p, self.seed, step, DR.TAG_ITEM_STREAMS)
+            out = {"user": DR.keep_mask(self.U, self.d, self.p, self.seed, step, DR.TAG_USER_PROFILE)}
+            for name in ("image", "text") + tuple("attr/" + k for k in self.keys):
+                s = self.slice_of(name)
+                out[name] = cat[:, s * self.d:(s + 1) * self.d]
+            self._keep[step] = out
+        return self._keep[step]
+
+    def factors(self, dtype, backward=False):
+        """{feature name: [rows, d] tensor of `dtype`}: scale where kept, 0 where dropped"""
+        from tests import _dropout_ref as DR
+        scale = torch.tensor(float(DR.scale(self.p)), dtype=torch.float32).to(dtype)
+        return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dtype) * scale for k, v in self.keep().items()}
+
+    def hooks(self, dtype):
+        fwd, bwd = self.factors(dtype), self.factors(dtype, backward=True)
+        return {k: (lambda x, k=k: _MaskMul.apply(x, fwd[k], bwd[k])) for k in fwd}
+
+
+class Restoration:
+    """The attribute-restoration term of main.py:258-273 for oracle_step(restore=), in the oracle's dtype with autograd:
+    rate * (crit(u_net(prof_u[u_nodes].detach()), user_targets[u_nodes]) + sum_k crit(i_net(att_i[k][i_nodes]), item_targets[k][i_nodes])).
+    crit(x, y, alpha): main.Trainer.sce_criterion / mse_criterion; decoder = {"u": (W, b), "i": (W, b), "slope": s} - the weights of
+    Models.Decoder's two Linears as constants and the negative slope of its LeakyReLU as the drop-in constructs it; the targets are
+    the UNMASKED embeddings, fp32 numbers widened like every other input."""
+
+    def __init__(self, u_nodes, i_nodes, decoder, user_targets, item_targets, rate, crit, alpha):
+        self.u_nodes, self.i_nodes = (torch.as_tensor(np.asarray(t), dtype=torch.long) for t in (u_nodes, i_nodes))
+        f32 = lambda x: torch.as_tensor(np.asarray(x)).detach().float()
+        self.net = {s: (f32(decoder[s][0]), f32(decoder[s][1])) for s in ("u", "i")}
+        self.slope = float(decoder["slope"])
+        self.user_targets, self.item_targets = f32(user_targets), {k: f32(v) for k, v in item_targets.items()}
+        self.rate, self.crit, self.alpha = float(rate), crit, alpha
+
+    def decode(self, side, x):
+        W, b = (t.to(x.dtype) for t in self.net[side])
+        return F.leaky_relu(F.linear(x, W, b), self.slope)
+
+    def user_rows(self, prof_u):
+        return prof_u[self.u_nodes].detach()                  # the reference wraps it in torch.tensor(...): no gradient
+
+    def item_rows(self, att, key):
+        return att[self.i_nodes]
+
+    def streams(self, fw, keys):
+        """the 1 + len(keys) stream losses (tensors): user, then the attributes in the keys' order"""
+        dt = fw["prof_u"].dtype
+        out = [self.crit(self.decode("u", self.user_rows(fw["prof_u"])), self.user_targets[self.u_nodes].to(dt), alpha=self.alpha)]
+        for k in keys:
+            out.append(self.crit(self.decode("i", self.item_rows(fw["att_i"][k], k)), self.item_targets[k][self.i_nodes].to(dt), alpha=self.alpha))
+        return out
+
+    def term(self, fw, keys):
+        """(the term that joins the loss, the stream losses)"""
+        vals = self.streams(fw, keys)
+        total = vals[0]
+        for v in vals[1:]:
+            total = total + v
+        return self.rate * total, vals
+
+
+def oracle_step(params, feats, R, batch, cfg: O.Config, dtype, drop: Optional[Dropout] = None, restore: Optional[Restoration] = None):
+    """drop / restore: the two opt-in modes (None: the default step, unchanged). With drop the forward's projections are dropped and
+    fwd["P_usr"] is the dropped tensor; with restore the result gains "re_vals" (the 1 + len(keys) stream losses) and `loss` includes
+    the term. Masking itself is not restated here: `feats` are the feature tensors as they stand after the step's masking round."""
     g = R if isinstance(R, Graphs) else Graphs(R)
     a_ui, a_iu = g.get(dtype)
     p = {k: torch.as_tensor(params[k]).detach().float().to(dtype).clone().requires_grad_(True) for k in PARAMS}
     f = {k: torch.as_tensor(v).float().to(dtype) for k, v in feats.items()}
     users, pos, neg = (torch.as_tensor(np.asarray(t), dtype=torch.long) for t in batch)
-    fw = O.forward(p, f, a_ui, a_iu, cfg)
+    if drop is None:
+        fw = O.forward(p, f, a_ui, a_iu, cfg)
+    else:
+        fw = O.forward(p, f, a_ui, a_iu, cfg, drop=drop.hooks(dtype))
     loss, parts = O.step_loss(fw, users, pos, neg, g.R.shape[1], cfg)
+    re_vals = None
+    if restore is not None:
+        term, re_vals = restore.term(fw, cfg.keys)
+        loss = loss + term
     grads = torch.autograd.grad(loss, [p[k] for k in PARAMS])
     n64 = lambda t: t.detach().to(torch.float64).numpy()
     fwd = {k: n64(fw[k]) for k in FWD}
@@ -109,8 +219,11 @@ def oracle_step(params, feats, R, batch, cfg: O.Config, dtype):
     with torch.no_grad():
         for tu, ti in bpr_tables(fw, cfg.keys):
             maxi.append(n64(F.logsigmoid((tu[users] * ti[pos]).sum(1) - (tu[users] * ti[neg]).sum(1) + 1e-8)))
-    return {"fwd": fwd, "bpr": np.array([[float(a.detach()), float(b.detach())] for a, b in parts["bpr"]], dtype=np.float64), "loss": float(loss.detach()),
-            "grad": {k: n64(t) for k, t in zip(PARAMS, grads)}, "maxi": maxi, "keep": int((1 - cfg.prune_loss_drop_rate) * len(users))}
+    out = {"fwd": fwd, "bpr": np.array([[float(a.detach()), float(b.detach())] for a, b in parts["bpr"]], dtype=np.float64), "loss": float(loss.detach()),
+           "grad": {k: n64(t) for k, t in zip(PARAMS, grads)}, "maxi": maxi, "keep": int((1 - cfg.prune_loss_drop_rate) * len(users))}
+    if re_vals is not None:
+        out["re_vals"] = np.array([float(v.detach()) for v in re_vals], dtype=np.float64)
+    return out
 
 
 def kept_sets(maxi, keep):
@@ -256,12 +369,19 @@ def compare_step(got, r64, r32, M: Optional[Dict[str, float]], prov: Optional[Pr
     ratios["loss"] = ratio
     if not ok:
         fails.append("loss: ratio %.3g (got %r, fp64 %r, fp32 %r)" % (ratio, float(got["loss"]), r64["loss"], r32["loss"]))
+    if "re_vals" in r64:                                                          # the restoration's stream losses: scalars like the others
+        assert len(got["re_vals"]) == len(r64["re_vals"]) == len(r32["re_vals"])
+        for j in range(len(r64["re_vals"])):
+            ok, ratio = scalar_check(got["re_vals"][j], r64["re_vals"][j], r32["re_vals"][j], m_of("scalar"), "restore%d" % j)
+            ratios["restore%d" % j] = ratio
+            if not ok:
+                fails.append("restore%d: ratio %.3g (got %r, fp64 %r, fp32 %r)" % (j, ratio, float(got["re_vals"][j]), r64["re_vals"][j], r32["re_vals"][j]))
     return fails, ratios
 
 
 def family_of_key(key: str) -> str:
     """the margin family of one of compare_step's ratio keys"""
-    if key == "loss" or key.startswith("bpr"):
+    if key == "loss" or key.startswith(("bpr", "restore")):
         return "scalar"
     return family(key.split("/", 1)[1])
 
@@ -315,6 +435,56 @@ CASE_B = dict(dataset="preprocessed_raw_MovieLens", n_users=3000, n_items=800, n
               argv=["--batch_size", "512", "--seed", "2022", "--debug", "--lr", "0.001", "--weight_size", "[64, 64, 64]",
                     "--embed_size", "64", "--epoch", "1"], batch_seed=3, n_distinct=400, n_repeat=8, pool_chunks=16)
 CASE_C = dict(CASE_B, argv=["--batch_size", "4608"] + CASE_B["argv"][2:], batch_seed=1, n_triples=4608, copies=8, pool_chunks=10)
+# The opt-in modes (tests/test_gpu_step_rows_modes.py), all on B's dataset, schedule and batch structure. The forward differs per step
+# here - a new dropout mask, or feature rows masked since the last step - so island_batches chooses every step's triples from the fp64
+# forward under THAT step's masks or features (mode_forwards).
+#   D  --drop_rate 0.3: the fp32 quotient 1 / (1 - p) is inexact (at the parity test's 0.5 it is 2).
+#   K  --mask True --mask_rate 0.25 --att_re_rate 0.5: 750 user and 200 item nodes per round, about three quarters of them in blocks the
+#      batch never reaches; K_MSE: the same under --feat_loss_type mse. eval_before: one evaluation - one masking round - precedes that
+#      step, so the round counter leaves the step index (rounds 0, 1, 3).
+#   U  --mask_rate 0.25 alone (user features only; the step keeps the schedule it has without the flag). ON B'S SHAPE, not A's hosted
+#      one: A's batches are the device sampler's, and its cut-gap condition holds for about one --seed in three thousand (above). With
+#      masking the seed also fixes the lists, so 6375 does not carry over, and a new search means several thousand seeds times three
+#      fp64 and three fp32 oracle steps at 9000 x 1000 each - hours on the CPU, where B's chosen triples meet the condition by construction.
+CASE_D = dict(CASE_B, argv=CASE_B["argv"] + ["--drop_rate", "0.3"], mode="drop")
+CASE_K = dict(CASE_B, argv=CASE_B["argv"] + ["--mask", "True", "--mask_rate", "0.25", "--att_re_rate", "0.5"], mode="mask", eval_before=2,
+              pool_chunks=64)          # (masked users and items score alike in the profile problems: fewer candidates clear the band)
+CASE_K_MSE = dict(CASE_K, argv=CASE_K["argv"] + ["--feat_loss_type", "mse"])
+CASE_U = dict(CASE_B, argv=CASE_B["argv"] + ["--mask_rate", "0.25"], mode="mask", eval_before=2, pool_chunks=64)
+
+
+def mask_rounds(case):
+    """The masking round of each of the STEPS steps: the step index, plus one from the step an evaluation precedes"""
+    e = case.get("eval_before")
+    return [s + (1 if e is not None and s >= e else 0) for s in range(STEPS)]
+
+
+def masked_features(feats, keys, seed, m_users, m_items, n_rounds):
+    """The feature tensors after each of the rounds 0 .. n_rounds - 1 (tests/_mask_ref.mask_round from from-scratch column sums; rounds
+    are cumulative and a function of (seed, round) alone, so they are known before any step runs) -> per round (feats, u_nodes, i_nodes).
+    m_items = 0: user features only."""
+    from tests import _mask_ref as MR
+    cur = {k: np.asarray(v, dtype=np.float32).copy() for k, v in feats.items()}
+    masked = ["user"] + (["attr/" + k for k in keys] if m_items else [])
+    sums = {k: MR.col_sums(cur[k]) for k in masked}
+    out = []
+    for rnd in range(n_rounds):
+        u_nodes = MR.nodes(cur["user"].shape[0], m_users, seed, rnd, MR.SIDE_USERS)
+        i_nodes = MR.nodes(cur["image"].shape[0], m_items, seed, rnd, MR.SIDE_ITEMS) if m_items else np.zeros(0, dtype=np.int64)
+        for k in masked:
+            cur[k], sums[k], _ = MR.mask_round(cur[k], sums[k], u_nodes if k == "user" else i_nodes)
+        out.append(({k: torch.from_numpy(v.copy()) for k, v in cur.items()}, u_nodes, i_nodes))
+    return out
+
+
+def mode_forwards(case, data, cfg, args):
+    """island_batches' per_step of a mode case: step -> (the feature tensors, the Dropout) the step's forward runs under"""
+    n_u, n_i = data.n_users, data.n_items
+    if case["mode"] == "drop":
+        return lambda s: (data.feats, Dropout(args.drop_rate, args.seed, s, n_u, n_i, cfg.embed_size, cfg.keys))
+    rounds = mask_rounds(case)
+    after = masked_features(data.feats, cfg.keys, args.seed, int(args.mask_rate * n_u), int(args.mask_rate * n_i) if args.mask else 0, rounds[-1] + 1)
+    return lambda s: (after[rounds[s]][0], None)
 
 
 def write_case(case, root):
@@ -386,8 +556,16 @@ def sampled_batch(data, exist_users, seed, batch_size, aug_rate, step):
 BAND = 0.1                       # a triple qualifies when |x_p| > BAND std(x_p) in every problem p
 
 
-def island_batches(case, data, graphs, cfg, params0):
-    """The injected batches of the STEPS steps of cases B and C: every user from block 0 (u % C == 0), every item from that block's
+def island_batches(case, data, graphs, cfg, params0, per_step=None, only=None):
+    """per_step (the mode cases: mode_forwards): step -> (feats, Dropout or None); a step's candidates are then judged in the fp64
+    forward under THAT step's features and masks, with a candidate pool of its own. only = s: the batch of step s alone, as a list of
+    one, from the parameters given - the step's own pre-step parameters (the generator is then seeded with (batch_seed, s)). The mode
+    cases need that: in case K triples chosen from the initial parameters had lost the empty stretch at the cut by the third step
+    (an exact tie across one problem's cut, gap 0, where B keeps 6 x the requirement; supposed cause: the restoration term pulls
+    every entry of item_trans the same way step after step). The masks and lists are functions of
+    (seed, round) alone, so the forward a step will run is known before it runs. per_step = None: one forward and one pool for all
+    steps, as cases B and C have always drawn them (the generator's draws are in the same order).
+    The injected batches of the STEPS steps of cases B and C: every user from block 0 (u % C == 0), every item from that block's
     island. B: n_distinct users once each and user[0] n_repeat + 1 >= 8 times; an item that is the positive of one triple and the
     negative of another (asserted); no two triples identical; fewer triples than the step's capacity. C: n_triples / copies distinct
     triples, each `copies` times, shuffled - copies divides both n_triples and the number of samples the prune keeps, so the ties
@@ -403,21 +581,33 @@ def island_batches(case, data, graphs, cfg, params0):
     import scipy.sparse as sp
     R = sp.csr_matrix(data.train_mat)
     C = case["n_communities"]
-    rng = np.random.default_rng(case["batch_seed"])
+    assert only is None or per_step is not None
+    rng = np.random.default_rng(case["batch_seed"] if only is None else [case["batch_seed"], only])
     block_users = np.flatnonzero((np.arange(R.shape[0]) % C == 0) & (R.getnnz(1) > 0))
     block_items = np.unique(R[block_users].indices)
     a_ui, a_iu = graphs.get(torch.float64)
-    with torch.no_grad():
-        fw = O.forward({k: torch.as_tensor(params0[k]).detach().double() for k in PARAMS}, {k: v.double() for k, v in data.feats.items()},
-                       a_ui, a_iu, cfg)
-        tabs = [(tu.numpy(), ti.numpy()) for tu, ti in bpr_tables(fw, cfg.keys)]
+    tabs = []
+
+    def forward_tables(feats, drop):
+        with torch.no_grad():
+            fw = O.forward({k: torch.as_tensor(params0[k]).detach().double() for k in PARAMS}, {k: v.double() for k, v in feats.items()},
+                           a_ui, a_iu, cfg, **({} if drop is None else {"drop": drop.hooks(torch.float64)}))
+            tabs[:] = [(tu.numpy(), ti.numpy()) for tu, ti in bpr_tables(fw, cfg.keys)]
+        if per_step is not None:                                                  # the block's score matrices: a candidate costs two look-ups
+            tabs[:] = [tu[block_users] @ ti[block_items].T for tu, ti in tabs]
+
+    u_at, i_at = np.zeros(R.shape[0], dtype=np.int64), np.zeros(R.shape[1], dtype=np.int64)
+    u_at[block_users], i_at[block_items] = np.arange(len(block_users)), np.arange(len(block_items))
 
     def signs(u, a, b):
         """+1 / -1 / 0 per candidate: easy / hard / unused"""
         lo = np.ones(len(u), dtype=bool)
         hi = np.ones(len(u), dtype=bool)
-        for tu, ti in tabs:
-            x = np.einsum("nd,nd->n", tu[u], ti[a] - ti[b])
+        for tab in tabs:
+            if per_step is not None:
+                x = tab[u_at[u], i_at[a]] - tab[u_at[u], i_at[b]]
+            else:
+                x = np.einsum("nd,nd->n", tab[0][u], tab[1][a] - tab[1][b])
             band = BAND * x.std()
             lo &= x < -band
             hi &= x > band
@@ -427,20 +617,30 @@ def island_batches(case, data, graphs, cfg, params0):
     ga, gb = np.meshgrid(block_items, block_items, indexing="ij")
     sa, sb = ga.reshape(-1), gb.reshape(-1)
     sa, sb = sa[sa != sb], sb[sa != sb]
-    s_star = signs(np.full(len(sa), star), sa, sb)
-    pool = {1: [], -1: []}
     others = block_users[1:]
-    for _ in range(case.get("pool_chunks", 6)):                                   # random candidates of the other users, in chunks
-        u = rng.choice(others, size=40000)
-        a, b = rng.choice(block_items, size=u.size), rng.choice(block_items, size=u.size)
-        sg = signs(u, a, b) * (a != b)
-        for sign in (1, -1):
-            pool[sign].append(np.stack([u, a, b], axis=1)[sg == sign])
-    pool = {k: np.unique(np.concatenate(v), axis=0) for k, v in pool.items()}
-    star_pool = {k: np.stack([np.full(int((s_star == k).sum()), star), sa[s_star == k], sb[s_star == k]], axis=1) for k in (1, -1)}
+
+    def pools():
+        """(pool, star_pool): {+1 / -1: [n, 3] triples} of the other users' random candidates and of every pair of the repeated user"""
+        s_star = signs(np.full(len(sa), star), sa, sb)
+        pool = {1: [], -1: []}
+        for _ in range(case.get("pool_chunks", 6)):                               # random candidates of the other users, in chunks
+            u = rng.choice(others, size=40000)
+            a, b = rng.choice(block_items, size=u.size), rng.choice(block_items, size=u.size)
+            sg = signs(u, a, b) * (a != b)
+            for sign in (1, -1):
+                pool[sign].append(np.stack([u, a, b], axis=1)[sg == sign])
+        pool = {k: np.unique(np.concatenate(v), axis=0) for k, v in pool.items()}
+        return pool, {k: np.stack([np.full(int((s_star == k).sum()), star), sa[s_star == k], sb[s_star == k]], axis=1) for k in (1, -1)}
+
+    if per_step is None:
+        forward_tables(data.feats, None)
+        pool, star_pool = pools()
     n = case.get("n_triples")
     out = []
-    for step in range(STEPS):
+    for step in (range(STEPS) if only is None else [only]):
+        if per_step is not None:
+            forward_tables(*per_step(step))
+            pool, star_pool = pools()
         if n is None:                                                             # B
             total = case["n_distinct"] + case["n_repeat"]
             keep = int((1 - cfg.prune_loss_drop_rate) * total)
@@ -491,4 +691,29 @@ def relabel(params, feats, R, batch, seed):
         out["fwd"] = {k: v[nu if side_of(k) == "u" else ni] for k, v in res["fwd"].items()}
         out["grad"] = {k: (v if side_of(k) is None else v[nu if side_of(k) == "u" else ni]) for k, v in res["grad"].items()}
         return out
+    back.ou, back.oi, back.nu, back.ni = ou, oi, nu, ni              # for what else names rows: relabel_modes
     return p2, f2, R[ou][:, oi].tocsr(), b2, back
+
+
+def relabel_modes(back, drop=None, restore=None):
+    """(drop, restore) of the problem relabel() renamed: the same masks on the renamed rows, the same nodes under their new names"""
+    d2 = r2 = None
+    if drop is not None:
+        d2 = Dropout(drop.p, drop.seed, drop.step, drop.U, drop.I, drop.d, drop.keys)
+        d2.keep = lambda step=None: {k: v[back.ou if k == "user" else back.oi] for k, v in drop.keep(step).items()}
+    if restore is not None:
+        r2 = Restoration(back.nu[restore.u_nodes.numpy()], back.ni[restore.i_nodes.numpy()], dict(restore.net, slope=restore.slope),
+                         restore.user_targets[back.ou], {k: v[back.oi] for k, v in restore.item_targets.items()}, restore.rate, restore.crit,
+                         restore.alpha)
+    return d2, r2
+
+
+def restoration_of(m, tr, keys, u_nodes, i_nodes):
+    """The Restoration of the drop-in module m's Trainer tr at its flags, for the round's node lists"""
+    a = m.args
+    crit = m.Trainer.mse_criterion if a.feat_loss_type == "mse" else m.Trainer.sce_criterion      # (neither reads self)
+    u_net, i_net = tr.decoder.u_net, tr.decoder.i_net
+    assert float(u_net[1].negative_slope) == float(i_net[1].negative_slope)
+    w = lambda lin: (lin.weight.detach().cpu(), lin.bias.detach().cpu())
+    return Restoration(u_nodes, i_nodes, {"u": w(u_net[0]), "i": w(i_net[0]), "slope": float(u_net[1].negative_slope)}, tr.user_init_embedding,
+                       {k: tr.item_attribute_embedding[k] for k in keys}, a.att_re_rate, lambda x, y, alpha: crit(None, x, y, alpha=alpha), a.alpha_l)

@@ -9,7 +9,12 @@ Measured on an MI355X. test_fused_step_matches_autograd_with_the_same_lists (nf_
 against the bound 1e-4: eager sce 7.3e-7 (step 1, text_trans.bias' gradient), graph sce 7.3e-7 (the same), f32 sce 1.1e-6 (step 0,
 item_id_embedding.weight's gradient), eager mse 6.5e-7, four streams 7.3e-7; the top-20 scores within 2.4e-7 on all five; user masking alone 5.5e-7. The running sums came out equal
 to the restated tree bit for bit. test_restoration_value_and_gradient_within_the_bound: worst error / bound 0.99 - the update of a
-non-zero destination row ends in one rounding, whose bound u |result| is tight by nature."""
+non-zero destination row ends in one rounding, whose bound u |result| is tight by nature.
+
+The whole-step tests here measure max |a - b| / max |b| per tensor against the project's own per-op path on a 96 x 80 graph, where almost
+no mask node lies outside the batch's reach. The ROW-LEVEL statement - every forward and gradient row and the restoration's stream losses
+against a float64 oracle, every masking round on its own, sc_I all-zero after every step, on a four-island 3000 x 800 graph with 70 % of
+the item list beyond the batch's reach - is tests/test_gpu_step_rows_modes.py, cases K, K_MSE and U."""
 import numpy as np
 import pytest
 import torch
