@@ -1133,6 +1133,31 @@ int llmrec_restore_finish_f32(int32_t n_values, const float* values, float rate,
                               float* const* views_host, int64_t ld, int32_t cols, const int64_t* nodes, int64_t m, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Checkpoint snapshot (csrc/snapshot.hip): n byte ranges ("segments") of device memory and ONE arena, moved by ONE launch whose
+ * table of segments travels by value (no device-side table, no host synchronisation; capturable). Additive: the ABI version stays.
+ *   llmrec_pack_arena_bytes  host arithmetic only, no device: offsets_host[i] = the offset of segment i in an arena that holds the
+ *               segments in the given order, each at a multiple of LLMREC_PACK_ALIGN; returns the arena's size (a multiple of
+ *               LLMREC_PACK_ALIGN; 0 for n == 0). Any n >= 0 (a caller with more than LLMREC_PACK_MAX_SEGMENTS segments lays out one
+ *               arena and issues several launches over consecutive slices of it). -1: n < 0, a null array with n > 0, a negative
+ *               size, a total beyond 2^63.
+ *   llmrec_pack_segments   direction 0 (pack):   arena[offset[i] .. + bytes[i]) = ptr[i][0 .. bytes[i]) for every i, and EVERY other
+ *                                                byte of arena[0 .. arena_bytes) = 0: equal states give byte-equal arenas;
+ *                          direction 1 (unpack): ptr[i][0 .. bytes[i]) = arena[offset[i] .. + bytes[i]); nothing else is written.
+ *               ptr_host / bytes_host / offset_host are HOST arrays read during the call; ptr[i] may have any alignment (16-byte
+ *               aligned: 16 bytes per lane; 4-byte aligned: 4; else single bytes on the tensor side), all offsets are 64-bit.
+ *               n == 0 with direction 0 zero-fills the arena.
+ * LLMREC_EINVAL before any HIP call, nothing written: n outside [0, LLMREC_PACK_MAX_SEGMENTS]; a direction other than 0 or 1; a null
+ * host array with n > 0; a null pointer with non-zero bytes; a negative size; an offset that is negative or not a multiple of
+ * LLMREC_PACK_ALIGN; a segment that passes arena_bytes; arena_bytes < 0, a null arena with arena_bytes > 0 or an arena that is not
+ * 16-byte aligned; direction 0 with two segments that overlap in the arena.
+ * ------------------------------------------------------------------------------------------ */
+#define LLMREC_PACK_MAX_SEGMENTS 64
+#define LLMREC_PACK_ALIGN 256
+int64_t llmrec_pack_arena_bytes(int32_t n, const int64_t* bytes_host, int64_t* offsets_host);
+int llmrec_pack_segments(int32_t n, const void* const* ptr_host, const int64_t* bytes_host, const int64_t* offset_host,
+                         void* arena, int64_t arena_bytes, int32_t direction, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline`; nothing on the product path calls it). One single-lane launch that
  * stores the device's constant-rate real-time counter (s_memrealtime) into *slot when the stream reaches it.
  * A captured HIP graph cannot carry event-record nodes for external events; a pair of these around a launch

@@ -113,6 +113,11 @@ class DeviceBatcher:
         return ops.guest_sampler(self.seed, self.step_dev, self.exist_users, self.n_items, self.train, self.B, 0, self.B, self.n_aug,
                                  self.aug_pos, self.aug_neg, users, pos, neg, n_valid, self.ticket)
 
+    def state_tensors(self):
+        """[(name, tensor)] of the sampler's device state between steps: the step counter. (The ticket is back at 0 behind every
+        launch; everything else is a constant of the run.)"""
+        return [("sampler/step_dev", self.step_dev)]
+
     def next(self, step: Optional[int] = None):
         """(users, pos, neg, n_valid) in fresh buffers; step = None continues the device counter."""
         dev = self.exist_users.device
@@ -130,3 +135,9 @@ def evaluate_topk(model, ui, iu, query_users: torch.Tensor, train: ops.Csr, k: i
     model.eval()
     fw = model(ui, iu, ui, iu, ui, iu)
     return ops.score_topk(fw[0], fw[1], query_users, train, k)
+
+
+def model_state_tensors(model, optimizer):
+    """[(name, tensor)] of a model's trained state on either path: every parameter in named_parameters() order, then the
+    optimiser's own list (FusedAdamW.state_tensors)."""
+    return [("param/" + name, p.data) for name, p in model.named_parameters()] + optimizer.state_tensors()

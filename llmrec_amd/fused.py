@@ -1224,12 +1224,15 @@ class FusedStep:
             raise
         return self.scal[1], self.scal[2], self.scal[3]
 
-    def _size_wgrad_for_rows(self):
+    def _size_wgrad_for_rows(self, expected: Optional[int] = None):
         """Lay the weight-gradient launch out for the list length the last step saw (+ 10 %): the kernel cuts a listed problem's slabs
         into equal pieces of the ACTUAL length every step, this only decides how many blocks each target gets. One host read-back;
-        the workspace is re-sized here (outside any capture)."""
-        n = int(self.act_n.item())
-        self.act_expected = max(64, min(self.U, int(n * 1.10) + 32))
+        the workspace is re-sized here (outside any capture). expected: the layout itself (finish_load: a saved run's), no read-back."""
+        if expected is not None:
+            self.act_expected = expected
+        else:
+            n = int(self.act_n.item())
+            self.act_expected = max(64, min(self.U, int(n * 1.10) + 32))
         need = ops.linear_wgrad_multi_workspace(self.wgrad_targets(self.dU_cat if self.preprop else self.dP_cat, self.dP_usr), self.wgrad_blocks)
         self.ws_wgrad_multi = torch.empty(max(need, 0), dtype=torch.uint8, device=self.dP_usr.device) if need >= 0 else False
 
@@ -1252,6 +1255,97 @@ class FusedStep:
 
     def flush(self):
         """Nothing is deferred in the single-graph step (DataParallelStep defers its AdamW)."""
+
+    # -- state (checkpoints) ----------------------------------------------------------------------
+    def state_tensors(self):
+        """[(name, tensor)] of EVERYTHING this step carries in device memory from one step boundary to the next; a checkpoint is these
+        bytes (llmrec_amd/checkpoint.py knows no more). A new piece of device state = one more line here.
+          param/*, adamw/*   every parameter of the model in named_parameters() order, AdamW's counter and both moments of each
+                    (engine.model_state_tensors);
+          row_stamp, flag_u, flag_i   the stamp counter and the rows' stamps. All three, so that a loaded state EQUALS the saved one: stale
+                    stamps that meet a rewound counter would make the fusion backward skip, or read, the wrong rows;
+          epoch_sums   the running sums of the logged scalars;
+          drop_step, drop_ticket   (drop_rate > 0) the dropout masks' counter and its count-off;
+          mask_step, mask_ticket, user_sums/*, item_sums/*   (mask_rate > 0) the masking round's counter, its count-off and the running
+                    fp64 column sums. The masked feature matrices themselves are NOT here: prepare_load() replays the rounds;
+          decoder/*   (the restoration term) the decoder's parameters: never stepped, but a resumed run must not depend on the order of
+                    initialisation.
+        NOT state, by design:
+          dE_u, dE_i, sc_U, sc_I, sc_prof, act_flags   the scatter targets and the reach flags are all-zero at every step boundary (the
+                    invariant LLMREC_CHECK_ZERO asserts), in the saved run and in the loading one;
+          .grad, saved, bpr_plan, out, scal, the forward / backward buffers, the node lists, the workspaces and partial sums   are
+                    rewritten by every step before anything reads them;
+          AX, a_rowsum, the targets, the adjacency   the pre-propagated operands are constants of the run, formed at set-up.
+        The sampler's counter belongs to the batcher (engine.DeviceBatcher.state_tensors), which the caller lists beside this step."""
+        from .engine import model_state_tensors
+        out = model_state_tensors(self.m, self.opt)
+        out += [("step/row_stamp", self.row_stamp), ("step/flag_u", self.flag_u), ("step/flag_i", self.flag_i), ("step/epoch_sums", self.epoch_sums)]
+        if self.drop_rate > 0:
+            out += [("step/drop_step", self.drop_step), ("step/drop_ticket", self.drop_ticket)]
+        if self.mask_rate > 0:
+            out += [("step/mask_step", self.mask_step), ("step/mask_ticket", self.mask_ticket)]
+            out += [("step/user_sums/%d" % k, t) for k, t in enumerate(self.user_sums)]
+            out += [("step/item_sums/%d" % k, t) for k, t in enumerate(self.item_sums)]
+        if self.restore:
+            out += [("decoder/" + name, p.data) for name, p in self.decoder.named_parameters()]
+        return out
+
+    def host_state(self):
+        """What the step keeps on the HOST across steps and a resumed run must share: the list length the weight-gradient launch is
+        laid out for (frozen at the first step, re-laid by check_wgrad_geometry) - it fixes that launch's summation partition."""
+        return {"act_expected": self.act_expected if self.wgrad_rows else None}
+
+    replayed_mask_rounds = None     # (rounds, seconds) of the last prepare_load()'s replay
+
+    def prepare_load(self, saved):
+        """Ahead of a load: saved(name) is the saved tensor of that name (a device tensor; None: not in the checkpoint). Only a masking
+        step has work here. Its feature matrices are not in the checkpoint (0.5 GB at the Netflix shape): the lists are a function of
+        (seed, round, side), the values of the running fp64 sums, and the kernels are deterministic, so a FRESH step (mask_step == 0,
+        features as read, sums from refresh_feature_sums()) replays _mask_round() saved-mask_step times and must then hold the saved
+        mask_step and sums bit for bit. A step that has already masked raises: there is no rollback in this mode."""
+        if not self.mask_rate > 0:
+            return
+        import time
+        want = saved("step/mask_step")
+        if want is None:
+            raise RuntimeError("FusedStep.prepare_load: the checkpoint holds no masking state")
+        if int(self.mask_step.view(torch.int64).item()) != 0:
+            raise RuntimeError("FusedStep.prepare_load: this step has already masked its features (mask_step != 0); a masking checkpoint "
+                               "loads into a fresh step only")
+        rounds = int(want.view(torch.int64).item())
+        t0 = time.perf_counter()
+        for _ in range(rounds):
+            self._mask_round()
+        torch.cuda.current_stream().synchronize()
+        self.replayed_mask_rounds = (rounds, time.perf_counter() - t0)
+        mine = dict(self.state_tensors())
+        bad = [name for name in mine if name.startswith(("step/mask_step", "step/user_sums/", "step/item_sums/"))
+               and not torch.equal(mine[name].view(torch.int64), saved(name).view(torch.int64))]
+        if bad:
+            raise RuntimeError("FusedStep.prepare_load: %d replayed masking rounds do not reproduce the saved %s (other features, "
+                               "another seed or mask_rate?)" % (rounds, bad))
+
+    def finish_load(self, host):
+        """Behind a load: the host half (host_state()). A different launch layout is applied now - and a captured step re-captured
+        without a warm-up step, as check_wgrad_geometry does."""
+        expected = (host or {}).get("act_expected")
+        if self.wgrad_rows and expected is not None and expected != self.act_expected:
+            self._size_wgrad_for_rows(int(expected))
+            if self.graph_exec is not None and self._capture_args is not None:
+                self.capture(warm=False, **self._capture_args)
+
+    @torch.no_grad()
+    def load_state(self, saved, host=None):
+        """Make this step's state the saved one: saved(name) -> tensor (any device). Writes INTO the existing tensors and never rebinds
+        one - a captured graph holds their addresses - so loading into a live, captured step is legal: a rollback to the saved step.
+        (llmrec_amd.checkpoint.Checkpointer moves the same bytes in one launch between prepare_load() and finish_load().)"""
+        self.prepare_load(saved)
+        for name, t in self.state_tensors():
+            src = saved(name)
+            if src is None or src.shape != t.shape or src.dtype != t.dtype:
+                raise RuntimeError("FusedStep.load_state: %s is missing from the saved state or has another shape / dtype" % name)
+            t.copy_(src)
+        self.finish_load(host)
 
     # -- evaluation -------------------------------------------------------------------------------
     def eval_topk(self, query_users: torch.Tensor, train: Optional[ops.Csr], K: int, use_graph: bool = False, held=None, Ks=None,

@@ -1207,6 +1207,35 @@ class FusedAdamW:
                 _lib.call("llmrec_adamw_multi_zero_rows_f32", len(group), arr, _p(self.dev_state), self.lr, self.betas[0], self.betas[1],
                           self.eps, self.wd, len(jobs), jarr, int(b_cap), _p(n_valid), _stream())
 
+    def state_tensors(self):
+        """[(name, tensor)] of everything the optimiser keeps on the device between steps: the step counter with its two bias
+        corrections (dev_state) and both moments of EVERY parameter, by the parameter's position - created here where they do not
+        exist yet (a checkpoint is loaded before the first step; a parameter that never gets a gradient keeps all-zero moments). A new
+        piece of device state of the optimiser is one more line here."""
+        if self.dev_state is None:
+            self.dev_state = torch.zeros(3, dtype=torch.float32, device=self.params[0].device)
+        out = [("adamw/dev_state", self.dev_state)]
+        for i, p in enumerate(self.params):
+            m, v = self.moments(p)
+            out += [("adamw/m/%d" % i, m), ("adamw/v/%d" % i, v)]
+        return out
+
+    def state_dict(self):
+        """The per-op path's form of state_tensors(): host copies by name, and the hyper-parameters the state was formed under."""
+        return {"state": {name: t.detach().cpu().clone() for name, t in self.state_tensors()},
+                "hyper": {"lr": self.lr, "betas": list(self.betas), "eps": self.eps, "weight_decay": self.wd}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """Copies a state_dict() INTO the existing tensors (never rebinds one: a captured graph holds their addresses)."""
+        mine = dict(self.state_tensors())
+        theirs = sd["state"]
+        bad = sorted(set(mine) ^ set(theirs)) + [k for k in mine if k in theirs and (mine[k].shape != theirs[k].shape or mine[k].dtype != theirs[k].dtype)]
+        if bad:
+            raise RuntimeError("FusedAdamW.load_state_dict: the state does not fit this optimiser: %s" % bad[:8])
+        for k, t in mine.items():
+            t.copy_(theirs[k])
+
     @torch.no_grad()
     def step_params_rows_group(self, params, sources, fuse_problems, d, softmax_bwd) -> bool:
         """step_params(params, sources) in ONE launch with two row sweeps that are independent of it (llmrec_step_rows_group_f32):
@@ -1562,3 +1591,52 @@ def topk_metrics(idx: torch.Tensor, hits: torch.Tensor, query_users: torch.Tenso
     _lib.call("llmrec_topk_metrics", n, _p(query_users.to(torch.int64).contiguous()), K, _p(hits.contiguous()), _p(idx.contiguous()),
               _p(test_rowptr), len(Ks), arr, _p(out), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Checkpoint snapshot: many tensors <-> one arena in one launch (csrc/snapshot.hip)
+# ---------------------------------------------------------------------------------------------
+PACK_MAX_SEGMENTS, PACK_ALIGN = CONST["LLMREC_PACK_MAX_SEGMENTS"], CONST["LLMREC_PACK_ALIGN"]
+
+
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def pack_layout(nbytes: Sequence[int]):
+    """(offsets, arena_bytes) of an arena that holds segments of these sizes in this order, each at a multiple of PACK_ALIGN
+    (llmrec_pack_arena_bytes: host arithmetic, no device)."""
+    n = len(nbytes)
+    b, o = (_c.c_int64 * max(n, 1))(*[int(x) for x in nbytes]), (_c.c_int64 * max(n, 1))()
+    total = _lib.query("llmrec_pack_arena_bytes", n, b, o)
+    if total < 0:
+        raise ValueError("pack_layout: a negative size, or a total beyond 2^63")
+    return [int(x) for x in o[:n]], total
+
+
+def pack_segments(tensors: Sequence[torch.Tensor], offsets: Sequence[int], arena: torch.Tensor, direction: int):
+    """direction 0: arena[offsets[i] ...] = the bytes of tensors[i], every other byte of the arena = 0; direction 1: the bytes of
+    tensors[i] = arena[offsets[i] ...] (llmrec_pack_segments, on the current stream; no synchronisation). The tensors are contiguous
+    device tensors of any dtype and alignment; the arena is a contiguous uint8 device tensor. One launch per PACK_MAX_SEGMENTS
+    tensors: each launch owns the slice of the arena from its first segment's offset to the next launch's (the first from 0, the last to
+    the arena's end), so the offsets of more than PACK_MAX_SEGMENTS tensors ascend (pack_layout's do). Returns the number of launches."""
+    n = len(tensors)
+    if len(offsets) != n or arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise RuntimeError("pack_segments: one offset per tensor and a contiguous uint8 arena expected")
+    _need_gpu(arena, *tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise RuntimeError("pack_segments: contiguous tensors expected")
+    if n > PACK_MAX_SEGMENTS and any(offsets[i] > offsets[i + 1] for i in range(n - 1)):
+        raise RuntimeError("pack_segments: more than %d segments need ascending offsets" % PACK_MAX_SEGMENTS)
+    total, launches = arena.numel(), 0
+    for lo in range(0, max(n, 1), PACK_MAX_SEGMENTS):
+        group = range(lo, min(lo + PACK_MAX_SEGMENTS, n))
+        base = int(offsets[lo]) if lo > 0 else 0
+        end = int(offsets[lo + PACK_MAX_SEGMENTS]) if lo + PACK_MAX_SEGMENTS < n else total
+        k = max(len(group), 1)
+        ptrs = (_c.c_void_p * k)(*[tensors[i].data_ptr() for i in group])
+        size = (_c.c_int64 * k)(*[_nbytes(tensors[i]) for i in group])
+        offs = (_c.c_int64 * k)(*[int(offsets[i]) - base for i in group])
+        _lib.call("llmrec_pack_segments", len(group), ptrs, size, offs, _c.c_void_p(arena.data_ptr() + base), end - base, int(direction), _stream())
+        launches += 1
+    return launches

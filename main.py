@@ -368,6 +368,7 @@ class Trainer(object):
                                       mask_rate=args.mask_rate, drop_rate=args.drop_rate, b_max=b_max,
                                       cap=ops.CONST["LLMREC_BPR_MAX_B"], wide_cap=ops.CONST["LLMREC_BPR_WIDE_MAX_B"],
                                       n_users=self.n_users, n_items=self.n_items)
+            self._route = path if device.type == "cuda" else "modular"   # (checkpoints record it)
             if path != "modular" and device.type == "cuda":
                 from llmrec_amd.fused import FusedStep
                 graph = type("G", (), {"ui": ops.operand_from_sparse_tensor(self.ui_graph),
@@ -460,6 +461,49 @@ class Trainer(object):
             loss = loss + crit(decoded_i[index], target, alpha=args.alpha_l)
         return args.att_re_rate * loss
 
+    # -- checkpoints (llmrec_amd/checkpoint.py; opt-in: LLMREC_CHECKPOINT / LLMREC_CHECKPOINT_EVERY / LLMREC_RESUME) -----------------
+    def _checkpointer(self):
+        """The run's Checkpointer over the owners of its device state: the fused step (parameters, AdamW, its counters and stamps), the
+        in-graph sampler where there is one, and the decoder; on the per-op path the parameters and FusedAdamW's state (its dropout is
+        covered by torch's generator state). --mask / --mask_rate > 0 on the per-op path is refused: that path rewrites the feature
+        matrices through torch.randperm every forward, and nothing here saves or replays them."""
+        if getattr(self, "_ckpt", None) is None:
+            from llmrec_amd import checkpoint, step_options
+            fused = self._fused_step()
+            if not fused and (args.mask or args.mask_rate != 0):
+                raise RuntimeError("checkpoints of --mask / --mask_rate > 0 need the fused step (LLMREC_FUSED=mask): the per-op path's "
+                                   "masked feature matrices are not part of a checkpoint")
+            in_graph_sampler = bool(self._device_sampler and USE_GRAPH() and fused)
+            listed = lambda fn: type("Listed", (), {"state_tensors": staticmethod(fn)})()
+            parts = [fused] if fused else [listed(lambda: engine.model_state_tensors(self.model_mm, self.optimizer))]
+            if in_graph_sampler:
+                parts.append(self._device_batcher())
+            if not (fused and fused.restore):                   # (a restoring step lists the decoder itself)
+                parts.append(listed(lambda: [("decoder/" + n, p_.data) for n, p_ in self.decoder.named_parameters()]))
+            csr = self.ui_graph_raw.tocsr().copy()
+            csr.sort_indices()
+            describe = {
+                "route": self._route, "device_sampler": bool(self._device_sampler),
+                "step_options": {f: getattr(fused, f) for f in step_options.StepOptions._fields} if fused else None,
+                "fingerprint": checkpoint.fingerprint(vars(args), self.n_users, self.n_items, csr.nnz, csr.indptr.astype(np.int64),
+                                                      csr.indices.astype(np.int64))}
+            self._ckpt = checkpoint.Checkpointer(parts, os.environ.get("LLMREC_CHECKPOINT") or None, describe, log=self.logger.logging)
+        return self._ckpt
+
+    def _checkpoint_host(self, **more):
+        return dict({"_global_step": self._global_step}, **more)
+
+    def save_checkpoint(self, path, **host_state):
+        """The state at this step boundary as one file (any step boundary; train() itself saves at epoch ends). Blocks until it is in place."""
+        self._checkpointer().save(os.path.abspath(path), self._checkpoint_host(**host_state))
+
+    def load_checkpoint(self, path, strict=True):
+        """Make this trainer's state the file's - parameters, optimiser, the step's device counters, the host generators - and return the
+        saved host state. Before the first step, or into a live captured step (a rollback). strict=False: a configuration mismatch warns."""
+        host = self._checkpointer().load(path, strict=strict)
+        self._global_step = int(host.get("_global_step", self._global_step))
+        return host
+
     def train(self):
         now_time = datetime.now()
         run_time = datetime.strftime(now_time, '%Y_%m_%d__%H_%M_%S')
@@ -472,7 +516,25 @@ class Trainer(object):
         # evaluation recognises the object (its device query tensor is converted once, not 13 k python ints per epoch)
         users_to_test = list(data_generator.test_set.keys())
         self._eval_own_list, self._eval_own = users_to_test, None
-        for epoch in range(args.epoch):
+        ckpt_dir, resume = os.environ.get("LLMREC_CHECKPOINT"), os.environ.get("LLMREC_RESUME")
+        ckpt_every = int(os.environ.get("LLMREC_CHECKPOINT_EVERY", "0") or 0)
+        first_epoch = last_epoch = 0
+        if resume:                                                       # before the first step and before any capture
+            host = self.load_checkpoint(resume)
+            # (a file of save_checkpoint() without these keys resumes the state and starts the epoch count over)
+            first_epoch, best_recall, stopping_step = int(host.get("epoch", -1)) + 1, host.get("best_recall", 0), int(host.get("stopping_step", 0))
+            test_ret = host.get("test_ret")
+            if test_ret is not None:
+                test_ret = {k: np.array(v) if isinstance(v, list) else v for k, v in test_ret.items()}
+            last_epoch = first_epoch - 1
+            self.logger.logging("checkpoint: resumed %s, continuing at epoch %d" % (resume, first_epoch))
+        if ckpt_dir:
+            os.makedirs(ckpt_dir, exist_ok=True)
+        # a request is taken behind the epoch's evaluation(s): an evaluation's masking round is inside the saved counter
+        request = lambda name, ep: self._checkpointer().request(name, self._checkpoint_host(
+            epoch=ep, best_recall=best_recall, stopping_step=stopping_step, test_ret=test_ret))
+        for epoch in range(first_epoch, args.epoch):
+            last_epoch = epoch
             t1 = time()
             n_batch = data_generator.n_train // args.batch_size + 1
             sums = torch.zeros(3, dtype=torch.float64, device=device)
@@ -538,12 +600,19 @@ class Trainer(object):
                 self.logger.logging("Test_Recall@%d: %.5f,  precision=[%.5f], ndcg=[%.5f]" % (
                     eval(args.Ks)[1], test_ret['recall'][1], test_ret['precision'][1], test_ret['ndcg'][1]))
                 stopping_step = 0
+                if ckpt_dir:
+                    request("best.ckpt", epoch)
             elif stopping_step < args.early_stopping_patience:
                 stopping_step += 1
                 self.logger.logging('#####Early stopping steps: %d #####' % stopping_step)
             else:
                 self.logger.logging('#####Early stop! #####')
                 break
+            if ckpt_dir and ckpt_every > 0 and (epoch + 1) % ckpt_every == 0:
+                request("last.ckpt", epoch)
+        if ckpt_dir:                                                     # once, by early stop or by the epoch limit; in place on return
+            request("last.ckpt", last_epoch)
+            self._checkpointer().wait()
         self.logger.logging(str(test_ret))
         return best_recall, run_time
 
