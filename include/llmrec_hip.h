@@ -985,6 +985,66 @@ int llmrec_score_auc_f32(int32_t n_query, const int64_t* query_users,
                          void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Serving: exact masked top-K under an item ALLOW-LIST (csrc/serve.hip). No counterpart in the reference, which ranks the whole
+ * catalogue for its test users only (utility/batch_test.py). Additive: the ABI version stays.
+ * For query user u, an allow mask allow[0 .. n_items) (uint8, ANY non-zero byte = eligible) and an optional train CSR the candidates are
+ *     { i : allow[i] != 0 and i not in the train row of u };
+ * the result is the first K of them by (score desc, ORIGINAL item id asc), the scores the bits llmrec_scores_f32 gives, entries behind the
+ * last candidate -1 / -inf: the rule and the arithmetic of llmrec_score_topk_wide_f32. The filter is applied by COMPACTION: the eligible
+ * rows of Ei become a dense table, the queried train rows are rewritten in its numbering, the wide call runs on that table and the ids
+ * are mapped back. A score is a per-pair fma chain that does not depend on where a row sits, and the compact numbering is monotone in
+ * the item id, so order and bits are those of a sweep over the whole table - and a filter that keeps a tenth of the catalogue sweeps a
+ * tenth of it.
+ *
+ * llmrec_item_filter_build: new_id[i] = the rank of i among the eligible items or -1, old_id[r] = the r-th eligible item (entries at and
+ *   beyond the count are not written), n_kept_dev[0] = their count. An exclusive scan of the flags over blocks of LLMREC_FILTER_TILE
+ *   items in three launches - per-block counts, one block scanning the counts, the write -, every cross-block hand-over a kernel boundary:
+ *   no block waits for another, no atomics; deterministic, capturable, nothing read back. n_items in [0, 2^31).
+ *   Workspace: llmrec_item_filter_workspace_bytes = A(4 ceil(n_items / LLMREC_FILTER_TILE)) + 256, A(x) = x rounded up to 256.
+ *
+ * llmrec_score_topk_filtered_f32: the arguments of llmrec_score_topk_wide_f32 (same meaning; 1 <= d <= 128, any ld >= d; query users may
+ *   be unsorted and repeated; mode as there) + the maps of the build + the HOST integer n_kept, which sizes the compact table and the
+ *   launches (the caller reads it once per filter). n_kept == 0: the outputs are filled with -1 / -inf and no sweep is launched (the
+ *   sweeps refuse an empty table). Otherwise, on the caller's one stream:
+ *     (a) the compact item table [n_kept][d4] through old_id (d4 = d rounded up to 4, pad columns zero, 256-byte aligned base - the sweeps'
+ *         vector path applies; row offsets old * ldi in 64 bits);
+ *     (b) the compact user rows [n_query][d4] + the identity query list;
+ *     (c) the mask CSR, n_query + 1 row pointers: row q = the entries c of the train row of query_users[q] with new_id[c] >= 0, written
+ *         as new_id[c] in row order (ascending stays ascending; duplicates are kept, as llmrec_csr_build keeps them) - count per query,
+ *         one single-block scan, write;
+ *     (d) llmrec_score_topk_wide_f32 on the compact tables with the mask as its train CSR (no train CSR: none);
+ *     (e) the ids through old_id; -1 stays -1.
+ *   6 launches (3 without a train CSR) + those of the wide call, a function of the host arguments alone; no allocation, no host read, no
+ *   atomics: capturable and deterministic.
+ *   train_nnz: the capacity of (c) and of the wide call - an upper bound of the sum of the queried train-row lengths, a user listed twice
+ *     counted twice (not read without a train CSR). train_nnz + n_query * K must stay below 2^31 for K > LLMREC_TOPK_MAX.
+ *   Caller errors the DEVICE detects before anything is written outside a buffer - every list then comes back empty (-1 / -inf) and the
+ *     call returns LLMREC_OK, as the wide call does for a short train_nnz: n_kept != n_kept_dev[0] (the compact table is then zero-filled:
+ *     (a) reads old_id only at ranks < n_kept and only when the counts agree), and a mask that outgrows train_nnz (its row pointers are
+ *     then all zero and no column is written).
+ *   Workspace (16-byte aligned; too small: LLMREC_EWORKSPACE): llmrec_score_topk_filtered_workspace_bytes = 0 for n_kept == 0, else
+ *       A(llmrec_score_topk_wide_workspace_bytes(n_query, n_kept, d, K, train_nnz))
+ *       + A(4 n_kept d4) + A(4 n_query d4) + A(8 n_query) + 256 + A(4 n_query) + A(4 (n_query + 1)) + A(4 train_nnz) + 256
+ *     (the wide call's workspace; item rows; user rows; query list; error word; per-query counts; mask row pointers; mask columns), -1
+ *     for bad sizes. llmrec_score_topk_filtered_mask_offset: the byte offset of the mask row pointers inside that workspace (the
+ *     columns follow at + A(4 (n_query + 1))): what a test reads (c) from; -1 where there is no mask (bad sizes, n_kept == 0).
+ * ------------------------------------------------------------------------------------------ */
+#define LLMREC_FILTER_TILE 2048
+int64_t llmrec_item_filter_workspace_bytes(int64_t n_items);
+int llmrec_item_filter_build(int64_t n_items, const uint8_t* allow, int32_t* new_id /* n_items */, int32_t* old_id /* n_items */,
+                             int32_t* n_kept_dev /* 1 */, void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
+int64_t llmrec_score_topk_filtered_workspace_bytes(int32_t n_query, int64_t n_items, int32_t n_kept, int32_t d, int32_t K, int64_t train_nnz);
+int64_t llmrec_score_topk_filtered_mask_offset(int32_t n_query, int64_t n_items, int32_t n_kept, int32_t d, int32_t K, int64_t train_nnz);
+int llmrec_score_topk_filtered_f32(int32_t n_query, const int64_t* query_users,
+                                   const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
+                                   int64_t n_items, int32_t d,
+                                   const int32_t* train_rowptr, const int32_t* train_colidx,
+                                   int32_t K, int32_t* out_idx, float* out_score,
+                                   void* workspace, int64_t workspace_bytes, int32_t mode, int64_t train_nnz,
+                                   const int32_t* new_id, const int32_t* old_id, const int32_t* n_kept_dev, int32_t n_kept,
+                                   llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * R11  on-device BPR sampler             replaces Data.sample (reference
  *                                        utility/load_data.py:157-195): B distinct users
  *                                        (keyed permutation of the users that have train items),

@@ -1358,6 +1358,70 @@ def topk_workspace(n_query: int, n_items: int, device, d: int = 64, K: Optional[
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
 
 
+class ItemFilter:
+    """The id maps of an item allow mask (llmrec_item_filter_build): new_id int32 [n_items] = the rank of an item among the eligible ones or
+    -1, old_id int32 [n_items] = the r-th eligible item (the entries from n_kept on are unspecified), n_kept_dev int32 [1] and the host's n_kept.
+    allow: uint8 or bool [n_items] on the GPU, any non-zero byte = eligible. The build is three launches without atomics; the constructor
+    then reads n_kept, which is ONE HOST READ of the device (the count sizes the compact table and the launches of every filtered call - the
+    trade-off of _wide_train_nnz: pay it once per filter, not per call; not capturable)."""
+
+    def __init__(self, allow: torch.Tensor):
+        _need_gpu(allow)
+        if allow.dtype == torch.bool:
+            allow = allow.view(torch.uint8)
+        if allow.dtype != torch.uint8 or allow.dim() != 1:
+            raise RuntimeError("ItemFilter: a 1-D uint8 / bool mask expected, got %s %s" % (allow.dtype, tuple(allow.shape)))
+        allow = allow.contiguous()
+        n = self.n_items = allow.numel()
+        dev = allow.device
+        self.new_id = torch.empty(n, dtype=torch.int32, device=dev)
+        self.old_id = torch.empty(n, dtype=torch.int32, device=dev)
+        self.n_kept_dev = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(_lib.query("llmrec_item_filter_workspace_bytes", n), dtype=torch.uint8, device=dev)
+        _lib.call("llmrec_item_filter_build", n, _p(allow), _p(self.new_id), _p(self.old_id), _p(self.n_kept_dev), _p(ws), ws.numel(), _stream())
+        self.n_kept = int(self.n_kept_dev.item())
+
+
+def topk_filtered_workspace(n_query: int, n_items: int, n_kept: int, device, d: int = 64, K: int = 50, train_nnz: int = 0) -> torch.Tensor:
+    """Scratch for llmrec_score_topk_filtered_f32 (include/llmrec_hip.h gives the formula)."""
+    nbytes = _lib.query("llmrec_score_topk_filtered_workspace_bytes", n_query, n_items, n_kept, d, K, train_nnz)
+    if nbytes < 0:
+        raise RuntimeError("topk_filtered_workspace: bad sizes (1 <= d <= 128, K <= %d, train_nnz + n_query * K < 2^31)" % CONST["LLMREC_TOPK_WIDE_MAX"])
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def score_topk_filtered(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, filt: Optional[ItemFilter], mode=None,
+                        train_nnz: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """score_topk among the items an ItemFilter keeps: (idx int32 [n, K] in ORIGINAL item ids, -1 = none, scores) - for every listed user the
+    first K of {eligible items not in the user's train row} by (score desc, item id asc), the score bits of ops.scores
+    (llmrec_score_topk_filtered_f32: the eligible rows as a dense table, the train rows in its numbering, the wide call, the ids mapped
+    back; a filter that keeps a tenth of the catalogue sweeps a tenth of it). filt=None forwards to score_topk.
+    train_nnz: as for score_topk - an upper bound of the queried train-row lengths that replaces the one host read (here it is needed at
+    every K, because the compact mask rows are sized by it); a bound that is too small returns empty lists. With it, and a workspace `ws`
+    of topk_filtered_workspace, the call is capturable."""
+    if filt is None:
+        return score_topk(Eu, Ei, query_users, train, K, mode=mode, train_nnz=train_nnz)
+    _need_gpu(Eu, Ei, query_users)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+        raise RuntimeError("score_topk_filtered: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (K, CONST["LLMREC_TOPK_WIDE_MAX"]))
+    if filt.n_items != I:
+        raise RuntimeError("score_topk_filtered: the filter covers %d items, the table has %d" % (filt.n_items, I))
+    kept = filt.n_kept
+    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
+    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
+    if ws is None:
+        ws = topk_filtered_workspace(n, I, kept, Eu.device, d, K, nnz)
+    _lib.call("llmrec_score_topk_filtered_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
+              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz,
+              _p(filt.new_id), _p(filt.old_id), _p(filt.n_kept_dev), kept, _stream())
+    return idx, sc
+
+
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage-1 candidate export: the top-k item ids per user WITHOUT masking, i.e. what the reference
     README's `torch.topk(user_emb @ item_emb.T, k=10)` snippet (README.md:243-247) produces for
