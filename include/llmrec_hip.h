@@ -1045,7 +1045,71 @@ int llmrec_score_topk_filtered_f32(int32_t n_query, const int64_t* query_users,
                                    llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * R11  on-device BPR sampler             replaces Data.sample (reference
+ * Serving with PER-QUERY exclusion lists (csrc/exclude.hip): items a user bought, saw or dismissed since the graph was built, items
+ * already shown, the earlier pages of a result. Additive: the ABI version stays, and llmrec_score_topk_filtered_f32 is unchanged.
+ *
+ * llmrec_score_topk_excluded_f32: the arguments of llmrec_score_topk_wide_f32 up to train_nnz (same meaning; 1 <= d <= 128; query users may
+ *   be unsorted and repeated), an exclusion CSR over the QUERIES of this call, and the filter arguments of the filtered call.
+ *   Result: for every query q the first K items of
+ *       { eligible items } minus { train row of query_users[q] } minus { exclusion row q }
+ *   by (score desc, ORIGINAL item id asc), the scores the bits of llmrec_scores_f32, -1 / -inf behind the last candidate, ids ORIGINAL ids.
+ *   The exclusion CSR: excl_rowptr [n_query + 1], excl_colidx [excl_nnz], int32, on the device. Row q belongs to QUERY q, not to a user:
+ *     a user listed twice may carry two different rows. Entries come in any order and may repeat. An entry < 0 or >= n_items is ignored
+ *     (-1 padding, as a previous call's output has it); with a filter so is an entry whose item is ineligible.
+ *     excl_rowptr == NULL with excl_nnz == 0: no exclusions (excl_colidx is then not read). excl_nnz is the EXACT entry count,
+ *     excl_rowptr[n_query]; excl_nnz > 0 needs both pointers.
+ *   The filter: new_id / old_id / n_kept_dev all NULL with n_kept == n_items: NO FILTER - the numbering is the identity, Ei is swept in
+ *     place through ldi (no item gather, no copy of the table) and no id is mapped back. Otherwise the three maps of
+ *     llmrec_item_filter_build and the host's n_kept, with the hand-shake of the filtered call (n_kept != n_kept_dev[0] sets the error
+ *     word). Maps that keep every item (n_kept == n_items) number the items as they are: Ei is swept in place then too.
+ *   The mask the sweeps read, n_query + 1 row pointers: row q = the ascending STABLE merge of
+ *       the train row's kept entries in the swept numbering, in row order - exactly row q of the filtered call's mask -, and
+ *       the exclusion row's kept entries in the swept numbering, sorted ascending;
+ *     duplicates are kept on both sides, and a train entry comes before an equal exclusion entry.
+ *   On the caller's one stream: (a) the compact user rows + the identity query list, and with a filter the compact item table, as the
+ *     filtered call; (b) entry e of exclusion row q (q by binary search in excl_rowptr) -> the 64-bit key q << 32 | id, a dropped entry ->
+ *     n_query << 32, behind every row; the same launch checks excl_rowptr; (c) one radix sort of the keys (the vendor sort of
+ *     llmrec_scatter_rows_f32, between two buffers of the workspace, bits [0, 32 + bits of n_query)); (d) per query the kept train count and
+ *     the lower bound of q << 32 in the sorted keys - the bound IS the exclusive scan of the kept exclusion counts; (e) one single-block scan:
+ *     the row pointers of the train side and, + the bounds, of the merged mask; (f) the train side's rows; (g) the merge, one wave per query,
+ *     wave-strided: a train entry lands at its index + the number of the query's keys below it, a key at its index + the number of train
+ *     entries at or below it, both by binary search - rows of thousands of entries need no LDS; (h) llmrec_score_topk_wide_f32 over the
+ *     swept tables with the merged mask, capacity train_nnz + excl_nnz; (i) ids through old_id (filter only) and, under the error word, -1 / -inf.
+ *     6 launches (5 without an exclusion CSR) + 1 with a filter + 1 with a train CSR + the sort's + the wide call's: a function of the host
+ *     arguments alone; no allocation, no host read, no atomics, every cross-block hand-over a kernel boundary: capturable and deterministic.
+ *   train_nnz: as for the filtered call (an upper bound of the sum of the queried train-row lengths; not read without a train CSR).
+ *     train_nnz + excl_nnz + n_query * K must stay below 2^31 (at every K).
+ *   Caller errors the DEVICE detects before anything is written outside a buffer - every list then comes back empty (-1 / -inf) and the call
+ *     returns LLMREC_OK: a train side that outgrows train_nnz; an excl_rowptr that does not start at 0, end at excl_nnz and never decrease;
+ *     n_kept != n_kept_dev[0]. The mask's row pointers are then all zero and no column is written.
+ *   n_kept == 0: the outputs are filled with -1 / -inf and no sweep is launched. n_query == 0: no launch.
+ *   Workspace (16-byte aligned; too small: LLMREC_EWORKSPACE): llmrec_score_topk_excluded_workspace_bytes = 0 for n_kept == 0, else
+ *       A(llmrec_score_topk_wide_workspace_bytes(n_query, n_kept, d, K, train_nnz + excl_nnz))
+ *       + [n_kept != n_items: A(4 n_kept d4)] + A(4 n_query d4) + A(8 n_query) + 256 + A(4 n_query) + 2 A(4 (n_query + 1))
+ *       + A(4 train_nnz) + 256 + 2 A(8 excl_nnz) + [excl_nnz > 0: A(excl_nnz + 32 MiB)]
+ *       + A(4 (n_query + 1)) + A(4 (train_nnz + excl_nnz)) + 256
+ *     (the wide call's workspace; item rows; user rows; query list; error word; train counts; train row pointers and key bounds; train
+ *     columns; two key buffers; the sort's temporary storage, the bound of llmrec_scatter_rows_workspace_bytes - a sort that asks for more
+ *     is LLMREC_EWORKSPACE before the first launch; mask row pointers; mask columns), -1 for bad sizes, the 2^31 sum included.
+ *     llmrec_score_topk_excluded_mask_offset: the byte offset of the merged mask's row pointers inside that workspace (the columns follow at
+ *     + A(4 (n_query + 1)), as the filtered call lays them out); -1 where there is no mask (bad sizes, n_kept == 0).
+ * ------------------------------------------------------------------------------------------ */
+int64_t llmrec_score_topk_excluded_workspace_bytes(int32_t n_query, int64_t n_items, int32_t n_kept, int32_t d, int32_t K, int64_t train_nnz,
+                                                   int64_t excl_nnz);
+int64_t llmrec_score_topk_excluded_mask_offset(int32_t n_query, int64_t n_items, int32_t n_kept, int32_t d, int32_t K, int64_t train_nnz,
+                                               int64_t excl_nnz);
+int llmrec_score_topk_excluded_f32(int32_t n_query, const int64_t* query_users,
+                                   const float* Eu, int64_t ldu, const float* Ei, int64_t ldi,
+                                   int64_t n_items, int32_t d,
+                                   const int32_t* train_rowptr, const int32_t* train_colidx,
+                                   int32_t K, int32_t* out_idx, float* out_score,
+                                   void* workspace, int64_t workspace_bytes, int32_t mode, int64_t train_nnz,
+                                   const int32_t* excl_rowptr /* n_query + 1 */, const int32_t* excl_colidx, int64_t excl_nnz,
+                                   const int32_t* new_id, const int32_t* old_id, const int32_t* n_kept_dev, int32_t n_kept,
+                                   llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * R11  on-device BPR sampler            replaces Data.sample (reference
  *                                        utility/load_data.py:157-195): B distinct users
  *                                        (keyed permutation of the users that have train items),
  *                                        one uniform positive from the user's CSR row, one

@@ -1422,6 +1422,57 @@ def score_topk_filtered(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr],
     return idx, sc
 
 
+def topk_excluded_workspace(n_query: int, n_items: int, n_kept: int, device, d: int = 64, K: int = 50, train_nnz: int = 0,
+                            excl_nnz: int = 0) -> torch.Tensor:
+    """Scratch for llmrec_score_topk_excluded_f32 (include/llmrec_hip.h gives the formula); n_kept = n_items without a filter."""
+    nbytes = _lib.query("llmrec_score_topk_excluded_workspace_bytes", n_query, n_items, n_kept, d, K, train_nnz, excl_nnz)
+    if nbytes < 0:
+        raise RuntimeError("topk_excluded_workspace: bad sizes (1 <= d <= 128, K <= %d, train_nnz + excl_nnz + n_query * K < 2^31)"
+                           % CONST["LLMREC_TOPK_WIDE_MAX"])
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def score_topk_excluded(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, exclude, filt: Optional[ItemFilter] = None, mode=None,
+                        train_nnz: Optional[int] = None, ws: Optional[torch.Tensor] = None):
+    """score_topk_filtered with one more exclusion list PER QUERY: (idx int32 [n, K] in ORIGINAL item ids, -1 = none, scores) - for query q
+    the first K of {eligible items} minus {train row of its user} minus {exclusion row q} by (score desc, item id asc), the score bits of
+    ops.scores (llmrec_score_topk_excluded_f32: the rows are sorted and merged with the train rows on the device, the unchanged sweeps run
+    over the merged mask). exclude: (rowptr int32 [n + 1], colidx int32) on the device, a CSR over the QUERIES of this call - a user listed
+    twice may carry two rows; entries in any order, repeats allowed, entries < 0 or >= n_items ignored (-1 padding), ineligible items
+    ignored. colidx.numel() must be rowptr[n] (the device checks it; a mismatch returns empty lists). exclude=None forwards to
+    score_topk_filtered: the same launches and bits as without this call. filt=None: no filter, Ei is swept in place.
+    train_nnz / ws (topk_excluded_workspace): as for score_topk_filtered; with both the call is capturable."""
+    if exclude is None:
+        return score_topk_filtered(Eu, Ei, query_users, train, K, filt, mode=mode, train_nnz=train_nnz, ws=ws)
+    rowptr, colidx = exclude
+    _need_gpu(Eu, Ei, query_users, rowptr, colidx)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+        raise RuntimeError("score_topk_excluded: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (K, CONST["LLMREC_TOPK_WIDE_MAX"]))
+    if filt is not None and filt.n_items != I:
+        raise RuntimeError("score_topk_excluded: the filter covers %d items, the table has %d" % (filt.n_items, I))
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() != n + 1:
+        raise RuntimeError("score_topk_excluded: exclude = (rowptr int32 [%d], colidx int32 [nnz]) expected, got %s %s and %s %s"
+                           % (n + 1, rowptr.dtype, tuple(rowptr.shape), colidx.dtype, tuple(colidx.shape)))
+    rowptr, colidx = rowptr.contiguous(), colidx.contiguous()
+    kept = filt.n_kept if filt is not None else I
+    excl_nnz = colidx.numel()
+    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
+    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
+    if ws is None:
+        ws = topk_excluded_workspace(n, I, kept, Eu.device, d, K, nnz, excl_nnz)
+    _lib.call("llmrec_score_topk_excluded_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
+              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz,
+              _p(rowptr), _p(colidx) if excl_nnz else None, excl_nnz,
+              _p(filt.new_id) if filt is not None else None, _p(filt.old_id) if filt is not None else None,
+              _p(filt.n_kept_dev) if filt is not None else None, kept, _stream())
+    return idx, sc
+
+
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage-1 candidate export: the top-k item ids per user WITHOUT masking, i.e. what the reference
     README's `torch.topk(user_emb @ item_emb.T, k=10)` snippet (README.md:243-247) produces for

@@ -1,13 +1,15 @@
 """Recommend from a checkpoint: the top-K items for a list of users, optionally among an allow-list or outside a deny-list of items.
 
     python recommend.py --checkpoint ckpt/best.ckpt --users users.txt --topk 20 [--allow_items F | --deny_items F] [--include_seen]
-                        --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model was trained with ...]
+                        [--exclude F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model was trained with ...]
 
 The flags above are this script's own; EVERY OTHER argument goes to the drop-in's parser untouched (utility/parser.py - the
 configuration the checkpoint was written under: a checkpoint of another configuration fails its fingerprint check). The script builds
 the Trainer, loads the checkpoint, recommends (llmrec_amd.serve.Recommender) and writes out.npz with `users` int64 [n], `items` int64
 [n, K] (-1 behind the last candidate) and `scores` float32 [n, K]. It trains nothing. Id files are .npy (integers) or text with one id
-per line. --mask / --mask_rate != 0 are refused: with them every forward is a masking round, and a serving run must not advance one."""
+per line. --exclude: (user, item) pairs - a .npy integer array [m, 2] or text with one `user item` per line -, items left out for that user
+on top of the train row; a pair applies to every occurrence of its user in --users, and a user that is not listed is ignored.
+--mask / --mask_rate != 0 are refused: with them every forward is a masking round, and a serving run must not advance one."""
 import argparse
 import importlib
 import os
@@ -27,6 +29,7 @@ def own_parser() -> argparse.ArgumentParser:
     g.add_argument("--allow_items", help="rank only among these item ids (.npy or text)")
     g.add_argument("--deny_items", help="rank among all but these item ids (.npy or text)")
     p.add_argument("--include_seen", action="store_true", help="do not exclude the user's train items")
+    p.add_argument("--exclude", help="(user, item) pairs to leave out per user: .npy [m, 2] or text, one `user item` per line")
     p.add_argument("--out", required=True, help="the .npz to write")
     return p
 
@@ -45,6 +48,35 @@ def read_ids(path: str) -> np.ndarray:
         return a.reshape(-1).astype(np.int64)
     with open(path) as f:
         return np.asarray([int(line) for line in f if line.strip()], dtype=np.int64)
+
+
+def read_pairs(path: str) -> np.ndarray:
+    """int64 (user, item) pairs [m, 2] from a .npy file or from text with one `user item` per line (blank lines ignored)."""
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != 2:
+            raise SystemExit("%s: an integer array [m, 2] of (user, item) pairs expected, got %s %s" % (path, a.dtype, a.shape))
+        return a.astype(np.int64)
+    pairs = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            w = line.split()
+            if not w:
+                continue
+            if len(w) != 2:
+                raise SystemExit("%s:%d: `user item` expected, got %r" % (path, no, line.strip()))
+            pairs.append((int(w[0]), int(w[1])))
+    return np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+
+
+def exclusion_lists(pairs: np.ndarray, users: np.ndarray) -> dict:
+    """{user: int64 item ids, in file order} of the pairs whose user is listed - Recommender.recommend's dict form, which applies a list
+    to every occurrence of its user."""
+    listed = np.isin(pairs[:, 0], users)
+    out = {}
+    for u, i in pairs[listed]:
+        out.setdefault(int(u), []).append(int(i))
+    return {u: np.asarray(v, dtype=np.int64) for u, v in out.items()}
 
 
 def refuse_masking(dropin_args):
@@ -76,12 +108,13 @@ def main(argv=None):
     users = read_ids(own.users)
     allow = read_ids(own.allow_items) if own.allow_items else None
     deny = read_ids(own.deny_items) if own.deny_items else None
+    exclude = exclusion_lists(read_pairs(own.exclude), users) if own.exclude else None
     m = load_dropin(rest)
     from llmrec_amd.serve import Recommender
     m.set_seed(m.args.seed)
     trainer = m.Trainer(data_config={})
     rec = Recommender.from_checkpoint(trainer, own.checkpoint)
-    items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen)
+    items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
     out = own.out if own.out.endswith(".npz") else own.out + ".npz"
     np.savez(out, users=users, items=items.cpu().numpy(), scores=scores.cpu().numpy())
     print("recommend.py: %d users x top %d -> %s" % (len(users), own.topk, out))
