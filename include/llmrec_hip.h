@@ -1109,6 +1109,37 @@ int llmrec_score_topk_excluded_f32(int32_t n_query, const int64_t* query_users,
                                    llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Serving users who are NOT rows of the training graph (csrc/foldin.hip): the embedding the trained model gives a row of the
+ * normalised adjacency that it has never seen, from the item-side tables alone. Additive: the ABI version stays.
+ *
+ * llmrec_fold_in_users_f32: n new users as a CSR over item ids (rowptr int32 [n + 1], colidx int32 [nnz], nnz = rowptr[n], on the
+ *   device), row_scale float [n] (the caller's: D^-1/2 of the row), id_rows [n][d] through ldid or NULL (zeros), and ONE table
+ *   T [n_items][C d] through ldt, C = L + 2 + n_attr + 1 slices of d columns:
+ *       chain I_0 .. I_{L-1} | image | text | attribute 0 .. n_attr - 1 | profile.
+ *   With S = the sum of T's rows at the entries of row r and g(c) = row_scale[r] * S[slice c]:
+ *       out[r] = (id_rows[r] + g(0) + ... + g(L - 2) + softmax(g(L - 1))) * fl(1 / (L + 1))
+ *                + c_m n(g(image)) + c_m n(g(text)) + c_u n(g(profile)) + sum_k c_a n(g(attribute k)),  n(x) = x / max(||x||_2, 1e-12),
+ *   added in this order, the mean and the normalised terms with the operations of llmrec_fuse_fwd_f32.
+ *   Entries < 0 or >= n_items add nothing (-1 padding; they do not change row_scale, which is the caller's); repeats count every time;
+ *   an empty row gives zero sums and a uniform softmax row. A row whose pointers are no CSR row (outside 0 <= rowptr[r] <=
+ *   rowptr[r + 1] <= nnz) counts as empty.
+ *   The sum is fp32 in a fixed order that depends on the row's length alone: segments of 256 entries; inside a segment of len entries
+ *   four runs of ceil(len / 4) consecutive entries, each added in the order given, meet as (r0 + r1) + (r2 + r3); the segments are
+ *   added in order. No atomics: a row's bits do not depend on the other rows of the call, on its position in it, or on the run.
+ *   One launch (every row of one segment is finished by the block that summed it); with nnz > 256 a second launch finishes the rows of
+ *   more than one segment from the workspace. Grids come from n and nnz: no host read, capturable. Offsets into T are 64-bit.
+ *   1 <= d <= 128, L >= 1, n_attr <= LLMREC_MAX_TERMS - 3, C d <= 2048 (else LLMREC_EUNSUPPORTED). float4 loads where d % 4 == 0,
+ *   ldt % 4 == 0 and T is 16-byte aligned, scalar loads otherwise: the same sums, bit for bit.
+ *   Workspace (16-byte aligned; too small: LLMREC_EWORKSPACE): llmrec_fold_in_users_workspace_bytes = 0 for nnz <= 256, else
+ *   (n + floor(nnz / 256)) * C d * 4 - one [C d] slot per block; -1 for bad sizes.
+ * ------------------------------------------------------------------------------------------ */
+int64_t llmrec_fold_in_users_workspace_bytes(int32_t n, int64_t nnz, int32_t L, int32_t n_attr, int32_t d);
+int llmrec_fold_in_users_f32(int32_t n, const int32_t* rowptr /* n + 1 */, const int32_t* colidx, int64_t nnz, const float* row_scale,
+                             const float* id_rows, int64_t ldid, const float* T, int64_t ldt, int64_t n_items,
+                             int32_t L, int32_t n_attr, int32_t d, float c_m, float c_u, float c_a,
+                             float* out, int64_t ldo, void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * R11  on-device BPR sampler            replaces Data.sample (reference
  *                                        utility/load_data.py:157-195): B distinct users
  *                                        (keyed permutation of the users that have train items),

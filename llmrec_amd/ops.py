@@ -1492,6 +1492,116 @@ def scores(Eu, Ei, query_users: torch.Tensor):
     return S
 
 
+# ---------------------------------------------------------------------------------------------
+# Serving: fold-in of users who are not rows of the graph (csrc/foldin.hip)
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class FoldInTables:
+    """The item side of a trained model in the form llmrec_fold_in_users_f32 gathers: ONE fp32 table T [n_items, C * d], C = L + 2 +
+    n_attr + 1 slices of d columns - chain I_0 .. I_{L-1} | image | text | attributes (the model's key order) | profile -, so that one
+    gathered item is one contiguous read; and what the kernel needs beside it: L, n_attr, d and the three rates (model_cat_rate,
+    user_cat_rate, item_cat_rate)."""
+    T: torch.Tensor
+    L: int
+    n_attr: int
+    d: int
+    c_m: float
+    c_u: float
+    c_a: float
+
+    @property
+    def C(self) -> int:
+        return self.L + 3 + self.n_attr
+
+    @property
+    def n_items(self) -> int:
+        return self.T.shape[0]
+
+    def slice(self, c: int) -> torch.Tensor:
+        """slice c of T as a column view [n_items, d]"""
+        return self.T[:, c * self.d:(c + 1) * self.d]
+
+    @staticmethod
+    def from_model(model, ui, iu, rates) -> "FoldInTables":
+        """The tables of `model` (MM_Model) as it stands, without dropout or masking whatever its mode: the projections and products of
+        MM_Model.forward's item side, by the kernels that forward runs (llmrec_linear_fwd_f32, llmrec_spmm_f32), written straight into
+        the column views of T. ui / iu: the normalised adjacency and its transpose (SparseOperand or the torch sparse tensors the
+        forward takes); rates: (model_cat_rate, user_cat_rate, item_cat_rate). Paid once per loaded checkpoint."""
+        ui = operand_from_sparse_tensor(ui) if isinstance(ui, torch.Tensor) else ui
+        iu = operand_from_sparse_tensor(iu) if isinstance(iu, torch.Tensor) else iu
+        keys = list(model.item_feats.keys())
+        L, d = int(model.n_ui_layers), model.item_id_embedding.weight.shape[1]
+        n_items = model.item_id_embedding.weight.shape[0]
+        if L < 1:
+            raise RuntimeError("FoldInTables: a model without a propagation layer has no user side to fold into")
+        c_m, c_u, c_a = (float(r) for r in rates)
+        with torch.no_grad():
+            t = FoldInTables(torch.empty(n_items, (L + 3 + len(keys)) * d, dtype=torch.float32, device=model.item_id_embedding.weight.device),
+                             L, len(keys), d, c_m, c_u, c_a)
+            t.slice(0).copy_(model.item_id_embedding.weight.detach())
+            for l in range(1, L):                                  # intermediate layers: no softmax
+                spmm_raw(iu.fwd, spmm_raw(ui.fwd, t.slice(l - 1)), out=t.slice(l))
+            lin = lambda feats, m, c: linear_fwd_raw(feats, m.weight.detach(), m.bias.detach(), out=t.slice(c))
+            lin(model.image_feats, model.image_trans, L)
+            lin(model.text_feats, model.text_trans, L + 1)
+            for k, key in enumerate(keys):
+                lin(model.item_feats[key], model.item_trans, L + 2 + k)
+            spmm_raw(iu.fwd, linear_fwd_raw(model.user_feats, model.user_trans.weight.detach(), model.user_trans.bias.detach()), out=t.slice(t.C - 1))
+        return t
+
+
+def fold_in_workspace(n: int, nnz: int, tables: FoldInTables, device) -> Optional[torch.Tensor]:
+    """Scratch for llmrec_fold_in_users_f32 (None where it needs none: no row can exceed one segment)."""
+    nbytes = _lib.query("llmrec_fold_in_users_workspace_bytes", n, nnz, tables.L, tables.n_attr, tables.d)
+    if nbytes < 0:
+        raise RuntimeError("fold_in_workspace: bad sizes (n, nnz < 2^31)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def fold_in_row_scale(rowptr: torch.Tensor) -> torch.Tensor:
+    """float32((float64(deg) + 1e-8) ** -0.5) per row, on the device: csr_norm's row constant for the lengths of `rowptr`."""
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.float64)
+    return (deg + 1e-8).pow(-0.5).to(torch.float32)
+
+
+def fold_in_users(tables: FoldInTables, rowptr: torch.Tensor, colidx: torch.Tensor, row_scale: Optional[torch.Tensor] = None,
+                  id_rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[n, d]: the embeddings the model behind `tables` gives n users who are not rows of its graph, from their item histories
+    (llmrec_fold_in_users_f32; include/llmrec_hip.h states the formula and the order of the sums). rowptr int32 [n + 1], colidx int32
+    [rowptr[n]] on the device: entries in the order to add them, repeats count, entries < 0 or >= n_items add nothing.
+    row_scale float32 [n]: D^-1/2 of each row - None: fold_in_row_scale(rowptr), i.e. from the row LENGTHS (padding included: it is
+    the caller's to pass rows without it, or the scale). id_rows [n, d]: the users' own id rows (None: zeros).
+    With row_scale, out and ws (fold_in_workspace) given the call allocates nothing and reads nothing back: capturable."""
+    _need_gpu(tables.T, rowptr, colidx, row_scale, id_rows, out, ws)
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() < 1:
+        raise RuntimeError("fold_in_users: rowptr int32 [n + 1] and colidx int32 [nnz] expected, got %s %s and %s %s"
+                           % (rowptr.dtype, tuple(rowptr.shape), colidx.dtype, tuple(colidx.shape)))
+    rowptr, colidx = rowptr.contiguous(), colidx.contiguous()
+    n, nnz, d = rowptr.numel() - 1, colidx.numel(), tables.d
+    T = tables.T
+    if T.dtype != torch.float32 or T.dim() != 2 or T.stride(1) != 1 or T.shape[1] != tables.C * d:
+        raise RuntimeError("fold_in_users: T must be fp32 [n_items, %d] with unit inner stride" % (tables.C * d))
+    if row_scale is None:
+        row_scale = fold_in_row_scale(rowptr)
+    if row_scale.dtype != torch.float32 or row_scale.numel() != n or not row_scale.is_contiguous():
+        raise RuntimeError("fold_in_users: row_scale must be contiguous fp32 [%d]" % n)
+    if id_rows is not None:
+        if id_rows.dtype != torch.float32 or tuple(id_rows.shape) != (n, d) or id_rows.stride(1) != 1:
+            raise RuntimeError("fold_in_users: id_rows must be fp32 [%d, %d] with unit inner stride" % (n, d))
+        id_rows = id_rows.detach()
+    if out is None:
+        out = torch.empty(n, d, dtype=torch.float32, device=T.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, d) or out.stride(1) != 1:
+        raise RuntimeError("fold_in_users: out must be fp32 [%d, %d] with unit inner stride" % (n, d))
+    if ws is None:
+        ws = fold_in_workspace(n, nnz, tables, T.device)
+    _lib.call("llmrec_fold_in_users_f32", n, _p(rowptr), _p(colidx) if nnz else None, nnz, _p(row_scale),
+              _p(id_rows), _ld(id_rows) if id_rows is not None else 0, _p(T), _ld(T), T.shape[0],
+              tables.L, tables.n_attr, d, tables.c_m, tables.c_u, tables.c_a, _p(out), _ld(out),
+              _p(ws), ws.numel() if ws is not None else 0, _stream())
+    return out
+
+
 def topk_hits(topk_idx: torch.Tensor, query_users: torch.Tensor, test_rowptr: torch.Tensor, test_colidx: torch.Tensor):
     q = query_users.to(torch.int64).contiguous()
     hits = torch.empty(topk_idx.shape, dtype=torch.uint8, device=topk_idx.device)

@@ -12,7 +12,11 @@ them with the train rows into the mask the same sweeps read (csrc/exclude.hip). 
 {eligible items, minus the user's train row with exclude_seen, minus the user's exclusion list} by (score descending, item id ascending),
 the scores the bits of ops.scores.
 
-Not covered: dp.py and the sharded evaluations take neither a filter nor exclusion lists, and the allow-list is one
+Users who are not rows of the graph (fold_in=True at construction): rec.recommend_new(histories, 20) / rec.embed_new(histories) embed
+each item history with the trained model, the item side held fixed (ops.FoldInTables / ops.fold_in_users, csrc/foldin.hip), and rank
+the new rows by the same exact top-K, the history's own items excluded.
+
+Not covered: fold-in moves no item embedding and adds no user to the graph; dp.py and the sharded evaluations take neither a filter nor exclusion lists, and the allow-list is one
 item set for all users of a call."""
 from __future__ import annotations
 
@@ -67,7 +71,7 @@ def _int_array(a, what: str) -> np.ndarray:
     return a.astype(np.int64)
 
 
-def exclusion_csr(exclude, users, n_items: int) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+def exclusion_csr(exclude, users, n_items: int, what: str = "exclude") -> Optional[Tuple[np.ndarray, np.ndarray]]:
     """Recommender.recommend's `exclude`, normalised on the HOST to one CSR over the listed users: (rowptr int32 [n + 1], colidx int32), row
     q = the list of the q-th listed user, entries in the order given. `users`: the n listed user ids (host integers). Accepted:
       None                               -> None (no lists)
@@ -76,40 +80,40 @@ def exclusion_csr(exclude, users, n_items: int) -> Optional[Tuple[np.ndarray, np
       an array or tensor [n, m]          one row per listed user, -1 padding: what a previous recommend() returned
       any other sequence of n sequences  one per listed user, in order (a list of two lists is this form; the pair is a tuple)
     Negative entries are padding and are dropped; an id >= n_items raises ValueError, as do a wrong row count, non-integer ids and a broken
-    rowptr. Pure host code: no device is needed."""
+    rowptr. `what` names the argument in the messages. Pure host code: no device is needed."""
     if exclude is None:
         return None
     users = np.asarray(users, dtype=np.int64).reshape(-1)
     n = users.size
     if isinstance(exclude, dict):
-        lists = {int(u): _int_array(v, "exclude[%r]" % (u,)).reshape(-1) for u, v in exclude.items()}
+        lists = {int(u): _int_array(v, "%s[%r]" % (what, u)).reshape(-1) for u, v in exclude.items()}
         none = np.zeros(0, np.int64)
         rows = [lists.get(int(u), none) for u in users]
     elif isinstance(exclude, tuple) and len(exclude) == 2:
-        rp, ci = _int_array(exclude[0], "exclude rowptr").reshape(-1), _int_array(exclude[1], "exclude colidx").reshape(-1)
+        rp, ci = _int_array(exclude[0], what + " rowptr").reshape(-1), _int_array(exclude[1], what + " colidx").reshape(-1)
         if rp.size != n + 1:
-            raise ValueError("exclude: rowptr of %d entries for %d users (n + 1 expected)" % (rp.size, n))
+            raise ValueError("%s: rowptr of %d entries for %d users (n + 1 expected)" % (what, rp.size, n))
         if rp[0] != 0 or rp[-1] != ci.size or np.any(np.diff(rp) < 0):
-            raise ValueError("exclude: rowptr must rise from 0 to len(colidx) = %d without decreasing" % ci.size)
+            raise ValueError("%s: rowptr must rise from 0 to len(colidx) = %d without decreasing" % (what, ci.size))
         rows = [ci[a:b] for a, b in zip(rp[:-1], rp[1:])]
     elif isinstance(exclude, (np.ndarray, torch.Tensor)) and exclude.ndim == 2:
-        a = _int_array(exclude, "exclude")
+        a = _int_array(exclude, what)
         if a.shape[0] != n:
-            raise ValueError("exclude: %d rows for %d users" % (a.shape[0], n))
+            raise ValueError("%s: %d rows for %d users" % (what, a.shape[0], n))
         rows = list(a)
     else:
         if isinstance(exclude, (np.ndarray, torch.Tensor)) or not hasattr(exclude, "__len__"):
-            raise ValueError("exclude: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
+            raise ValueError("%s: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected" % what)
         if len(exclude) != n:
-            raise ValueError("exclude: %d rows for %d users" % (len(exclude), n))
-        rows = [_int_array(r, "exclude[%d]" % i).reshape(-1) for i, r in enumerate(exclude)]
+            raise ValueError("%s: %d rows for %d users" % (what, len(exclude), n))
+        rows = [_int_array(r, "%s[%d]" % (what, i)).reshape(-1) for i, r in enumerate(exclude)]
     rows = [r[r >= 0] for r in rows]
     top = max((int(r.max()) for r in rows if r.size), default=-1)
     if top >= n_items:
-        raise ValueError("exclude: ids must lie in [0, %d) or be negative padding; got %d" % (n_items, top))
+        raise ValueError("%s: ids must lie in [0, %d) or be negative padding; got %d" % (what, n_items, top))
     rowptr = np.concatenate([[0], np.cumsum([r.size for r in rows], dtype=np.int64)])
     if rowptr[-1] >= 1 << 31:
-        raise ValueError("exclude: %d entries exceed int32 row pointers" % rowptr[-1])
+        raise ValueError("%s: %d entries exceed int32 row pointers" % (what, rowptr[-1]))
     colidx = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     return rowptr.astype(np.int32), colidx.astype(np.int32)
 
@@ -120,23 +124,74 @@ def csr_slice(csr: Tuple[np.ndarray, np.ndarray], a: int, b: int) -> Tuple[np.nd
     return (rp[a:b + 1] - rp[a]).astype(np.int32), ci[rp[a]:rp[b]]
 
 
+def history_csr(histories, n_items: int, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Recommender.recommend_new's `histories`, normalised on the HOST: (rowptr int32 [n + 1], colidx int32), row q = the item set of new
+    user q - sorted, unique, in range. A history is a set, as a row of the binary adjacency is, and sorting makes the embedding
+    independent of the order given, bit for bit. The container forms of exclusion_csr, except that a dict is keyed by POSITION: key q is
+    new user q, and without `n` the dict has max key + 1 rows. n: the row count something else fixes (id_rows); another count raises
+    ValueError, as do a dict key outside [0, n), an id >= n_items and non-integer ids. Negative ids are padding."""
+    if histories is None:
+        raise ValueError("histories: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
+    if isinstance(histories, dict):
+        keys = [int(q) for q in histories]
+        rows = (max(keys) + 1 if keys else 0) if n is None else int(n)
+        if keys and (min(keys) < 0 or max(keys) >= rows):
+            raise ValueError("histories: a dict is keyed by position, keys must lie in [0, %d); got %d .. %d" % (rows, min(keys), max(keys)))
+    elif isinstance(histories, tuple) and len(histories) == 2:
+        rows = _int_array(histories[0], "histories rowptr").size - 1
+    elif hasattr(histories, "__len__") and not (isinstance(histories, (np.ndarray, torch.Tensor)) and histories.ndim != 2):
+        rows = len(histories)
+    else:
+        rows = 0                                                   # (not a container: exclusion_csr names what is expected)
+    if n is not None and rows != int(n):
+        raise ValueError("histories: %d rows for %d new users" % (rows, n))
+    rp, ci = exclusion_csr(histories, np.arange(rows), n_items, what="histories")
+    q = np.repeat(np.arange(rows, dtype=np.int64), np.diff(rp))
+    key = np.unique(q * n_items + ci)                              # sorted by (row, id), repeats collapsed
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(key // n_items, minlength=rows), dtype=np.int64)])
+    return rowptr.astype(np.int32), (key % n_items).astype(np.int32)
+
+
+def csr_join(a: Tuple[np.ndarray, np.ndarray], b: Optional[Tuple[np.ndarray, np.ndarray]]) -> Tuple[np.ndarray, np.ndarray]:
+    """Row q of the result = row q of `a` followed by row q of `b` (two host CSRs over the same rows; b None: a)."""
+    if b is None:
+        return a
+    (ra, ca), (rb, cb) = a, b
+    n = ra.size - 1
+    q = np.concatenate([np.repeat(np.arange(n), np.diff(ra)), np.repeat(np.arange(n), np.diff(rb))])
+    col = np.concatenate([ca, cb])[np.argsort(q, kind="stable")]
+    return (ra.astype(np.int64) + rb).astype(np.int32), col.astype(np.int32)
+
+
 class Recommender:
-    def __init__(self, E_u: torch.Tensor, E_i: torch.Tensor, train: Optional[ops.Csr]):
+    def __init__(self, E_u: torch.Tensor, E_i: torch.Tensor, train: Optional[ops.Csr], fold_in: Optional[ops.FoldInTables] = None,
+                 iu: Optional[ops.Csr] = None):
         """E_u [n_users, d], E_i [n_items, d] fp32 on the GPU (CLONED here: a trainer that goes on training does not move them);
-        train: the device CSR of the interactions to exclude (ops.Csr, rows ascending), or None."""
+        train: the device CSR of the interactions to exclude (ops.Csr, rows ascending), or None. fold_in: the item-side tables
+        recommend_new / embed_new gather (ops.FoldInTables, with the rates), iu: the item-side CSR they were built over - both None:
+        only users of the graph can be served."""
         ops._need_gpu(E_u, E_i)
         if E_u.dim() != 2 or E_i.dim() != 2 or E_u.shape[1] != E_i.shape[1]:
             raise ValueError("Recommender: E_u [n_users, d] and E_i [n_items, d] expected, got %s and %s" % (tuple(E_u.shape), tuple(E_i.shape)))
         self.E_u, self.E_i = E_u.detach().clone(), E_i.detach().clone()
         self.n_users, self.n_items = self.E_u.shape[0], self.E_i.shape[0]
         self.train = train
+        if fold_in is not None and (fold_in.n_items != self.n_items or fold_in.d != self.E_i.shape[1]):
+            raise ValueError("Recommender: fold-in tables of %d items x d = %d beside E_i %s" % (fold_in.n_items, fold_in.d, tuple(self.E_i.shape)))
+        self.fold_in, self.iu = fold_in, iu
         self._filters = {}                                         # flag bytes -> ops.ItemFilter
 
     @classmethod
-    def from_trainer(cls, trainer) -> "Recommender":
+    def from_trainer(cls, trainer, fold_in: bool = False) -> "Recommender":
         """The embeddings Trainer.test would rank by now: FusedStep.forward() on the fused routes, the model's no-grad forward in eval mode
         on the per-op path; the train CSR of the drop-in's data_generator.device_state. On a masking route (--mask / --mask_rate > 0) this
-        forward is ONE MASKING ROUND, as every evaluation is: it advances the step's round counter."""
+        forward is ONE MASKING ROUND, as every evaluation is: it advances the step's round counter.
+        fold_in: also build the item-side tables of recommend_new / embed_new from the model's parameters (ops.FoldInTables.from_model:
+        on either route, nothing is read from the fused step's buffers) and keep the item-side CSR and the rates. A masking
+        configuration is refused: its features are redrawn every forward, and there is no one item side to hold fixed."""
+        module = sys.modules[type(trainer).__module__]
+        if fold_in and (module.args.mask or module.args.mask_rate != 0):
+            raise RuntimeError("Recommender: fold_in is refused under --mask / --mask_rate != 0 (every forward is a masking round)")
         if trainer.model_mm.training:
             trainer.model_mm.eval()
         fused = trainer._fused_step()
@@ -147,14 +202,18 @@ class Recommender:
             else:
                 E_u, E_i, *_ = trainer.model_mm(trainer.ui_graph, trainer.iu_graph, trainer.image_ui_graph, trainer.image_iu_graph,
                                                 trainer.text_ui_graph, trainer.text_iu_graph)
-        data_generator = sys.modules[type(trainer).__module__].data_generator
-        return cls(E_u, E_i, data_generator.device_state(E_u.device)["train"])
+        tables = iu = None
+        if fold_in:
+            a = module.args
+            tables = ops.FoldInTables.from_model(trainer.model_mm, trainer.ui_graph, trainer.iu_graph, (a.model_cat_rate, a.user_cat_rate, a.item_cat_rate))
+            iu = ops.operand_from_sparse_tensor(trainer.iu_graph).fwd
+        return cls(E_u, E_i, module.data_generator.device_state(E_u.device)["train"], tables, iu)
 
     @classmethod
-    def from_checkpoint(cls, trainer, path: str) -> "Recommender":
+    def from_checkpoint(cls, trainer, path: str, fold_in: bool = False) -> "Recommender":
         """trainer.load_checkpoint(path) (a file of another configuration fails its fingerprint check), then from_trainer."""
         trainer.load_checkpoint(path)
-        return cls.from_trainer(trainer)
+        return cls.from_trainer(trainer, fold_in=fold_in)
 
     def item_filter(self, flags: Optional[torch.Tensor]) -> Optional[ops.ItemFilter]:
         """The ItemFilter of a flag vector, cached on the vector's CONTENT (its bytes come to the host once per call to be compared; a new
@@ -194,6 +253,67 @@ class Recommender:
             return torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
 
         parts = [ops.score_topk_excluded(self.E_u, self.E_i, q[a:a + step], train, int(k), rows(a), filt) for a in range(0, n, max(step, 1))]
+        if not parts:
+            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
+        return idx.to(torch.int64), sc
+
+    def _tables(self) -> ops.FoldInTables:
+        if self.fold_in is None:
+            raise RuntimeError("Recommender: built without fold_in=True - Recommender.from_trainer / from_checkpoint(..., fold_in=True) "
+                               "build the item-side tables that new users are embedded from")
+        return self.fold_in
+
+    def _id_rows(self, id_rows) -> Optional[torch.Tensor]:
+        if id_rows is None:
+            return None
+        t = torch.as_tensor(id_rows).to(device=self.E_i.device, dtype=torch.float32)
+        if t.dim() != 2 or t.shape[1] != self.E_i.shape[1]:
+            raise ValueError("id_rows: [n, %d] expected, got %s" % (self.E_i.shape[1], tuple(t.shape)))
+        return t.contiguous()
+
+    def _embed(self, hist: Tuple[np.ndarray, np.ndarray], id_rows: Optional[torch.Tensor], a: int, b: int) -> torch.Tensor:
+        dev = self.E_i.device
+        rp, ci = csr_slice(hist, a, b)
+        return ops.fold_in_users(self._tables(), torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev),
+                                 id_rows=id_rows[a:b] if id_rows is not None else None)
+
+    def embed_new(self, histories, id_rows=None) -> torch.Tensor:
+        """E_new float32 [n, d]: the embeddings of n users who are not rows of the graph, from their item histories - what the trained
+        model's forward gives a user with that row of the adjacency, the item side held fixed (ops.fold_in_users). histories: any form
+        history_csr accepts (a history is a SET: order and repeats do not matter). id_rows [n, d]: the users' own id rows - a new
+        user has none: zeros (None)."""
+        self._tables()
+        ids = self._id_rows(id_rows)
+        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
+        return self._embed(hist, ids, 0, hist[0].size - 1)
+
+    def recommend_new(self, histories, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None, id_rows=None,
+                      chunk: Optional[int] = 65536):
+        """recommend() for users who are not rows of the graph: (items int64 [n, k], scores float32 [n, k]) for n item histories, the k
+        best eligible items by (score descending, item id ascending), -1 / -inf behind the last candidate, the scores the bits of
+        ops.scores(embed_new(histories, id_rows), E_i, arange(n)). exclude_history: leave out the history's own items; exclude: one more
+        list per new user, in any form exclusion_csr accepts (a dict is keyed by position here). allow_items / deny_items / chunk: as
+        for recommend. Needs fold_in=True at construction."""
+        self._tables()
+        dev = self.E_i.device
+        ids = self._id_rows(id_rows)
+        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
+        n = hist[0].size - 1
+        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
+        excl = exclusion_csr(exclude, np.arange(n), self.n_items) if exclude is not None else None
+        if exclude_history:
+            excl = csr_join(hist, excl)
+        step = n if not chunk or chunk >= n else int(chunk)
+        parts = []
+        for a in range(0, n, max(step, 1)):
+            b = min(a + step, n)
+            E_new = self._embed(hist, ids, a, b)
+            rows = None
+            if excl is not None:
+                rp, ci = csr_slice(excl, a, b)
+                rows = torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
+            parts.append(ops.score_topk_excluded(E_new, self.E_i, torch.arange(b - a, device=dev), None, int(k), rows, filt))
         if not parts:
             return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
         idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))

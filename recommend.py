@@ -1,7 +1,8 @@
 """Recommend from a checkpoint: the top-K items for a list of users, optionally among an allow-list or outside a deny-list of items.
 
-    python recommend.py --checkpoint ckpt/best.ckpt --users users.txt --topk 20 [--allow_items F | --deny_items F] [--include_seen]
-                        [--exclude F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model was trained with ...]
+    python recommend.py --checkpoint ckpt/best.ckpt (--users users.txt | --histories hist.txt) --topk 20 [--allow_items F | --deny_items F]
+                        [--include_seen] [--exclude F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model
+                        was trained with ...]
 
 The flags above are this script's own; EVERY OTHER argument goes to the drop-in's parser untouched (utility/parser.py - the
 configuration the checkpoint was written under: a checkpoint of another configuration fails its fingerprint check). The script builds
@@ -9,6 +10,10 @@ the Trainer, loads the checkpoint, recommends (llmrec_amd.serve.Recommender) and
 [n, K] (-1 behind the last candidate) and `scores` float32 [n, K]. It trains nothing. Id files are .npy (integers) or text with one id
 per line. --exclude: (user, item) pairs - a .npy integer array [m, 2] or text with one `user item` per line -, items left out for that user
 on top of the train row; a pair applies to every occurrence of its user in --users, and a user that is not listed is ignored.
+--histories (instead of --users): the users are NOT rows of the training graph - (row, item) pairs in the format of --exclude, row q the
+q-th new user (rows 0 .. the largest row listed; a row without a pair has an empty history). Each is embedded from its item history by
+the trained model with the item side held fixed (Recommender.recommend_new) and ranked as above; the history's own items are left out
+unless --include_seen; --exclude pairs are then (row, item) too; the .npz holds `rows` int64 [n] in place of `users`.
 --mask / --mask_rate != 0 are refused: with them every forward is a masking round, and a serving run must not advance one."""
 import argparse
 import importlib
@@ -23,12 +28,14 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 def own_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, allow_abbrev=False)
     p.add_argument("--checkpoint", required=True, help="a file of Trainer.save_checkpoint / LLMREC_CHECKPOINT (best.ckpt, last.ckpt)")
-    p.add_argument("--users", required=True, help="user ids: .npy or text, one id per line")
+    who = p.add_mutually_exclusive_group(required=True)
+    who.add_argument("--users", help="user ids: .npy or text, one id per line")
+    who.add_argument("--histories", help="new users as (row, item) pairs: .npy [m, 2] or text, one `row item` per line; row q is the q-th new user")
     p.add_argument("--topk", type=int, required=True, help="items per user (<= 1024)")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--allow_items", help="rank only among these item ids (.npy or text)")
     g.add_argument("--deny_items", help="rank among all but these item ids (.npy or text)")
-    p.add_argument("--include_seen", action="store_true", help="do not exclude the user's train items")
+    p.add_argument("--include_seen", action="store_true", help="do not exclude the user's train items (--histories: the history's items)")
     p.add_argument("--exclude", help="(user, item) pairs to leave out per user: .npy [m, 2] or text, one `user item` per line")
     p.add_argument("--out", required=True, help="the .npz to write")
     return p
@@ -105,7 +112,14 @@ def main(argv=None):
         sys.path.insert(0, ROOT)
     from utility.parser import parse_args
     refuse_masking(parse_args(rest))                               # (unknown flags are the drop-in parser's errors, raised here)
-    users = read_ids(own.users)
+    if own.histories:
+        pairs = read_pairs(own.histories)
+        if pairs.size and pairs[:, 0].min() < 0:
+            raise SystemExit("%s: a negative row" % own.histories)
+        users = np.arange(int(pairs[:, 0].max()) + 1 if pairs.size else 0, dtype=np.int64)
+        histories = exclusion_lists(pairs, users)
+    else:
+        users = read_ids(own.users)
     allow = read_ids(own.allow_items) if own.allow_items else None
     deny = read_ids(own.deny_items) if own.deny_items else None
     exclude = exclusion_lists(read_pairs(own.exclude), users) if own.exclude else None
@@ -113,10 +127,14 @@ def main(argv=None):
     from llmrec_amd.serve import Recommender
     m.set_seed(m.args.seed)
     trainer = m.Trainer(data_config={})
-    rec = Recommender.from_checkpoint(trainer, own.checkpoint)
-    items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
+    rec = Recommender.from_checkpoint(trainer, own.checkpoint, fold_in=bool(own.histories))
+    if own.histories:
+        histories = [histories.get(int(q), ()) for q in users]
+        items, scores = rec.recommend_new(histories, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen, exclude=exclude)
+    else:
+        items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
     out = own.out if own.out.endswith(".npz") else own.out + ".npz"
-    np.savez(out, users=users, items=items.cpu().numpy(), scores=scores.cpu().numpy())
+    np.savez(out, items=items.cpu().numpy(), scores=scores.cpu().numpy(), **{"rows" if own.histories else "users": users})
     print("recommend.py: %d users x top %d -> %s" % (len(users), own.topk, out))
 
 
