@@ -985,7 +985,7 @@ int llmrec_score_auc_f32(int32_t n_query, const int64_t* query_users,
                          void* workspace, int64_t workspace_bytes, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Serving: exact masked top-K under an item ALLOW-LIST (csrc/serve.hip). No counterpart in the reference, which ranks the whole
+ * Serving: exact masked top-K under an item ALLOW-LIST (csrc/serve.hip: the filter build and the pipeline of both scoring entries). No counterpart in the reference, which ranks the whole
  * catalogue for its test users only (utility/batch_test.py). Additive: the ABI version stays.
  * For query user u, an allow mask allow[0 .. n_items) (uint8, ANY non-zero byte = eligible) and an optional train CSR the candidates are
  *     { i : allow[i] != 0 and i not in the train row of u };
@@ -1045,7 +1045,7 @@ int llmrec_score_topk_filtered_f32(int32_t n_query, const int64_t* query_users,
                                    llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Serving with PER-QUERY exclusion lists (csrc/exclude.hip): items a user bought, saw or dismissed since the graph was built, items
+ * Serving with PER-QUERY exclusion lists (the pipeline of csrc/serve.hip with the exclusion stage of csrc/exclude.hip): items a user bought, saw or dismissed since the graph was built, items
  * already shown, the earlier pages of a result. Additive: the ABI version stays, and llmrec_score_topk_filtered_f32 is unchanged.
  *
  * llmrec_score_topk_excluded_f32: the arguments of llmrec_score_topk_wide_f32 up to train_nnz (same meaning; 1 <= d <= 128; query users may

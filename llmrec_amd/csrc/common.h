@@ -54,6 +54,19 @@ int topk_eval_sums_wide_partials(int32_t n_query, const int64_t* query_users, in
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// csrc/exclude.hip: the exclusion stage of the serving pipeline (csrc/serve.hip), on the pipeline's stream. The bytes the pipeline reserves for
+// the vendor sort of excl_nnz 64-bit keys (the bound llmrec_scatter_rows_workspace_bytes gives the same sort) ...
+static inline int64_t exclude_sort_reserve(int64_t excl_nnz) { return excl_nnz > 0 ? align_up(excl_nnz + (32ll << 20), 256) : 0; }
+// ... what the sort asks for, before the call's first launch (more than the reserve: LLMREC_EWORKSPACE in `name`'s words) ...
+int exclude_sort_need(const char* name, int32_t n_query, int64_t excl_nnz, size_t* need, hipStream_t stream);
+// ... the keys  q << 32 | id  of the exclusion rows and the checks of excl_rowptr (one launch, with an exclusion CSR), then the sort
+// (excl_nnz > 0); *sorted = the buffer that holds the rows in order, each ascending ...
+int exclude_sorted_keys(int32_t n_query, const int32_t* excl_rowptr, const int32_t* excl_colidx, int64_t excl_nnz, const int32_t* new_id, int64_t n_items,
+                        uint64_t* keys_a, uint64_t* keys_b, void* temp, size_t need, uint32_t* err, const uint64_t** sorted, hipStream_t stream);
+// ... and mask row q = the stable ascending merge of train row q (trp, tcol) and the query's keys [kbeg[q], kbeg[q + 1]) (one launch)
+int exclude_merge_rows(int32_t n_query, const int32_t* trp, const int32_t* tcol, const int32_t* kbeg, const uint64_t* sorted, const int32_t* rp,
+                       int32_t* colidx, int64_t cap, const uint32_t* err, hipStream_t stream);
+
 // grid size for a grid-stride kernel: enough blocks to fill 256 CUs x 8, never more than needed
 static inline int grid_for(int64_t work_items, int per_block, int max_blocks = 256 * 8) {
     int64_t b = ceil_div(work_items, per_block);

@@ -25,24 +25,19 @@
 // over the ranks are lane-partial + butterfly, and a block adds its 128 users in a fixed order (wave w: users 32 w .. 32 w + 31 one after the
 // other; then the four waves pairwise) into the partial layout of the one-thread kernel: llmrec_topk_eval_sums (topk.hip) launches this kernel
 // through topk_eval_sums_wide_partials and adds the partials with its own second launch.
-#include "common.h"
+#include "compact.h"
 #include <limits.h>
 
 namespace llmrec {
 
-constexpr int TW_SCAN_THREADS = 1024;
 constexpr int TW_MAX_RANK_WORDS = LLMREC_TOPK_WIDE_MAX / 64;      // 16 ranks per lane
 
-// block = 256 >> shift queries x (1 << shift) columns (the power of two >= d4): no division per element
+// gather_user_rows (compact.h) + what the rounds start from: no ids emitted yet, the overflow word open
 __global__ __launch_bounds__(256) void tw_gather_kernel(int n_query, const int64_t* __restrict__ query_users, const float* __restrict__ Eu, int64_t ldu,
                                                         int d, int d4, int shift, float* __restrict__ Ug, int64_t* __restrict__ ident,
                                                         int32_t* __restrict__ cnt, uint32_t* __restrict__ ovf) {
-    const int k = threadIdx.x & ((1 << shift) - 1);
-    const int64_t q = (int64_t)blockIdx.x * (256 >> shift) + (threadIdx.x >> shift);
     if (blockIdx.x == 0 && threadIdx.x == 0) *ovf = 0u;
-    if (q >= n_query || k >= d4) return;
-    Ug[q * d4 + k] = k < d ? Eu[query_users[q] * ldu + k] : 0.0f;
-    if (k == 0) { ident[q] = q; cnt[q] = 0; }
+    gather_user_rows(n_query, query_users, Eu, ldu, d, d4, shift, Ug, ident, [=](int64_t q) { cnt[q] = 0; });
 }
 
 __device__ __forceinline__ int64_t tw_row_len(const int32_t* __restrict__ a_rowptr, const int64_t* __restrict__ a_rows, const int32_t* __restrict__ cnt, int64_t q) {
@@ -51,38 +46,19 @@ __device__ __forceinline__ int64_t tw_row_len(const int32_t* __restrict__ a_rowp
     return len;
 }
 
-// rowptr[0 .. n_query] = exclusive scan of the new row lengths. One block walks the queries in tiles of 1024, thread t on query base + t
-// (neighbouring lanes read neighbouring entries): inclusive scan inside each wave by shuffles, the 16 wave totals through LDS, a running
-// carry from tile to tile. int64 sums in a fixed order. When the total exceeds the capacity the row pointers are overwritten with zeros.
-__global__ __launch_bounds__(TW_SCAN_THREADS) void tw_rowptr_kernel(int n_query, const int32_t* __restrict__ a_rowptr, const int64_t* __restrict__ a_rows,
-                                                                    const int32_t* __restrict__ cnt, int64_t cap, int32_t* __restrict__ rowptr,
-                                                                    uint32_t* __restrict__ ovf) {
-    __shared__ int64_t wave_total[TW_SCAN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const uint32_t was_bad = *ovf;                                 // (read by every thread before the barriers below; written once, after them)
-    int64_t carry = 0;
-    for (int64_t base = 0; base < n_query; base += TW_SCAN_THREADS) {
-        const int64_t q = base + t;
-        const int64_t len = q < n_query ? tw_row_len(a_rowptr, a_rows, cnt, q) : 0;
-        int64_t incl = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int64_t up = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += up;
-        }
-        if (lane == 63) wave_total[w] = incl;
-        __syncthreads();
-        int64_t before = 0, tile = 0;
-#pragma unroll
-        for (int i = 0; i < TW_SCAN_THREADS / 64; ++i) { const int64_t x = wave_total[i]; if (i < w) before += x; tile += x; }
-        if (q < n_query) rowptr[q] = (int32_t)(carry + before + incl - len);
-        carry += tile;
-        __syncthreads();                                           // (wave_total is rewritten by the next tile)
-    }
-    const bool bad = was_bad != 0u || carry > cap;
+// rowptr[0 .. n_query] = exclusive scan of the new row lengths (block_exclusive_scan of compact.h). When the total exceeds the capacity the
+// row pointers are overwritten with zeros.
+__global__ __launch_bounds__(SCAN_THREADS) void tw_rowptr_kernel(int n_query, const int32_t* __restrict__ a_rowptr, const int64_t* __restrict__ a_rows,
+                                                                 const int32_t* __restrict__ cnt, int64_t cap, int32_t* __restrict__ rowptr,
+                                                                 uint32_t* __restrict__ ovf) {
+    const int t = threadIdx.x;
+    const uint32_t was_bad = *ovf;                                 // (read by every thread before the scan's barriers; written once, after them)
+    const int64_t total = block_exclusive_scan<SCAN_THREADS>(
+        n_query, [=](int64_t q) { return tw_row_len(a_rowptr, a_rows, cnt, q); }, [=](int64_t q, int64_t at) { rowptr[q] = (int32_t)at; });
+    const bool bad = was_bad != 0u || total > cap;
     if (bad)
-        for (int64_t q = t; q < n_query; q += TW_SCAN_THREADS) rowptr[q] = 0;
-    if (t == 0) { rowptr[n_query] = bad ? 0 : (int32_t)carry; *ovf = bad ? 1u : 0u; }
+        for (int64_t q = t; q < n_query; q += SCAN_THREADS) rowptr[q] = 0;
+    if (t == 0) { rowptr[n_query] = bad ? 0 : (int32_t)total; *ovf = bad ? 1u : 0u; }
 }
 
 __global__ __launch_bounds__(256) void tw_merge_kernel(int n_query, const int32_t* __restrict__ a_rowptr, const int32_t* __restrict__ a_colidx,
@@ -326,8 +302,7 @@ int llmrec_score_topk_wide_f32(int32_t n_query, const int64_t* query_users,
     const int c = mode == LLMREC_TOPK_MODE_PREFILTER ? LLMREC_TOPK_PREFILTER_MAX_K : LLMREC_TOPK_MAX;
     const int wave_grid = (int)ceil_div(n_query, 4);
 
-    int shift = 2;
-    while ((1 << shift) < d4) ++shift;
+    const int shift = gather_shift(d4);
     LLMREC_CHECK_ARG(shift <= 8, "score_topk_wide: d = %d > 256", d);
     tw_gather_kernel<<<(unsigned)ceil_div(n_query, 256 >> shift), 256, 0, stream>>>(n_query, query_users, Eu, ldu, d, d4, shift, Ug, ident, cnt, ovf);
     LLMREC_LAUNCH_CHECK();
@@ -338,7 +313,7 @@ int llmrec_score_topk_wide_f32(int32_t n_query, const int64_t* query_users,
         const int32_t* a_rowptr = p == 0 ? train_rowptr : rp[(p - 1) & 1];
         const int32_t* a_colidx = p == 0 ? train_colidx : ci[(p - 1) & 1];
         const int64_t* a_rows = p == 0 ? query_users : nullptr;
-        tw_rowptr_kernel<<<1, TW_SCAN_THREADS, 0, stream>>>(n_query, a_rowptr, a_rows, cnt, train_nnz + (int64_t)n_query * col, rp[p & 1], ovf);   // (pass 0: the train rows alone against train_nnz)
+        tw_rowptr_kernel<<<1, SCAN_THREADS, 0, stream>>>(n_query, a_rowptr, a_rows, cnt, train_nnz + (int64_t)n_query * col, rp[p & 1], ovf);   // (pass 0: the train rows alone against train_nnz)
         LLMREC_LAUNCH_CHECK();
         tw_merge_kernel<<<wave_grid, 256, 0, stream>>>(n_query, a_rowptr, a_colidx, a_rows, tmp_idx, p == 0 ? 0 : c, rp[p & 1], ci[p & 1], cap, ovf);
         LLMREC_LAUNCH_CHECK();

@@ -1390,6 +1390,36 @@ def topk_filtered_workspace(n_query: int, n_items: int, n_kept: int, device, d: 
     return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
 
 
+def _score_topk_served(name: str, Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=None):
+    """What score_topk_filtered and score_topk_excluded share: row-major tables, the query list, the K and filter-size checks, the outputs,
+    train_nnz, the workspace and the filter's pointer triple around llmrec_<name>_f32. exclude: the checked (rowptr, colidx) of the
+    excluded entry, whose three arguments go between train_nnz and the maps."""
+    _need_gpu(Eu, Ei, query_users)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+        raise RuntimeError("%s: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (name, K, CONST["LLMREC_TOPK_WIDE_MAX"]))
+    if filt is not None and filt.n_items != I:
+        raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
+    kept = filt.n_kept if filt is not None else I
+    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
+    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
+    excl = ()
+    if exclude is not None:
+        excl_nnz = exclude[1].numel()
+        excl = (_p(exclude[0]), _p(exclude[1]) if excl_nnz else None, excl_nnz)
+    if ws is None:
+        ws = (topk_filtered_workspace(n, I, kept, Eu.device, d, K, nnz) if exclude is None else
+              topk_excluded_workspace(n, I, kept, Eu.device, d, K, nnz, excl_nnz))
+    maps = (_p(filt.new_id), _p(filt.old_id), _p(filt.n_kept_dev)) if filt is not None else (None, None, None)
+    _lib.call("llmrec_%s_f32" % name, n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
+              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz, *excl, *maps, kept, _stream())
+    return idx, sc
+
+
 def score_topk_filtered(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, filt: Optional[ItemFilter], mode=None,
                         train_nnz: Optional[int] = None, ws: Optional[torch.Tensor] = None):
     """score_topk among the items an ItemFilter keeps: (idx int32 [n, K] in ORIGINAL item ids, -1 = none, scores) - for every listed user the
@@ -1401,25 +1431,7 @@ def score_topk_filtered(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr],
     of topk_filtered_workspace, the call is capturable."""
     if filt is None:
         return score_topk(Eu, Ei, query_users, train, K, mode=mode, train_nnz=train_nnz)
-    _need_gpu(Eu, Ei, query_users)
-    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
-    q = query_users.to(torch.int64).contiguous()
-    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
-    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
-        raise RuntimeError("score_topk_filtered: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (K, CONST["LLMREC_TOPK_WIDE_MAX"]))
-    if filt.n_items != I:
-        raise RuntimeError("score_topk_filtered: the filter covers %d items, the table has %d" % (filt.n_items, I))
-    kept = filt.n_kept
-    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
-    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
-    nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
-    if ws is None:
-        ws = topk_filtered_workspace(n, I, kept, Eu.device, d, K, nnz)
-    _lib.call("llmrec_score_topk_filtered_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-              K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz,
-              _p(filt.new_id), _p(filt.old_id), _p(filt.n_kept_dev), kept, _stream())
-    return idx, sc
+    return _score_topk_served("score_topk_filtered", Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws)
 
 
 def topk_excluded_workspace(n_query: int, n_items: int, n_kept: int, device, d: int = 64, K: int = 50, train_nnz: int = 0,
@@ -1446,31 +1458,12 @@ def score_topk_excluded(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr],
         return score_topk_filtered(Eu, Ei, query_users, train, K, filt, mode=mode, train_nnz=train_nnz, ws=ws)
     rowptr, colidx = exclude
     _need_gpu(Eu, Ei, query_users, rowptr, colidx)
-    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
-    q = query_users.to(torch.int64).contiguous()
-    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
-    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
-        raise RuntimeError("score_topk_excluded: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (K, CONST["LLMREC_TOPK_WIDE_MAX"]))
-    if filt is not None and filt.n_items != I:
-        raise RuntimeError("score_topk_excluded: the filter covers %d items, the table has %d" % (filt.n_items, I))
+    n = query_users.numel()
     if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() != n + 1:
         raise RuntimeError("score_topk_excluded: exclude = (rowptr int32 [%d], colidx int32 [nnz]) expected, got %s %s and %s %s"
                            % (n + 1, rowptr.dtype, tuple(rowptr.shape), colidx.dtype, tuple(colidx.shape)))
     rowptr, colidx = rowptr.contiguous(), colidx.contiguous()
-    kept = filt.n_kept if filt is not None else I
-    excl_nnz = colidx.numel()
-    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
-    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
-    nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
-    if ws is None:
-        ws = topk_excluded_workspace(n, I, kept, Eu.device, d, K, nnz, excl_nnz)
-    _lib.call("llmrec_score_topk_excluded_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-              K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz,
-              _p(rowptr), _p(colidx) if excl_nnz else None, excl_nnz,
-              _p(filt.new_id) if filt is not None else None, _p(filt.old_id) if filt is not None else None,
-              _p(filt.n_kept_dev) if filt is not None else None, kept, _stream())
-    return idx, sc
+    return _score_topk_served("score_topk_excluded", Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=(rowptr, colidx))
 
 
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:

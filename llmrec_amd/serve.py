@@ -8,7 +8,7 @@ Recommender holds the two embedding tables Trainer.test ranks by and the train C
 masked top-K - or, under an allow / deny list, ops.score_topk_filtered: the eligible rows as a dense table, the same sweeps over it, the
 ids mapped back (csrc/serve.hip). `exclude` adds one exclusion list PER LISTED USER - what the user bought, saw or dismissed since the graph
 was built, what this session has shown, the earlier pages of a result: ops.score_topk_excluded sorts the lists on the device and merges
-them with the train rows into the mask the same sweeps read (csrc/exclude.hip). The lists are exact: for every listed user the first k of
+them with the train rows into the mask the same sweeps read (the same pipeline of csrc/serve.hip, with the exclusion stage of csrc/exclude.hip). The lists are exact: for every listed user the first k of
 {eligible items, minus the user's train row with exclude_seen, minus the user's exclusion list} by (score descending, item id ascending),
 the scores the bits of ops.scores.
 

@@ -138,8 +138,8 @@ def test_argument_checks_run_without_a_device():
 @needs_hipcc
 def test_no_kernel_of_serve_hip_uses_scratch():
     res = resource_usage("serve.hip")
-    names = ("if_count_kernel", "if_scan_kernel", "if_write_kernel", "sf_gather_users_kernel", "sf_gather_items_kernel", "sf_count_kernel",
-             "sf_rowptr_kernel", "sf_mask_kernel", "sf_map_back_kernel", "sf_fill_empty_kernel")
+    names = ("if_count_kernel", "if_scan_kernel", "if_write_kernel", "sv_users_kernel", "sv_items_kernel", "sv_count_kernel", "sv_rowptr_kernel",
+             "sv_train_rows_kernel", "sv_finish_kernel")
     for name in names:
         assert [k for k in res if name in k], name
     assert len(res) == len(names)

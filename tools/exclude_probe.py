@@ -1,5 +1,5 @@
-"""Times ops.score_topk_excluded (csrc/exclude.hip) against the same call without exclusion lists, unfiltered and under a filter that
-keeps a tenth of the items.
+"""Times ops.score_topk_excluded (the serving pipeline of csrc/serve.hip with the exclusion stage of csrc/exclude.hip) against the same
+call without exclusion lists, unfiltered and under a filter that keeps a tenth of the items.
 
     python tools/exclude_probe.py [--big] [--reps 60] [--out FILE.json]
 

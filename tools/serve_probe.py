@@ -1,4 +1,5 @@
-"""Times ops.score_topk against ops.score_topk_filtered (csrc/serve.hip) at several allow fractions, and the filter build alone.
+"""Times ops.score_topk against ops.score_topk_filtered (the serving pipeline of csrc/serve.hip, without its exclusion stage) at several
+allow fractions, and the filter build alone.
 
     python tools/serve_probe.py [--big] [--reps 60] [--out FILE.json]
 
