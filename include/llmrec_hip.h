@@ -1109,6 +1109,57 @@ int llmrec_score_topk_excluded_f32(int32_t n_query, const int64_t* query_users,
                                    llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Serving with PER-QUERY candidate lists (csrc/candidates.hip): "here are this request's candidates; rank them for this user" - the output
+ * of a retrieval stage, a campaign's items, a shop's shelf. Only the listed pairs are scored; the sweeps are not involved. Additive: the
+ * ABI version stays, and no other prototype changes.
+ *
+ * llmrec_score_topk_candidates_f32: query users (unsorted, repeats allowed), the two tables (1 <= d <= 128, any ld >= d, any 4-byte-aligned
+ *   base: nothing outside [row, row + d) is read on any layout), the train CSR or NULL, K >= 1 with n_query * K < 2^31 (NO 1024 cap: nothing
+ *   here is sized by K except the final write), a candidate CSR and an optional exclusion CSR over the QUERIES of this call, and new_id of
+ *   an item filter or NULL (only new_id is read; nothing is compacted and no id is mapped back).
+ *   Result: for query q with user u = query_users[q], the ids of candidate row q taken as a SET (repeats collapse; an id < 0, >= n_items
+ *   or with new_id[id] < 0 is ignored) minus { train row of u } minus { exclusion row q }; the first K of what remains by
+ *   (score desc, ORIGINAL item id asc), the scores the bits of llmrec_scores_f32, -1 / -inf behind the last candidate. The result does not
+ *   depend on the order of a candidate row's entries or on their repeats, bit for bit.
+ *   The candidate CSR: cand_rowptr [n_query + 1], cand_colidx [cand_nnz], int32, on the device; row q belongs to QUERY q, not to a user: a
+ *     user listed twice may carry two different rows. cand_nnz is the EXACT entry count, cand_rowptr[n_query].
+ *   The exclusion CSR: the row rules of llmrec_score_topk_excluded_f32 (unsorted, repeats, padding; excl_rowptr == NULL with excl_nnz == 0:
+ *     none). The train rows: ascending, duplicates allowed, as llmrec_csr_build leaves them.
+ *   On the caller's one stream: (a) the error word is opened; (b) entry e of candidate row q (q by binary search in cand_rowptr) -> the
+ *     64-bit key q << 32 | original id, a dropped entry -> n_query << 32, behind every row; the same launch checks cand_rowptr; (c) one radix
+ *     sort of the keys (the vendor sort, between two buffers of the workspace, bits [0, 32 + bits of n_query)): rows in order, each
+ *     ascending by id, repeats adjacent; (d) with an exclusion CSR, the keys kernel and the sort of the excluded call, identity numbering;
+ *     (e) the score kernel: sorted key e is dropped if it equals key e - 1, is the dropped key, has its id in the train row of its user or
+ *     has its key among the sorted exclusion keys (binary searches); otherwise its score is the k-ordered fp32 fma chain of
+ *     llmrec_scores_f32 (for c, for s in 0..3, for q4 in 0..3: k = 16 c + 4 q4 + s, k < d, acc = fmaf(u[k], i[k], acc) from acc = +0), and
+ *     the pair (q << 32 | ~m(score), id) goes out, m the order-preserving map of float bits to uint32; (f) one STABLE radix sort of the
+ *     pairs over the same bits: its input ascends by id inside a query, so equal scores stay in id order (the chain never gives -0.0: equal
+ *     floats are equal keys); (g) one wave per query: the lower bounds of q << 32 and (q + 1) << 32 in the sorted keys, the first
+ *     min(K, count) ids and the scores decoded from the keys, -1 / -inf behind them.
+ *     4 launches (5 with an exclusion CSR) + the sorts': a function of the host arguments alone; no allocation, no host read, no atomics,
+ *     every cross-block hand-over a kernel boundary: capturable and deterministic. Tables are finite by contract: the rank of a NaN score
+ *     is unspecified (nothing faults, nothing is written out of bounds).
+ *   Caller errors the DEVICE detects - every list then comes back empty (-1 / -inf) and the call returns LLMREC_OK: a cand_rowptr or an
+ *     excl_rowptr that does not start at 0, end at its nnz and never decrease.
+ *   n_query == 0: no launch. cand_nnz == 0: one launch that fills the outputs; no workspace is needed.
+ *   Bad sizes: LLMREC_EINVAL (the size function: -1), decided before any launch, as is a short workspace (LLMREC_EWORKSPACE).
+ *   Workspace (16-byte aligned): llmrec_score_topk_candidates_workspace_bytes = 0 for n_query == 0 or cand_nnz == 0, else, with A(x) = x
+ *     rounded up to 256,
+ *       256 + 2 A(8 cand_nnz) + 2 A(4 cand_nnz) + A(cand_nnz + 32 MiB) + 2 A(8 excl_nnz) + [excl_nnz > 0: A(excl_nnz + 32 MiB)]
+ *     (error word; two key buffers and two id buffers; the temporary storage of the two candidate sorts, the bound of the excluded call - a
+ *     sort that asks for more is LLMREC_EWORKSPACE before the first launch; the exclusion stage's two key buffers and its reserve). The
+ *     per-query bounds live in registers of the last launch: no buffer.
+ * ------------------------------------------------------------------------------------------ */
+int64_t llmrec_score_topk_candidates_workspace_bytes(int32_t n_query, int32_t K, int64_t cand_nnz, int64_t excl_nnz);
+int llmrec_score_topk_candidates_f32(int32_t n_query, const int64_t* query_users,
+                                     const float* Eu, int64_t ldu, const float* Ei, int64_t ldi, int64_t n_items, int32_t d,
+                                     const int32_t* train_rowptr, const int32_t* train_colidx,
+                                     int32_t K, int32_t* out_idx, float* out_score, void* workspace, int64_t workspace_bytes,
+                                     const int32_t* cand_rowptr /* n_query + 1 */, const int32_t* cand_colidx, int64_t cand_nnz,
+                                     const int32_t* excl_rowptr /* n_query + 1 or NULL */, const int32_t* excl_colidx, int64_t excl_nnz,
+                                     const int32_t* new_id /* NULL = no filter */, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Serving users who are NOT rows of the training graph (csrc/foldin.hip): the embedding the trained model gives a row of the
  * normalised adjacency that it has never seen, from the item-side tables alone. Additive: the ABI version stays.
  *

@@ -1,5 +1,5 @@
 // compact.h - the device pieces of the compaction layers in front of the sweeps, each defined once: topk_wide.hip (the rounds), serve.hip (the
-// serving pipeline) and exclude.hip (its exclusion stage) include it; nothing else does.
+// serving pipeline), exclude.hip (its exclusion stage) and candidates.hip (the candidate lists: swept_id) include it; nothing else does.
 #pragma once
 #include "common.h"
 

@@ -1466,6 +1466,54 @@ def score_topk_excluded(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr],
     return _score_topk_served("score_topk_excluded", Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=(rowptr, colidx))
 
 
+def _query_csr(name: str, what: str, csr, n: int):
+    """A checked (rowptr int32 [n + 1], colidx int32) device CSR over the n queries of a call."""
+    rowptr, colidx = csr
+    _need_gpu(rowptr, colidx)
+    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() != n + 1:
+        raise RuntimeError("%s: %s = (rowptr int32 [%d], colidx int32 [nnz]) expected, got %s %s and %s %s"
+                           % (name, what, n + 1, rowptr.dtype, tuple(rowptr.shape), colidx.dtype, tuple(colidx.shape)))
+    return rowptr.contiguous(), colidx.contiguous()
+
+
+def score_topk_candidates_workspace(n_query: int, K: int, cand_nnz: int, excl_nnz: int = 0, device="cuda") -> torch.Tensor:
+    """Scratch for llmrec_score_topk_candidates_f32 (include/llmrec_hip.h gives the formula)."""
+    nbytes = _lib.query("llmrec_score_topk_candidates_workspace_bytes", n_query, K, cand_nnz, excl_nnz)
+    if nbytes < 0:
+        raise RuntimeError("score_topk_candidates_workspace: bad sizes (K >= 1, n_query * K < 2^31, cand_nnz and excl_nnz in [0, 2^31))")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def score_topk_candidates(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, candidates, exclude=None,
+                          filt: Optional[ItemFilter] = None, ws: Optional[torch.Tensor] = None):
+    """Exact top-K among PER-QUERY candidate lists: (idx int32 [n, K] in item ids, -1 = none, scores float32 [n, K]) - for query q the first
+    K of {ids of candidate row q, as a set} minus {train row of its user} minus {exclusion row q} by (score desc, item id asc), the score
+    bits of ops.scores (llmrec_score_topk_candidates_f32, csrc/candidates.hip: only the listed pairs are scored, two radix sorts select).
+    candidates / exclude: (rowptr int32 [n + 1], colidx int32) on the device, CSRs over the QUERIES of this call - a user listed twice may
+    carry two rows; entries in any order, repeats allowed, entries < 0 or >= n_items ignored, as are items a filter does not keep (only
+    filt.new_id is read). colidx.numel() must be rowptr[n] (the device checks it; a mismatch returns empty lists). Any K >= 1 with
+    n * K < 2^31. Nothing is read back: with a workspace `ws` of score_topk_candidates_workspace the call is capturable."""
+    name = "score_topk_candidates"
+    _need_gpu(Eu, Ei, query_users)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    if filt is not None and filt.n_items != I:
+        raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
+    crp, cci = _query_csr(name, "candidates", candidates, n)
+    erp, eci = _query_csr(name, "exclude", exclude, n) if exclude is not None else (None, None)
+    cand_nnz, excl_nnz = cci.numel(), eci.numel() if eci is not None else 0
+    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
+    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    if ws is None:
+        ws = score_topk_candidates_workspace(n, K, cand_nnz, excl_nnz, Eu.device)
+    _lib.call("llmrec_score_topk_candidates_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
+              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), _p(crp), _p(cci) if cand_nnz else None, cand_nnz,
+              _p(erp), _p(eci) if excl_nnz else None, excl_nnz, _p(filt.new_id) if filt is not None else None, _stream())
+    return idx, sc
+
+
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage-1 candidate export: the top-k item ids per user WITHOUT masking, i.e. what the reference
     README's `torch.topk(user_emb @ item_emb.T, k=10)` snippet (README.md:243-247) produces for

@@ -16,8 +16,13 @@ Users who are not rows of the graph (fold_in=True at construction): rec.recommen
 each item history with the trained model, the item side held fixed (ops.FoldInTables / ops.fold_in_users, csrc/foldin.hip), and rank
 the new rows by the same exact top-K, the history's own items excluded.
 
-Not covered: fold-in moves no item embedding and adds no user to the graph; dp.py and the sharded evaluations take neither a filter nor exclusion lists, and the allow-list is one
-item set for all users of a call."""
+Per-request candidate lists - the output of a retrieval stage, a campaign's items, a shop's shelf: rec.rank(users, candidates, 20) /
+rec.rank_new(histories, candidates, 20) return the k best of each user's OWN list by the same order and the same score bits
+(ops.score_topk_candidates, csrc/candidates.hip: only the listed pairs are scored, two radix sorts select; no sweep of the catalogue). A
+list is a set; allow / deny lists, the train row and `exclude` remove from it as they do for recommend().
+
+Not covered: fold-in moves no item embedding and adds no user to the graph; dp.py and the sharded evaluations take
+neither a filter nor exclusion or candidate lists; recommend()'s allow-list is one item set for all users of a call (per-user sets: rank)."""
 from __future__ import annotations
 
 import sys
@@ -257,6 +262,65 @@ class Recommender:
             return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
         idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
         return idx.to(torch.int64), sc
+
+    def _rank_chunks(self, n: int, k: int, chunk, cand, excl, filt, call):
+        """What rank and rank_new share: the chunks of n queries, the candidate and exclusion CSRs sliced per chunk and sent to the device;
+        call(a, b, candidates, exclude, filt) ranks queries [a, b)."""
+        dev = self.E_i.device
+        step = n if not chunk or chunk >= n else int(chunk)
+
+        def rows(csr, a, b):
+            if csr is None:
+                return None
+            rp, ci = csr_slice(csr, a, b)
+            return torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
+
+        parts = [call(a, min(a + step, n), rows(cand, a, min(a + step, n)), rows(excl, a, min(a + step, n)), filt) for a in range(0, n, max(step, 1))]
+        if not parts:
+            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
+        return idx.to(torch.int64), sc
+
+    def rank(self, users, candidates, k: int, allow_items=None, deny_items=None, exclude_seen: bool = True, exclude=None,
+             chunk: Optional[int] = 65536):
+        """(items int64 [n, k], scores float32 [n, k]) for the listed users (any order, repeats allowed): the k best of each user's OWN
+        candidate list, -1 / -inf behind the last candidate (ops.score_topk_candidates: only the listed pairs are scored). candidates: one
+        id list per listed user, in any form exclusion_csr accepts - a dict user id -> ids (a listed user without a key has an empty
+        list: its row comes back all -1), a (rowptr, colidx) tuple, an [n, m] array or tensor with -1 padding, a sequence of n id
+        sequences; a list is a SET: order and repeats do not matter, bit for bit. allow_items / deny_items / exclude_seen / exclude /
+        chunk: as for recommend (an ineligible, seen or excluded candidate is left out). Any k >= 1."""
+        dev = self.E_u.device
+        q = _ids(users, "users", self.n_users, dev)
+        host_users = q.cpu().numpy()
+        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
+        train = self.train if exclude_seen else None
+        if candidates is None:
+            raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
+        cand = exclusion_csr(candidates, host_users, self.n_items, what="candidates")
+        excl = exclusion_csr(exclude, host_users, self.n_items) if exclude is not None else None
+        return self._rank_chunks(q.numel(), int(k), chunk, cand, excl, filt,
+                                 lambda a, b, c, e, f: ops.score_topk_candidates(self.E_u, self.E_i, q[a:b], train, int(k), c, e, f))
+
+    def rank_new(self, histories, candidates, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None,
+                 id_rows=None, chunk: Optional[int] = 65536):
+        """rank() for users who are not rows of the graph, as recommend_new is to recommend: n item histories, one candidate list per new
+        user (a dict is keyed by position here), the scores the bits of ops.scores(embed_new(histories, id_rows), E_i, arange(n)).
+        exclude_history: leave out the history's own items. Needs fold_in=True at construction."""
+        self._tables()
+        dev = self.E_i.device
+        ids = self._id_rows(id_rows)
+        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
+        n = hist[0].size - 1
+        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
+        if candidates is None:
+            raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
+        cand = exclusion_csr(candidates, np.arange(n), self.n_items, what="candidates")
+        excl = exclusion_csr(exclude, np.arange(n), self.n_items) if exclude is not None else None
+        if exclude_history:
+            excl = csr_join(hist, excl)
+        return self._rank_chunks(n, int(k), chunk, cand, excl, filt,
+                                 lambda a, b, c, e, f: ops.score_topk_candidates(self._embed(hist, ids, a, b), self.E_i, torch.arange(b - a, device=dev),
+                                                                                 None, int(k), c, e, f))
 
     def _tables(self) -> ops.FoldInTables:
         if self.fold_in is None:

@@ -1,7 +1,7 @@
 """Recommend from a checkpoint: the top-K items for a list of users, optionally among an allow-list or outside a deny-list of items.
 
     python recommend.py --checkpoint ckpt/best.ckpt (--users users.txt | --histories hist.txt) --topk 20 [--allow_items F | --deny_items F]
-                        [--include_seen] [--exclude F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model
+                        [--include_seen] [--exclude F] [--candidates F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model
                         was trained with ...]
 
 The flags above are this script's own; EVERY OTHER argument goes to the drop-in's parser untouched (utility/parser.py - the
@@ -14,6 +14,8 @@ on top of the train row; a pair applies to every occurrence of its user in --use
 q-th new user (rows 0 .. the largest row listed; a row without a pair has an empty history). Each is embedded from its item history by
 the trained model with the item side held fixed (Recommender.recommend_new) and ranked as above; the history's own items are left out
 unless --include_seen; --exclude pairs are then (row, item) too; the .npz holds `rows` int64 [n] in place of `users`.
+--candidates: (user, item) pairs in the format of --exclude, (row, item) with --histories - each user's OWN candidate list: the script then
+ranks only those items per user (Recommender.rank / rank_new; a user without a pair gets an empty list), and --topk has no 1024 cap.
 --mask / --mask_rate != 0 are refused: with them every forward is a masking round, and a serving run must not advance one."""
 import argparse
 import importlib
@@ -37,6 +39,7 @@ def own_parser() -> argparse.ArgumentParser:
     g.add_argument("--deny_items", help="rank among all but these item ids (.npy or text)")
     p.add_argument("--include_seen", action="store_true", help="do not exclude the user's train items (--histories: the history's items)")
     p.add_argument("--exclude", help="(user, item) pairs to leave out per user: .npy [m, 2] or text, one `user item` per line")
+    p.add_argument("--candidates", help="(user, item) pairs: rank only each user's own candidates; .npy [m, 2] or text, one `user item` per line")
     p.add_argument("--out", required=True, help="the .npz to write")
     return p
 
@@ -123,6 +126,7 @@ def main(argv=None):
     allow = read_ids(own.allow_items) if own.allow_items else None
     deny = read_ids(own.deny_items) if own.deny_items else None
     exclude = exclusion_lists(read_pairs(own.exclude), users) if own.exclude else None
+    candidates = exclusion_lists(read_pairs(own.candidates), users) if own.candidates else None
     m = load_dropin(rest)
     from llmrec_amd.serve import Recommender
     m.set_seed(m.args.seed)
@@ -130,7 +134,13 @@ def main(argv=None):
     rec = Recommender.from_checkpoint(trainer, own.checkpoint, fold_in=bool(own.histories))
     if own.histories:
         histories = [histories.get(int(q), ()) for q in users]
-        items, scores = rec.recommend_new(histories, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen, exclude=exclude)
+        if candidates is not None:
+            items, scores = rec.rank_new(histories, candidates, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen,
+                                         exclude=exclude)
+        else:
+            items, scores = rec.recommend_new(histories, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen, exclude=exclude)
+    elif candidates is not None:
+        items, scores = rec.rank(users, candidates, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
     else:
         items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
     out = own.out if own.out.endswith(".npz") else own.out + ".npz"
