@@ -889,10 +889,16 @@ int llmrec_score_topk_ws_f32(int32_t n_query, const int64_t* query_users,
 /* The same call with the sweep's arithmetic chosen explicitly (round 5). Lists and scores are BIT-IDENTICAL in both modes:
  *   LLMREC_TOPK_MODE_EXACT_SWEEP  every score by the exact-fp32 MFMA chain (what llmrec_score_topk_ws_f32 runs);
  *   LLMREC_TOPK_MODE_PREFILTER    the sweep on bf16 MFMAs (both operands as two round-to-nearest bf16 terms, three products:
- *                                 |s - s'| <= 2^-14 ||u|| ||i||) keeps each user's 64 best items by the UPPER BOUND ub = s' + 2^-14 ||u|| ||i||;
+ *                                 |s - s'| <= c ||u|| ||i||, c = 2^-14 for d <= 64 and 2^-13 above) keeps each user's 64 best items by the
+ *                                 UPPER BOUND ub = s' + c ||u|| ||i||;
  *                                 those 64 are then scored with the exact fp32 fma chain, re-ranked, and VERIFIED: (64th ub) < (K-th exact
  *                                 score) proves that no other item can be in the top K. User tiles that fail the proof are swept again by the
- *                                 exact kernel (second launch; the other tiles' blocks exit at once). Needs the workspace;
+ *                                 exact kernel (second launch; the other tiles' blocks exit at once).
+ *                                 MAGNITUDES: the guarantee holds for every finite table. The bound's own fp32 arithmetic is trusted for rows
+ *                                 with 2^-44 <= ||x|| <= 2^44 and for all-zero rows; an item row outside that window has the bound +inf
+ *                                 (always kept and scored exactly), a user row outside it sends its tile to the exact sweep. Tables whose
+ *                                 scores are normal fp32 numbers get the exact sweep's bits in both modes at any scale; only the
+ *                                 mode's speed belongs to the window. Needs the workspace;
  *                                 K <= LLMREC_TOPK_PREFILTER_MAX_K (else the exact sweep runs). llmrec_score_topk_stats_offset: byte offset inside
  *                                 the workspace of three uint32 words the mode leaves behind - [0] = the drains of the sweep's candidate
  *                                 pools, summed over its blocks (round 6), [1] = the number of user tiles the exact sweep had to redo, [2] = the

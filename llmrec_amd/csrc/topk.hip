@@ -54,7 +54,7 @@ struct TopkArgs {
     int mode;
     uint4* pk2;
     uint32_t* hdr;               // [1] user tiles flagged for the exact sweep (statistics)
-    float* cn;                   // per item: 2^-14 ||item|| rounded up (the item's factor of the score's upper bound)
+    float* cn;                   // per item: tk_pre_slack(d) ||item|| rounded up (the item's factor of the score's upper bound; +inf outside the magnitude window)
     uint32_t* fb_word;           // one word per user tile: != 0 = the verification failed, the exact sweep redoes the tile
     const uint32_t* only_flagged; // exact sweep: blocks of tiles whose word is 0 exit at once (NULL: every tile)
     // users with long train rows: a block builds bitmaps (one word per item tile) of up to TK_HEAVY_PER_BLOCK of its users in its own
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(256, (DK <= 4 ? 4 : 2)) void score_topk_kernel(Topk
 // round-to-nearest splits: |r| <= 2^-16 |x|):
 //     s' = <u_h, i_h> + <u_h, i_m> + <u_m, i_h>          (three MFMAs per 32 k: 192 matrix cycles per 16 x 32 tile at d = 64)
 //     s - s' = <u_h, i_r> + <u_m, i_m> + <u_m, i_r> + <u_r, i>   =>   |s - s'| <= (3.02 x 2^-16 + fp32 accumulation of 192 terms) sum_k |u_k| |i_k|
-//                                                                            <=  2^-14 ||u|| ||i||                     (Cauchy-Schwarz)
+//                                                                            <=  2^-14 ||u|| ||i||                     (Cauchy-Schwarz; 2^-13 beyond d = 64: tk_pre_slack)
 // so  ub(u, i) := s' + 2^-14 ||u|| ||i||  is an UPPER BOUND of the exact score, item by item (a cold item with a tiny embedding gets a tiny
 // slack: thousands of near-identical cold rows do not blur the boundary the way one max-norm slack for all items did - the first form of the
 // verification sent 34 % of the Netflix-shaped bench's user tiles to the exact sweep for exactly that reason).
@@ -614,6 +614,26 @@ __device__ __forceinline__ void tk_split8(const float (&x)[8], uint4& H, uint4& 
 // bound doubles there (the d = 64 constant was used for every d).
 __device__ __host__ __forceinline__ float tk_pre_slack(int d) { return d <= 64 ? 0x1p-14f : 0x1p-13f; }
 constexpr float TK_NORM_UP = 1.0f + 0x1p-10f;
+// THE MAGNITUDE WINDOW. The bound above is a statement about real numbers; its fp32 arithmetic holds while the squares of the norms neither
+// underflow nor overflow. Below |x| ~ 2^-75 every x^2 is 0 in fp32: the norm is 0, the slack term vanishes and ub = s' - while the scores
+// against users of ordinary size are perfectly normal floats (tests/test_gpu_topk_bound.py: a proven list that misses an item of the true
+// top K). So the bound is TRUSTED only for rows with 2^-44 <= ||x|| <= 2^44 (squared sums inside [TK_SS_MIN, TK_SS_MAX]) and for all-zero rows:
+//   - inside the window the squares that are lost (|x_k| < 2^-63) are below 2^-31 of the sum, far inside TK_NORM_UP; whatever a bf16 part, a product
+//     or a partial sum loses to underflow or to a flushed subnormal is below 2^-126 times the other operand's norm, or below 2^-117 in all
+//     3 d products - against a slack term of at least 2^-14 x 2^-44 times that norm, and of at least 2^-102; nothing overflows (|s'| < 2^94);
+//   - an ITEM outside the window gets the bound +inf (cn = +inf): always kept, scored exactly, and more than 64 - K of them fail every proof.
+//     Its elements beyond 2^44 are packed as zeros, so that s' stays finite and ub = +inf, never inf - inf;
+//   - a USER outside the window (all-zero rows included: 0 x inf has no sign, and such a row's proof fails on its ties anyway) flags its tile
+//     for the exact sweep at the start of the bf16 sweep.
+// Nothing changes inside the window: the same sums, the same bounds, the same proofs.
+constexpr float TK_SS_MIN = 0x1p-88f, TK_SS_MAX = 0x1p88f, TK_ELEM_MAX = 0x1p44f;
+// one step of a row's sum of squares. A square that underflows still counts (as the smallest normal float): only an all-zero row sums to 0
+__device__ __forceinline__ float tk_sq_step(float x, float ss) { return fmaxf(fmaf(x, x, ss), x != 0.f ? 0x1p-126f : 0.f); }
+// cn of an item from its sum of squares: slack ||i|| rounded up, +inf outside the window
+__device__ __forceinline__ float tk_item_cn(float ss, int d) {
+    const bool trusted = ss == 0.f || (ss >= TK_SS_MIN && ss <= TK_SS_MAX);                         // (NaN: not trusted)
+    return trusted ? tk_pre_slack(d) * (sqrtf(ss) * TK_NORM_UP) : INFINITY;
+}
 
 // workspace header of the mode (first 256 bytes of the fragment area): [0] drains of the bf16 sweep (all blocks), [1] user tiles flagged for the exact sweep, [2] train rows swept as bitmaps
 // the item table as bf16 (hi, mid) MFMA fragments: pk2[(((tile * 2 + n) * DK32 + c) * 2 + hm) * 64 + lane], lane = 16 (k group) + item-in-tile;
@@ -633,11 +653,13 @@ __global__ __launch_bounds__(256) void topk_pack_items_bf16_kernel(TopkArgs a, i
     float x[8];
     float ss = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { const int k = 8 * g + j; x[j] = k < a.d ? row[k] : 0.f; ss = fmaf(x[j], x[j], ss); }
+    for (int j = 0; j < 8; ++j) { const int k = 8 * g + j; x[j] = k < a.d ? row[k] : 0.f; ss = tk_sq_step(x[j], ss); }
     if (a.cn && (G & (G - 1)) == 0) {                                  // G = 4, 8, 16: an item's threads are G aligned neighbouring lanes - its
         for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);   // squared norm by a butterfly (fixed tree); G = 12: topk_item_norm_kernel
-        if (g == 0) a.cn[item_p] = item_p < a.n_items ? tk_pre_slack(a.d) * (sqrtf(ss) * TK_NORM_UP) : __builtin_nanf("");   // (NaN: a padded slot's bound never passes a filter)
+        if (g == 0) a.cn[item_p] = item_p < a.n_items ? tk_item_cn(ss, a.d) : __builtin_nanf("");   // (NaN: a padded slot's bound never passes a filter)
     }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = fabsf(x[j]) <= TK_ELEM_MAX ? x[j] : 0.f;   // (the row is outside the window: its bound is +inf whatever s' is)
     uint4 H, M;
     tk_split8(x, H, M);
     const int64_t tile = item_p / TK_TILE;
@@ -654,10 +676,10 @@ __global__ __launch_bounds__(256) void topk_item_norm_kernel(TopkArgs a, float* 
         float ss = 0.f;
         if (item < a.n_items) {
             const float* row = a.Ei + item * a.ldi;
-            for (int k = gl; k < a.d; k += 16) ss = fmaf(row[k], row[k], ss);
+            for (int k = gl; k < a.d; k += 16) ss = tk_sq_step(row[k], ss);
         }
         ss = group_sum<16>(ss);
-        if (gl == 0) cn[item] = item < a.n_items ? tk_pre_slack(a.d) * (sqrtf(ss) * TK_NORM_UP) : __builtin_nanf("");
+        if (gl == 0) cn[item] = item < a.n_items ? tk_item_cn(ss, a.d) : __builtin_nanf("");
     }
 }
 
@@ -794,6 +816,11 @@ __global__ __launch_bounds__(256, (DK32 <= 2 ? 4 : 2)) void score_topk_pre_kerne
     }
     un2 += __shfl_xor(un2, 16, 64); un2 += __shfl_xor(un2, 32, 64);    // ||u||^2 of row li, in every lane with that li
     const float un_row = sqrtf(un2) * TK_NORM_UP;
+    // a user row outside the magnitude window (TK_SS_MIN): its tile goes to the exact sweep (rows past n_query repeat the last user; every
+    // wave of the block - and every part of a split tile - finds the same, one lane says it)
+    if (__ballot(!(un2 >= TK_SS_MIN && un2 <= TK_SS_MAX)) != 0ull && threadIdx.x == 0) {
+        if (atomicExch(reinterpret_cast<unsigned int*>(&a.fb_word[tile]), 1u) == 0u) atomicAdd(&a.hdr[1], 1u);
+    }
     float unr[4];                                                      // ||u|| (rounded up) of the four rows this lane's accumulators belong to
 #pragma unroll
     for (int r = 0; r < 4; ++r) unr[r] = __shfl(un_row, lq * 4 + r, 64);

@@ -30,6 +30,9 @@ def main():
             shapes = ((65536, 1_000_000, 64, 50, 2), (16384, 1_000_000, 128, 50, 2)) if kind == "random" else ()
         if "--crossover" in sys.argv:                          # where does the bf16 mode stop paying? (item table: I x d x 4 bytes)
             shapes = tuple((16384, I, 64, 50, 5) for I in (10_322, 32_768, 65_536, 131_072, 262_144, 524_288, 1_000_000)) if kind == "random" else ()
+        if "--shapes" in sys.argv:                             # U,I,d,K,iters;... on random tables (A/B of two builds of the library: LLMREC_LIB)
+            spec = sys.argv[sys.argv.index("--shapes") + 1]
+            shapes = tuple(tuple(int(v) for v in s.split(",")) for s in spec.split(";")) if kind == "random" else ()
         for U, I, d, K, iters in shapes:
             Eu, Ei = tables(kind, U, I, d, g)
             q = torch.arange(U, device="cuda")
