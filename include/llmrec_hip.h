@@ -1166,6 +1166,47 @@ int llmrec_score_topk_candidates_f32(int32_t n_query, const int64_t* query_users
                                      const int32_t* new_id /* NULL = no filter */, llmrec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Candidate lists under PER-GROUP QUOTAS (csrc/quota.hip): "at most m items of any one brand, seller, category or series in a user's list".
+ * Additive: the ABI version stays, and no other prototype changes.
+ *
+ * llmrec_score_topk_candidates_capped_f32: the arguments of llmrec_score_topk_candidates_f32 with the same meaning, then
+ *   item_group int32 [n_items] on the device: item_group[i] in [0, n_groups) is the group of item i; any other value (-1, >= n_groups) means
+ *     NO GROUP, and such an item is never capped;
+ *   the cap: group_cap int32 [n_groups] on the device, one cap >= 0 per group (0 removes the group), or group_cap == NULL and one cap >= 1 for
+ *     every group (cap is not read beside a group_cap).
+ *   Result: query q's survivors are those of the uncapped call (candidate row q as a set, minus ineligible items, minus the train row, minus
+ *   exclusion row q), ranked by (score desc, ORIGINAL item id asc). The rank of a grouped item WITHIN ITS GROUP is the number of survivors
+ *   of the same query and the same group that stand before it. An item is kept if it has no group or if that rank is below its group's
+ *   cap; the list is the first K kept items, -1 / -inf behind the last one, the scores the bits of llmrec_scores_f32. This is the greedy
+ *   walk down the ranking that takes an item while its group still has room. A cap at least as large as every group's survivor count
+ *   gives the uncapped call's result, bit for bit. K <= LLMREC_TOPK_WIDE_MAX here: K sizes the group table of the last launch.
+ *   On the caller's one stream: stages (a) to (f) of llmrec_score_topk_candidates_f32 - one internal function that both entries call: the
+ *     same launches, the same buffers -, then (g') one wave per query: the query's range in the sorted keys as in (g), walked in chunks of
+ *     64 sorted entries. Per chunk a lane's rank within its group = base[g] + the earlier lanes of the chunk with the same group; a ballot
+ *     and a prefix popcount of the kept lanes give the output slot, a lane writes if its slot is below K, and the wave stops when K items
+ *     are taken or the range ends. base[g] is a per-wave hash table in LDS keyed by group id, 2^s >= 2 K slots of 8 bytes (at most 32 KiB
+ *     per block); only the first lane of a group within a chunk, and only if it is kept, adds the chunk's entries of the group to it (a
+ *     group that is not kept any more has a count >= its cap in the table, or cap 0: nothing more is asked of it), so fewer than K slots
+ *     are ever in use. Slots are claimed by integer LDS compare-and-swap; the counts read back do not depend on the table's layout.
+ *     The launch count of the uncapped call: a function of the host arguments alone; no allocation, no host read, no global atomics, no
+ *     float atomics: capturable and deterministic.
+ *   Caller errors the DEVICE detects (a broken cand_rowptr / excl_rowptr): every list comes back empty and the call returns LLMREC_OK, as
+ *     in the uncapped call. n_query == 0: no launch. cand_nnz == 0: one launch that fills the outputs; no workspace is needed.
+ *   LLMREC_EINVAL before any launch: what the uncapped call refuses, K > LLMREC_TOPK_WIDE_MAX, item_group == NULL, n_groups < 1, and
+ *     group_cap == NULL together with cap < 1. A short workspace: LLMREC_EWORKSPACE.
+ *   Workspace: llmrec_score_topk_candidates_workspace_bytes(n_query, K, cand_nnz, excl_nnz), the uncapped call's - the table lives in LDS.
+ * ------------------------------------------------------------------------------------------ */
+int llmrec_score_topk_candidates_capped_f32(int32_t n_query, const int64_t* query_users,
+                                            const float* Eu, int64_t ldu, const float* Ei, int64_t ldi, int64_t n_items, int32_t d,
+                                            const int32_t* train_rowptr, const int32_t* train_colidx,
+                                            int32_t K, int32_t* out_idx, float* out_score, void* workspace, int64_t workspace_bytes,
+                                            const int32_t* cand_rowptr /* n_query + 1 */, const int32_t* cand_colidx, int64_t cand_nnz,
+                                            const int32_t* excl_rowptr /* n_query + 1 or NULL */, const int32_t* excl_colidx, int64_t excl_nnz,
+                                            const int32_t* new_id /* NULL = no filter */,
+                                            const int32_t* item_group /* n_items */, int32_t n_groups, const int32_t* group_cap /* n_groups or NULL */,
+                                            int32_t cap, llmrec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Serving users who are NOT rows of the training graph (csrc/foldin.hip): the embedding the trained model gives a row of the
  * normalised adjacency that it has never seen, from the item-side tables alone. Additive: the ABI version stays.
  *

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libllmrec_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
-SOURCES = ["graph.hip", "spmm.hip", "spmm_bf16.hip", "dense.hip", "wgrad_host.hip", "rowops.hip", "dropout.hip", "mask.hip", "snapshot.hip", "bpr.hip", "topk.hip", "topk_wide.hip", "serve.hip", "exclude.hip", "candidates.hip", "foldin.hip"]
+SOURCES = ["graph.hip", "spmm.hip", "spmm_bf16.hip", "dense.hip", "wgrad_host.hip", "rowops.hip", "dropout.hip", "mask.hip", "snapshot.hip", "bpr.hip", "topk.hip", "topk_wide.hip", "serve.hip", "exclude.hip", "candidates.hip", "quota.hip", "foldin.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

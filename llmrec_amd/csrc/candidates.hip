@@ -19,7 +19,9 @@
 //                      the scores decoded from the keys, -1 / -inf behind them - and everywhere under the error word
 // cand_nnz == 0 is one launch of cd_write_kernel (every list empty), n_query == 0 none. Sizes and launch counts come from host arguments
 // alone; no allocation, no host read, no atomics, every cross-block hand-over a kernel boundary: capturable and deterministic.
-#include "compact.h"
+// Everything up to the second sort is cd_sorted_pairs (declared in candidates.h), which the capped entry of quota.hip calls too: that entry
+// differs in its last launch alone.
+#include "candidates.h"
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
 
@@ -52,13 +54,6 @@ __global__ __launch_bounds__(256) void cd_keys_kernel(int n_query, const int32_t
         }
     }
 }
-
-// the order-preserving map of float bits to uint32 (a larger float is a larger word) and back
-__device__ __forceinline__ uint32_t cd_ordered(float x) {
-    const uint32_t b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float cd_unordered(uint32_t m) { return __uint_as_float((m & 0x80000000u) ? m ^ 0x80000000u : ~m); }
 
 // columns [16 c, 16 c + 16) of a user row and an item row (zeros past d: fmaf(0, 0, acc) == acc, since acc is never -0.0)
 __device__ __forceinline__ void cd_load_chunk(const float* ur, const float* ir, int c, int d, bool vec, float4 (&uv)[4], float4 (&iv)[4]) {
@@ -152,20 +147,14 @@ __global__ __launch_bounds__(256) void cd_score_kernel(CandArgs a) {
     a.out_id[e] = id;
 }
 
-// wave q: lanes 0 and 1 find where the keys of query q begin and end in the sorted keys (the dropped keys lie behind every query)
+// wave q: the range of query q in the sorted keys (cd_query_range of candidates.h), its first min(K, count) pairs
 __global__ __launch_bounds__(256) void cd_write_kernel(int n_query, int K, const uint64_t* __restrict__ keys, const int32_t* __restrict__ ids, int64_t n_keys,
                                                        int32_t* __restrict__ out_idx, float* __restrict__ out_score, const uint32_t* __restrict__ err) {
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= n_query) return;                                      // (wave-uniform)
-    int64_t lo = 0, hi = 0;
-    if (err && *err == 0u) {                                       // (err == nullptr: no candidate entry at all)
-        const uint64_t head = (uint64_t)(q + (lane & 1)) << 32;
-        hi = n_keys;
-        while (lo < hi) { const int64_t mid = lo + ((hi - lo) >> 1); if (keys[mid] < head) lo = mid + 1; else hi = mid; }
-        hi = __shfl(lo, 1, 64);
-        lo = __shfl(lo, 0, 64);
-    }
+    int64_t lo, hi;
+    cd_query_range(keys, n_keys, q, lane, err, lo, hi);                // (err == nullptr: no candidate entry at all)
     const int64_t count = hi - lo;
     for (int j = lane; j < K; j += 64) {
         const bool in = j < count;
@@ -212,6 +201,88 @@ static int cd_lanes() {
 }
 #endif
 
+int cd_check(const char* name, const CandCall& c) {
+    LLMREC_CHECK_ARG(c.n_query >= 0 && c.n_items > 0 && c.n_items < (1ll << 31) && c.d >= 1 && c.d <= 128 && c.K >= 1,
+                     "%s: bad sizes (1 <= d <= 128, K >= 1, 0 < n_items < 2^31)", name);
+    LLMREC_CHECK_ARG((int64_t)c.n_query * c.K < (1ll << 31), "%s: n_query * K must lie below 2^31", name);
+    LLMREC_CHECK_ARG(c.cand_nnz >= 0 && c.cand_nnz < (1ll << 31), "%s: cand_nnz outside [0, 2^31)", name);
+    LLMREC_CHECK_ARG(c.excl_nnz >= 0 && c.excl_nnz < (1ll << 31), "%s: excl_nnz outside [0, 2^31)", name);
+    if (c.n_query == 0) return LLMREC_OK;
+    LLMREC_CHECK_ARG(c.query_users && c.Eu && c.Ei && c.out_idx && c.out_score && c.ldu >= c.d && c.ldi >= c.d, "%s: null pointer or ld < d", name);
+    LLMREC_CHECK_ARG((c.train_rowptr == nullptr) == (c.train_colidx == nullptr), "%s: train CSR incomplete", name);
+    LLMREC_CHECK_ARG(c.cand_rowptr, "%s: cand_rowptr is missing", name);
+    LLMREC_CHECK_ARG(c.cand_colidx || c.cand_nnz == 0, "%s: cand_nnz > 0 without cand_colidx", name);
+    LLMREC_CHECK_ARG(c.excl_rowptr || c.excl_nnz == 0, "%s: excl_nnz > 0 without excl_rowptr", name);
+    LLMREC_CHECK_ARG(c.excl_colidx || c.excl_nnz == 0, "%s: excl_nnz > 0 without excl_colidx", name);
+    return LLMREC_OK;
+}
+
+int cd_sorted_pairs(const char* name, const CandCall& c, hipStream_t stream, CandSorted* out) {
+    const int32_t n_query = c.n_query;
+    const int64_t cand_nnz = c.cand_nnz, excl_nnz = c.excl_nnz;
+    int64_t off[CD_PARTS];
+    const int64_t need = cd_parts(cand_nnz, excl_nnz, off);
+    LLMREC_CHECK_ARG(c.workspace && (uintptr_t)c.workspace % 16 == 0, "%s: needs the workspace (16-byte aligned)", name);
+    if (c.workspace_bytes < need) {
+        set_error("%s: workspace %lld < %lld", name, (long long)c.workspace_bytes, (long long)need);
+        return LLMREC_EWORKSPACE;
+    }
+    char* x = (char*)c.workspace;
+    uint32_t* err = (uint32_t*)(x + off[CD_ERR]);
+    hipcub::DoubleBuffer<uint64_t> kbuf((uint64_t*)(x + off[CD_KEYS_A]), (uint64_t*)(x + off[CD_KEYS_B]));
+    void* temp = x + off[CD_SORT];
+    const int n = (int)cand_nnz, end_bit = cd_end_bit(n_query);
+    int rc;
+
+    // what the three sorts ask for, before the first launch
+    size_t need_keys = 0, need_pairs = 0, need_excl = 0;
+    {
+        hipcub::DoubleBuffer<uint64_t> k0(nullptr, nullptr);
+        hipcub::DoubleBuffer<int32_t> v0(nullptr, nullptr);
+        LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need_keys, k0, n, 0, end_bit, stream));
+        LLMREC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need_pairs, k0, v0, n, 0, end_bit, stream));
+        const size_t most = need_keys > need_pairs ? need_keys : need_pairs;
+        if (most > (size_t)exclude_sort_reserve(cand_nnz)) {
+            set_error("%s: the sort needs %zu B of temporary storage > %lld", name, most, (long long)exclude_sort_reserve(cand_nnz));
+            return LLMREC_EWORKSPACE;
+        }
+    }
+    if (c.excl_rowptr && (rc = exclude_sort_need(name, n_query, excl_nnz, &need_excl, stream)) != LLMREC_OK) return rc;
+
+    cd_open_kernel<<<1, 64, 0, stream>>>(err);
+    LLMREC_LAUNCH_CHECK();
+    const int64_t work = cand_nnz > (int64_t)n_query + 1 ? cand_nnz : (int64_t)n_query + 1;
+    cd_keys_kernel<<<grid_for(work, 256), 256, 0, stream>>>(n_query, c.cand_rowptr, c.cand_colidx, cand_nnz, c.new_id, c.n_items, kbuf.Current(), err);
+    LLMREC_LAUNCH_CHECK();
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(temp, need_keys, kbuf, n, 0, end_bit, stream));
+    const uint64_t* excl = nullptr;
+    if (c.excl_rowptr && (rc = exclude_sorted_keys(n_query, c.excl_rowptr, c.excl_colidx, excl_nnz, nullptr, c.n_items, (uint64_t*)(x + off[CD_EX_A]),
+                                                   (uint64_t*)(x + off[CD_EX_B]), x + off[CD_EX_SORT], need_excl, err, &excl, stream)) != LLMREC_OK)
+        return rc;
+
+    CandArgs a;
+    a.n_query = n_query; a.query_users = c.query_users;
+    a.Eu = c.Eu; a.ldu = c.ldu; a.Ei = c.Ei; a.ldi = c.ldi; a.d = c.d;
+    a.vec_ok = (c.ldu % 4 == 0) && (c.ldi % 4 == 0) && (((uintptr_t)c.Eu | (uintptr_t)c.Ei) % 16 == 0);
+    a.train_rowptr = c.train_rowptr; a.train_colidx = c.train_colidx;
+    a.excl = excl_nnz > 0 ? excl : nullptr; a.excl_nnz = excl_nnz;
+    a.keys = kbuf.Current(); a.cand_nnz = cand_nnz;
+    a.out_key = kbuf.Alternate(); a.out_id = (int32_t*)(x + off[CD_IDS_A]);
+    a.err = err;
+#ifdef LLMREC_TOOLS_BUILD
+    if (cd_lanes() == 1) cd_score_kernel<1><<<(unsigned)ceil_div(cand_nnz, 256), 256, 0, stream>>>(a);
+    else
+#endif
+    cd_score_kernel<4><<<(unsigned)ceil_div(4 * cand_nnz, 256), 256, 0, stream>>>(a);
+    LLMREC_LAUNCH_CHECK();
+
+    hipcub::DoubleBuffer<uint64_t> sbuf(kbuf.Alternate(), kbuf.Current());
+    hipcub::DoubleBuffer<int32_t> vbuf((int32_t*)(x + off[CD_IDS_A]), (int32_t*)(x + off[CD_IDS_B]));
+    LLMREC_HIP(hipcub::DeviceRadixSort::SortPairs(temp, need_pairs, sbuf, vbuf, n, 0, end_bit, stream));
+    out->keys = sbuf.Current(); out->ids = vbuf.Current(); out->err = err;
+    return LLMREC_OK;
+}
+
 }  // namespace llmrec
 
 using namespace llmrec;
@@ -233,18 +304,10 @@ int llmrec_score_topk_candidates_f32(int32_t n_query, const int64_t* query_users
                                      const int32_t* excl_rowptr, const int32_t* excl_colidx, int64_t excl_nnz,
                                      const int32_t* new_id, llmrec_stream_t stream_) {
     const char* name = "score_topk_candidates";
-    LLMREC_CHECK_ARG(n_query >= 0 && n_items > 0 && n_items < (1ll << 31) && d >= 1 && d <= 128 && K >= 1,
-                     "%s: bad sizes (1 <= d <= 128, K >= 1, 0 < n_items < 2^31)", name);
-    LLMREC_CHECK_ARG((int64_t)n_query * K < (1ll << 31), "%s: n_query * K must lie below 2^31", name);
-    LLMREC_CHECK_ARG(cand_nnz >= 0 && cand_nnz < (1ll << 31), "%s: cand_nnz outside [0, 2^31)", name);
-    LLMREC_CHECK_ARG(excl_nnz >= 0 && excl_nnz < (1ll << 31), "%s: excl_nnz outside [0, 2^31)", name);
-    if (n_query == 0) return LLMREC_OK;
-    LLMREC_CHECK_ARG(query_users && Eu && Ei && out_idx && out_score && ldu >= d && ldi >= d, "%s: null pointer or ld < d", name);
-    LLMREC_CHECK_ARG((train_rowptr == nullptr) == (train_colidx == nullptr), "%s: train CSR incomplete", name);
-    LLMREC_CHECK_ARG(cand_rowptr, "%s: cand_rowptr is missing", name);
-    LLMREC_CHECK_ARG(cand_colidx || cand_nnz == 0, "%s: cand_nnz > 0 without cand_colidx", name);
-    LLMREC_CHECK_ARG(excl_rowptr || excl_nnz == 0, "%s: excl_nnz > 0 without excl_rowptr", name);
-    LLMREC_CHECK_ARG(excl_colidx || excl_nnz == 0, "%s: excl_nnz > 0 without excl_colidx", name);
+    const CandCall c = {n_query, query_users, Eu, ldu, Ei, ldi, n_items, d, train_rowptr, train_colidx, K, out_idx, out_score, workspace, workspace_bytes,
+                        cand_rowptr, cand_colidx, cand_nnz, excl_rowptr, excl_colidx, excl_nnz, new_id};
+    int rc = cd_check(name, c);
+    if (rc != LLMREC_OK || n_query == 0) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     const unsigned wave_grid = (unsigned)ceil_div(n_query, 4);
     if (cand_nnz == 0) {                                           // no candidate entry: every list is empty
@@ -252,66 +315,9 @@ int llmrec_score_topk_candidates_f32(int32_t n_query, const int64_t* query_users
         LLMREC_LAUNCH_CHECK();
         return LLMREC_OK;
     }
-    int64_t off[CD_PARTS];
-    const int64_t need = cd_parts(cand_nnz, excl_nnz, off);
-    LLMREC_CHECK_ARG(workspace && (uintptr_t)workspace % 16 == 0, "%s: needs the workspace (16-byte aligned)", name);
-    if (workspace_bytes < need) {
-        set_error("%s: workspace %lld < %lld", name, (long long)workspace_bytes, (long long)need);
-        return LLMREC_EWORKSPACE;
-    }
-    char* x = (char*)workspace;
-    uint32_t* err = (uint32_t*)(x + off[CD_ERR]);
-    hipcub::DoubleBuffer<uint64_t> kbuf((uint64_t*)(x + off[CD_KEYS_A]), (uint64_t*)(x + off[CD_KEYS_B]));
-    void* temp = x + off[CD_SORT];
-    const int n = (int)cand_nnz, end_bit = cd_end_bit(n_query);
-    int rc;
-
-    // what the three sorts ask for, before the first launch
-    size_t need_keys = 0, need_pairs = 0, need_excl = 0;
-    {
-        hipcub::DoubleBuffer<uint64_t> k0(nullptr, nullptr);
-        hipcub::DoubleBuffer<int32_t> v0(nullptr, nullptr);
-        LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need_keys, k0, n, 0, end_bit, stream));
-        LLMREC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need_pairs, k0, v0, n, 0, end_bit, stream));
-        const size_t most = need_keys > need_pairs ? need_keys : need_pairs;
-        if (most > (size_t)exclude_sort_reserve(cand_nnz)) {
-            set_error("%s: the sort needs %zu B of temporary storage > %lld", name, most, (long long)exclude_sort_reserve(cand_nnz));
-            return LLMREC_EWORKSPACE;
-        }
-    }
-    if (excl_rowptr && (rc = exclude_sort_need(name, n_query, excl_nnz, &need_excl, stream)) != LLMREC_OK) return rc;
-
-    cd_open_kernel<<<1, 64, 0, stream>>>(err);
-    LLMREC_LAUNCH_CHECK();
-    const int64_t work = cand_nnz > (int64_t)n_query + 1 ? cand_nnz : (int64_t)n_query + 1;
-    cd_keys_kernel<<<grid_for(work, 256), 256, 0, stream>>>(n_query, cand_rowptr, cand_colidx, cand_nnz, new_id, n_items, kbuf.Current(), err);
-    LLMREC_LAUNCH_CHECK();
-    LLMREC_HIP(hipcub::DeviceRadixSort::SortKeys(temp, need_keys, kbuf, n, 0, end_bit, stream));
-    const uint64_t* excl = nullptr;
-    if (excl_rowptr && (rc = exclude_sorted_keys(n_query, excl_rowptr, excl_colidx, excl_nnz, nullptr, n_items, (uint64_t*)(x + off[CD_EX_A]),
-                                                 (uint64_t*)(x + off[CD_EX_B]), x + off[CD_EX_SORT], need_excl, err, &excl, stream)) != LLMREC_OK)
-        return rc;
-
-    CandArgs a;
-    a.n_query = n_query; a.query_users = query_users;
-    a.Eu = Eu; a.ldu = ldu; a.Ei = Ei; a.ldi = ldi; a.d = d;
-    a.vec_ok = (ldu % 4 == 0) && (ldi % 4 == 0) && (((uintptr_t)Eu | (uintptr_t)Ei) % 16 == 0);
-    a.train_rowptr = train_rowptr; a.train_colidx = train_colidx;
-    a.excl = excl_nnz > 0 ? excl : nullptr; a.excl_nnz = excl_nnz;
-    a.keys = kbuf.Current(); a.cand_nnz = cand_nnz;
-    a.out_key = kbuf.Alternate(); a.out_id = (int32_t*)(x + off[CD_IDS_A]);
-    a.err = err;
-#ifdef LLMREC_TOOLS_BUILD
-    if (cd_lanes() == 1) cd_score_kernel<1><<<(unsigned)ceil_div(cand_nnz, 256), 256, 0, stream>>>(a);
-    else
-#endif
-    cd_score_kernel<4><<<(unsigned)ceil_div(4 * cand_nnz, 256), 256, 0, stream>>>(a);
-    LLMREC_LAUNCH_CHECK();
-
-    hipcub::DoubleBuffer<uint64_t> sbuf(kbuf.Alternate(), kbuf.Current());
-    hipcub::DoubleBuffer<int32_t> vbuf((int32_t*)(x + off[CD_IDS_A]), (int32_t*)(x + off[CD_IDS_B]));
-    LLMREC_HIP(hipcub::DeviceRadixSort::SortPairs(temp, need_pairs, sbuf, vbuf, n, 0, end_bit, stream));
-    cd_write_kernel<<<wave_grid, 256, 0, stream>>>(n_query, K, sbuf.Current(), vbuf.Current(), cand_nnz, out_idx, out_score, err);
+    CandSorted s;
+    if ((rc = cd_sorted_pairs(name, c, stream, &s)) != LLMREC_OK) return rc;
+    cd_write_kernel<<<wave_grid, 256, 0, stream>>>(n_query, K, s.keys, s.ids, cand_nnz, out_idx, out_score, s.err);
     LLMREC_LAUNCH_CHECK();
     return LLMREC_OK;
 }

@@ -1,5 +1,6 @@
 // compact.h - the device pieces of the compaction layers in front of the sweeps, each defined once: topk_wide.hip (the rounds), serve.hip (the
-// serving pipeline), exclude.hip (its exclusion stage) and candidates.hip (the candidate lists: swept_id) include it; nothing else does.
+// serving pipeline), exclude.hip (its exclusion stage) and candidates.h (the candidate lists and their quotas: swept_id, lanes_below) include it;
+// nothing else does.
 #pragma once
 #include "common.h"
 

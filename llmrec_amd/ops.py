@@ -1514,6 +1514,55 @@ def score_topk_candidates(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr
     return idx, sc
 
 
+def score_topk_candidates_capped(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, candidates, item_group: torch.Tensor, cap,
+                                 exclude=None, filt: Optional[ItemFilter] = None, ws: Optional[torch.Tensor] = None, n_groups: Optional[int] = None):
+    """score_topk_candidates under per-group quotas: (idx int32 [n, K], scores float32 [n, K]) - query q's survivors ranked as there, and of
+    every group only the first cap(g) of them kept; the list is the first K kept items (llmrec_score_topk_candidates_capped_f32,
+    csrc/quota.hip: the uncapped call's launches up to the sorted pairs, then one wave per query walks the ranking).
+    item_group: int32 [n_items] on the device; a value outside [0, n_groups) means no group (never capped). cap: an int >= 1 for every group,
+    or an int32 device tensor [n_groups] of caps >= 0 (0 removes the group; n_groups is then its length). n_groups with an int cap:
+    int(item_group.max()) + 1 unless given - giving it keeps the call free of host reads. K <= LLMREC_TOPK_WIDE_MAX (1024).
+    candidates / exclude / filt: as for score_topk_candidates; ws: its workspace (score_topk_candidates_workspace) - with it (and n_groups
+    or a cap tensor) the call is capturable."""
+    name = "score_topk_candidates_capped"
+    _need_gpu(Eu, Ei, query_users, item_group)
+    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
+    q = query_users.to(torch.int64).contiguous()
+    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
+    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+        raise RuntimeError("%s: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (name, K, CONST["LLMREC_TOPK_WIDE_MAX"]))
+    if filt is not None and filt.n_items != I:
+        raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
+    if item_group.dtype != torch.int32 or item_group.dim() != 1 or item_group.numel() != I:
+        raise RuntimeError("%s: item_group int32 [%d] expected, got %s %s" % (name, I, item_group.dtype, tuple(item_group.shape)))
+    item_group = item_group.contiguous()
+    if isinstance(cap, torch.Tensor):
+        _need_gpu(cap)
+        if cap.dtype != torch.int32 or cap.dim() != 1 or cap.numel() < 1 or (n_groups is not None and int(n_groups) != cap.numel()):
+            raise RuntimeError("%s: cap = int32 [n_groups >= 1] expected, got %s %s (n_groups = %s)" % (name, cap.dtype, tuple(cap.shape), n_groups))
+        caps, one, groups = cap.contiguous(), 0, cap.numel()
+    else:
+        if int(cap) != cap or cap < 1:
+            raise RuntimeError("%s: an integer cap >= 1 or an int32 tensor [n_groups] expected, got %r" % (name, cap))
+        caps, one = None, int(cap)
+        groups = int(n_groups) if n_groups is not None else max(int(item_group.max()) + 1, 1)
+        if groups < 1:
+            raise RuntimeError("%s: n_groups = %d, at least 1 expected" % (name, groups))
+    crp, cci = _query_csr(name, "candidates", candidates, n)
+    erp, eci = _query_csr(name, "exclude", exclude, n) if exclude is not None else (None, None)
+    cand_nnz, excl_nnz = cci.numel(), eci.numel() if eci is not None else 0
+    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
+    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+    if ws is None:
+        ws = score_topk_candidates_workspace(n, K, cand_nnz, excl_nnz, Eu.device)
+    _lib.call("llmrec_score_topk_candidates_capped_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
+              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), _p(crp), _p(cci) if cand_nnz else None, cand_nnz,
+              _p(erp), _p(eci) if excl_nnz else None, excl_nnz, _p(filt.new_id) if filt is not None else None,
+              _p(item_group), groups, _p(caps), one, _stream())
+    return idx, sc
+
+
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage-1 candidate export: the top-k item ids per user WITHOUT masking, i.e. what the reference
     README's `torch.topk(user_emb @ item_emb.T, k=10)` snippet (README.md:243-247) produces for

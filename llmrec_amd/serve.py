@@ -21,8 +21,19 @@ rec.rank_new(histories, candidates, 20) return the k best of each user's OWN lis
 (ops.score_topk_candidates, csrc/candidates.hip: only the listed pairs are scored, two radix sorts select; no sweep of the catalogue). A
 list is a set; allow / deny lists, the train row and `exclude` remove from it as they do for recommend().
 
+Quotas - "at most m items of any one brand, seller, category or series in a list": group_of= (one group id per item, negative = none) and
+per_group= (one cap, or one per group; 0 removes a group) on all four calls. The list is the greedy walk down the user's ranking that takes
+an item while its group has room; equivalently an item is kept if fewer than cap(group) survivors of its group stand before it, and the
+list is the first k kept items. rank / rank_new walk the ranking of the user's own list in the last launch of the candidate pipeline
+(ops.score_topk_candidates_capped, csrc/quota.hip). recommend / recommend_new are exact over the whole catalogue in two rounds: round 1
+fetches the first min(1024, overfetch * k) items of every ranking with the sweeps and walks them - a prefix of the ranking gives a prefix
+of the walk, so a list that comes back full is final, and so is the list of a user whose fetched row was not full (it held every
+survivor); round 2 walks the whole catalogue for the remaining users alone. The lists do not depend on `overfetch`; rec.last_quota says how
+many users round 2 served.
+
 Not covered: fold-in moves no item embedding and adds no user to the graph; dp.py and the sharded evaluations take
-neither a filter nor exclusion or candidate lists; recommend()'s allow-list is one item set for all users of a call (per-user sets: rank)."""
+neither a filter nor exclusion or candidate lists nor quotas; recommend()'s allow-list is one item set for all users of a call (per-user
+sets: rank); under quotas k <= 1024, and recommend()'s two rounds read one flag vector back, so that route is not capturable."""
 from __future__ import annotations
 
 import sys
@@ -34,6 +45,8 @@ import torch
 from . import ops
 
 _MAX_FILTERS = 4                                                   # ItemFilters kept per Recommender (each holds 2 x n_items int32)
+ROUND2_PAIRS = 1 << 23                                             # recommend() under quotas: (query, item) pairs per whole-catalogue call of round 2
+#                                                                    (about 25 bytes of workspace per pair + 32 MiB: some 240 MiB)
 
 
 def _ids(ids, what: str, bound: int, device) -> torch.Tensor:
@@ -121,6 +134,50 @@ def exclusion_csr(exclude, users, n_items: int, what: str = "exclude") -> Option
         raise ValueError("%s: %d entries exceed int32 row pointers" % (what, rowptr[-1]))
     colidx = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     return rowptr.astype(np.int32), colidx.astype(np.int32)
+
+
+def group_quota(group_of, per_group, n_items: int) -> Optional[Tuple[np.ndarray, object, int]]:
+    """Recommender's `group_of` / `per_group`, normalised on the HOST: None without both, else (item_group int32 [n_items] with -1 = no group,
+    cap, n_groups) - cap an int >= 1 for every group, or an int32 array [n_groups] of caps >= 0 (0 removes the group).
+    group_of: an array or tensor of n_items integers, negative = no group. per_group: an int >= 1, or a sequence of n_groups ints >= 0 that
+    covers every group id in group_of (with an int, n_groups is the largest group id + 1). One argument without the other raises
+    ValueError, as do a wrong length, non-integer values and a negative cap. Pure host code: no device is needed."""
+    if group_of is None and per_group is None:
+        return None
+    if group_of is None or per_group is None:
+        raise ValueError("group_of and per_group go together: %s is missing" % ("group_of" if group_of is None else "per_group"))
+    g = _int_array(group_of, "group_of")
+    if g.ndim != 1 or g.size != n_items:
+        raise ValueError("group_of: %d integers expected (one per item), got shape %s" % (n_items, tuple(g.shape)))
+    top = int(g.max()) if g.size else -1
+    if top >= (1 << 31) - 1:
+        raise ValueError("group_of: group ids must lie below 2^31 - 1; got %d" % top)
+    group = np.where(g < 0, -1, g).astype(np.int32)
+    if isinstance(per_group, (bool, np.bool_)):
+        raise ValueError("per_group: an integer or a sequence of integers expected, got %r" % (per_group,))
+    if isinstance(per_group, (int, np.integer)):
+        if per_group < 1:
+            raise ValueError("per_group: one cap for every group must be at least 1; got %d" % per_group)
+        return group, int(per_group), max(top + 1, 1)
+    if isinstance(per_group, (float, np.floating)) or isinstance(per_group, (str, bytes, dict)) or \
+            not (hasattr(per_group, "__len__") or isinstance(per_group, torch.Tensor)):
+        raise ValueError("per_group: an integer or a sequence of integers expected, got %r" % (per_group,))
+    caps = _int_array(per_group, "per_group")
+    if caps.ndim != 1 or caps.size < 1 or caps.size <= top:
+        raise ValueError("per_group: one cap per group expected (group ids reach %d), got shape %s" % (top, tuple(caps.shape)))
+    if caps.min() < 0:
+        raise ValueError("per_group: a cap must not be negative; got %d" % int(caps.min()))
+    return group, np.minimum(caps, (1 << 31) - 1).astype(np.int32), int(caps.size)
+
+
+def csr_rows(csr: Tuple[np.ndarray, np.ndarray], rows: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The listed rows of a host CSR, in the order listed, as a CSR of their own."""
+    rp, ci = csr
+    rows = np.asarray(rows, dtype=np.int64)
+    lens = (rp[rows + 1] - rp[rows]).astype(np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(lens)])
+    take = np.repeat(rp[rows].astype(np.int64) - rowptr[:-1], lens) + np.arange(rowptr[-1])
+    return rowptr.astype(np.int32), ci[take].astype(np.int32)
 
 
 def csr_slice(csr: Tuple[np.ndarray, np.ndarray], a: int, b: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -235,14 +292,19 @@ class Recommender:
         return filt
 
     def recommend(self, users, k: int, allow_items=None, deny_items=None, exclude_seen: bool = True, chunk: Optional[int] = 65536,
-                  exclude=None):
+                  exclude=None, group_of=None, per_group=None, overfetch: int = 2):
         """(items int64 [n, k], scores float32 [n, k]) for the listed users (any order, repeats allowed): the k best eligible items,
         -1 / -inf behind the last candidate. allow_items / deny_items: id lists or tensors - both given means allowed and not denied;
         exclude_seen: leave out the user's train row; chunk: users per call, which bounds the workspace (the lists do not depend on it;
         None = one call). k <= LLMREC_TOPK_WIDE_MAX (1024).
         exclude: one more exclusion list per listed user, in any form exclusion_csr accepts - a dict user id -> ids, a (rowptr, colidx)
         tuple, an [n, m] array or tensor with -1 padding (the `items` of an earlier call: the next page), or a sequence of n id
-        sequences. It is normalised on the host (a device tensor comes to the host once) and sliced per chunk."""
+        sequences. It is normalised on the host (a device tensor comes to the host once) and sliced per chunk.
+        group_of / per_group (both or neither): quotas - group_of[i] is the group of item i (n_items integers, negative = no group),
+        per_group the cap: an int >= 1 for every group or one int >= 0 per group (group_quota). Of every group a list then holds at most
+        its cap: the greedy walk down the user's ranking that takes an item while its group has room - exactly, over the whole catalogue,
+        in two rounds (_recommend_capped). overfetch: round 1 looks at the first min(1024, overfetch * k) items of each ranking; the lists
+        do not depend on it, only the number of users who need round 2 (self.last_quota = {"queries": n, "round2": r} after the call)."""
         dev = self.E_u.device
         q = _ids(users, "users", self.n_users, dev)
         filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
@@ -250,6 +312,9 @@ class Recommender:
         n = q.numel()
         step = n if not chunk or chunk >= n else int(chunk)
         excl = exclusion_csr(exclude, q.cpu().numpy(), self.n_items) if exclude is not None else None
+        quota = group_quota(group_of, per_group, self.n_items)
+        if quota is not None:
+            return self._recommend_capped(n, int(k), step, excl, filt, quota, overfetch, lambda a, b: (self.E_u, q[a:b], train))
 
         def rows(a):
             if excl is None:
@@ -262,6 +327,63 @@ class Recommender:
             return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
         idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
         return idx.to(torch.int64), sc
+
+    def _quota_on_device(self, quota):
+        """(item_group int32 [n_items], cap: int or int32 [n_groups], n_groups) of group_quota, the arrays on the device."""
+        group, cap, n_groups = quota
+        dev = self.E_i.device
+        return torch.from_numpy(group).to(dev), cap if isinstance(cap, int) else torch.from_numpy(cap).to(dev), n_groups
+
+    def _recommend_capped(self, n: int, k: int, step: int, excl, filt, quota, overfetch, side):
+        """recommend / recommend_new under quotas, exact over the whole catalogue. side(a, b) = (Eu, query list, train CSR or None) of queries
+        [a, b); excl: the host exclusion CSR over all n queries, or None. Per chunk:
+          round 1  the first K1 = min(1024, overfetch * k) ids of every ranking (ops.score_topk_excluded: the sweeps), then those rows, -1
+                   padding included, as candidate rows of ops.score_topk_candidates_capped. A prefix of the ranking gives a prefix of the
+                   greedy walk, so a capped list that came back FULL is final; and a fetched row that was NOT full held every survivor,
+                   so its capped list is final too. Such queries are settled. Finding the others costs one host read.
+          round 2  the unsettled queries alone: the capped op with the whole catalogue as each query's candidate row, with the train rows,
+                   the exclusion rows and the filter; at most ROUND2_PAIRS (query, item) pairs per call. Its lists replace round 1's.
+        The lists therefore do not depend on overfetch or on the chunk. self.last_quota counts the queries and those sent to round 2."""
+        dev = self.E_i.device
+        top = ops.CONST["LLMREC_TOPK_WIDE_MAX"]
+        if k < 1 or k > top:
+            raise ValueError("k = %d: under quotas 1 <= k <= %d" % (k, top))
+        if isinstance(overfetch, bool) or not isinstance(overfetch, (int, np.integer)) or overfetch < 1:
+            raise ValueError("overfetch: an integer >= 1 expected, got %r" % (overfetch,))
+        group, cap, n_groups = self._quota_on_device(quota)
+        K1 = min(top, int(overfetch) * k)
+        self.last_quota = {"queries": n, "round2": 0}
+        every = torch.arange(self.n_items, dtype=torch.int32, device=dev)
+        per_call = max(1, ROUND2_PAIRS // self.n_items)
+        on_dev = lambda csr: (torch.from_numpy(csr[0]).to(dev), torch.from_numpy(np.ascontiguousarray(csr[1])).to(dev))
+        parts = []
+        for a in range(0, n, max(step, 1)):
+            b = min(a + step, n)
+            Eu, qu, train = side(a, b)
+            fetched, _ = ops.score_topk_excluded(Eu, self.E_i, qu, train, K1, on_dev(csr_slice(excl, a, b)) if excl is not None else None, filt)
+            rows = torch.arange(b - a + 1, dtype=torch.int32, device=dev) * K1, fetched.reshape(-1)
+            idx, sc = ops.score_topk_candidates_capped(Eu, self.E_i, qu, None, k, rows, group, cap, n_groups=n_groups)
+            unsettled = ((idx[:, k - 1] < 0) & (fetched[:, K1 - 1] >= 0)).nonzero().reshape(-1)
+            todo = unsettled.cpu().numpy()                         # (the one host read)
+            self.last_quota["round2"] += int(todo.size)
+            for s in range(0, todo.size, per_call):
+                u = unsettled[s:s + per_call]
+                m = u.numel()
+                whole = torch.arange(m + 1, dtype=torch.int32, device=dev) * self.n_items, every.repeat(m)
+                gone = on_dev(csr_rows(excl, a + todo[s:s + per_call])) if excl is not None else None
+                idx[u], sc[u] = ops.score_topk_candidates_capped(Eu, self.E_i, qu[u], train, k, whole, group, cap, gone, filt, n_groups=n_groups)
+            parts.append((idx, sc))
+        if not parts:
+            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
+        return idx.to(torch.int64), sc
+
+    def _ranker(self, k: int, quota):
+        """ops.score_topk_candidates, or with quotas its capped form, as f(Eu, query list, train, candidates, exclude, filt)."""
+        if quota is None:
+            return lambda Eu, qu, train, c, e, f: ops.score_topk_candidates(Eu, self.E_i, qu, train, k, c, e, f)
+        group, cap, n_groups = self._quota_on_device(quota)
+        return lambda Eu, qu, train, c, e, f: ops.score_topk_candidates_capped(Eu, self.E_i, qu, train, k, c, group, cap, e, f, n_groups=n_groups)
 
     def _rank_chunks(self, n: int, k: int, chunk, cand, excl, filt, call):
         """What rank and rank_new share: the chunks of n queries, the candidate and exclusion CSRs sliced per chunk and sent to the device;
@@ -282,13 +404,15 @@ class Recommender:
         return idx.to(torch.int64), sc
 
     def rank(self, users, candidates, k: int, allow_items=None, deny_items=None, exclude_seen: bool = True, exclude=None,
-             chunk: Optional[int] = 65536):
+             chunk: Optional[int] = 65536, group_of=None, per_group=None):
         """(items int64 [n, k], scores float32 [n, k]) for the listed users (any order, repeats allowed): the k best of each user's OWN
         candidate list, -1 / -inf behind the last candidate (ops.score_topk_candidates: only the listed pairs are scored). candidates: one
         id list per listed user, in any form exclusion_csr accepts - a dict user id -> ids (a listed user without a key has an empty
         list: its row comes back all -1), a (rowptr, colidx) tuple, an [n, m] array or tensor with -1 padding, a sequence of n id
         sequences; a list is a SET: order and repeats do not matter, bit for bit. allow_items / deny_items / exclude_seen / exclude /
-        chunk: as for recommend (an ineligible, seen or excluded candidate is left out). Any k >= 1."""
+        chunk: as for recommend (an ineligible, seen or excluded candidate is left out). Any k >= 1.
+        group_of / per_group: quotas, as for recommend - the greedy walk down the ranking of the user's own list
+        (ops.score_topk_candidates_capped; then k <= 1024)."""
         dev = self.E_u.device
         q = _ids(users, "users", self.n_users, dev)
         host_users = q.cpu().numpy()
@@ -298,16 +422,18 @@ class Recommender:
             raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
         cand = exclusion_csr(candidates, host_users, self.n_items, what="candidates")
         excl = exclusion_csr(exclude, host_users, self.n_items) if exclude is not None else None
-        return self._rank_chunks(q.numel(), int(k), chunk, cand, excl, filt,
-                                 lambda a, b, c, e, f: ops.score_topk_candidates(self.E_u, self.E_i, q[a:b], train, int(k), c, e, f))
+        ranker = self._ranker(int(k), group_quota(group_of, per_group, self.n_items))
+        return self._rank_chunks(q.numel(), int(k), chunk, cand, excl, filt, lambda a, b, c, e, f: ranker(self.E_u, q[a:b], train, c, e, f))
 
     def rank_new(self, histories, candidates, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None,
-                 id_rows=None, chunk: Optional[int] = 65536):
+                 id_rows=None, chunk: Optional[int] = 65536, group_of=None, per_group=None):
         """rank() for users who are not rows of the graph, as recommend_new is to recommend: n item histories, one candidate list per new
         user (a dict is keyed by position here), the scores the bits of ops.scores(embed_new(histories, id_rows), E_i, arange(n)).
-        exclude_history: leave out the history's own items. Needs fold_in=True at construction."""
+        exclude_history: leave out the history's own items. group_of / per_group: quotas, as for rank. Needs fold_in=True at
+        construction."""
         self._tables()
         dev = self.E_i.device
+        ranker = self._ranker(int(k), group_quota(group_of, per_group, self.n_items))
         ids = self._id_rows(id_rows)
         hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
         n = hist[0].size - 1
@@ -319,8 +445,7 @@ class Recommender:
         if exclude_history:
             excl = csr_join(hist, excl)
         return self._rank_chunks(n, int(k), chunk, cand, excl, filt,
-                                 lambda a, b, c, e, f: ops.score_topk_candidates(self._embed(hist, ids, a, b), self.E_i, torch.arange(b - a, device=dev),
-                                                                                 None, int(k), c, e, f))
+                                 lambda a, b, c, e, f: ranker(self._embed(hist, ids, a, b), torch.arange(b - a, device=dev), None, c, e, f))
 
     def _tables(self) -> ops.FoldInTables:
         if self.fold_in is None:
@@ -353,12 +478,12 @@ class Recommender:
         return self._embed(hist, ids, 0, hist[0].size - 1)
 
     def recommend_new(self, histories, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None, id_rows=None,
-                      chunk: Optional[int] = 65536):
+                      chunk: Optional[int] = 65536, group_of=None, per_group=None, overfetch: int = 2):
         """recommend() for users who are not rows of the graph: (items int64 [n, k], scores float32 [n, k]) for n item histories, the k
         best eligible items by (score descending, item id ascending), -1 / -inf behind the last candidate, the scores the bits of
         ops.scores(embed_new(histories, id_rows), E_i, arange(n)). exclude_history: leave out the history's own items; exclude: one more
         list per new user, in any form exclusion_csr accepts (a dict is keyed by position here). allow_items / deny_items / chunk: as
-        for recommend. Needs fold_in=True at construction."""
+        for recommend, as are group_of / per_group / overfetch (quotas, exact in two rounds). Needs fold_in=True at construction."""
         self._tables()
         dev = self.E_i.device
         ids = self._id_rows(id_rows)
@@ -369,6 +494,10 @@ class Recommender:
         if exclude_history:
             excl = csr_join(hist, excl)
         step = n if not chunk or chunk >= n else int(chunk)
+        quota = group_quota(group_of, per_group, self.n_items)
+        if quota is not None:
+            return self._recommend_capped(n, int(k), step, excl, filt, quota, overfetch,
+                                          lambda a, b: (self._embed(hist, ids, a, b), torch.arange(b - a, device=dev), None))
         parts = []
         for a in range(0, n, max(step, 1)):
             b = min(a + step, n)

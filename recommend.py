@@ -1,7 +1,7 @@
 """Recommend from a checkpoint: the top-K items for a list of users, optionally among an allow-list or outside a deny-list of items.
 
     python recommend.py --checkpoint ckpt/best.ckpt (--users users.txt | --histories hist.txt) --topk 20 [--allow_items F | --deny_items F]
-                        [--include_seen] [--exclude F] [--candidates F] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model
+                        [--include_seen] [--exclude F] [--candidates F] [--item_groups F --per_group M] --out out.npz --dataset netflix_valid_item --data_path ./data/ [the flags the model
                         was trained with ...]
 
 The flags above are this script's own; EVERY OTHER argument goes to the drop-in's parser untouched (utility/parser.py - the
@@ -16,6 +16,10 @@ the trained model with the item side held fixed (Recommender.recommend_new) and 
 unless --include_seen; --exclude pairs are then (row, item) too; the .npz holds `rows` int64 [n] in place of `users`.
 --candidates: (user, item) pairs in the format of --exclude, (row, item) with --histories - each user's OWN candidate list: the script then
 ranks only those items per user (Recommender.rank / rank_new; a user without a pair gets an empty list), and --topk has no 1024 cap.
+--item_groups with --per_group (both or neither): quotas - a .npy integer array [n_items] or text with one group id per line, line i the
+group of item i (negative: no group), and the cap M >= 1: a list then holds at most M items of any one group, taken greedily down the
+user's ranking (exact; Recommender's group_of / per_group). They work with --users and --histories, with and without --candidates (under
+quotas --topk <= 1024 on every route).
 --mask / --mask_rate != 0 are refused: with them every forward is a masking round, and a serving run must not advance one."""
 import argparse
 import importlib
@@ -40,13 +44,21 @@ def own_parser() -> argparse.ArgumentParser:
     p.add_argument("--include_seen", action="store_true", help="do not exclude the user's train items (--histories: the history's items)")
     p.add_argument("--exclude", help="(user, item) pairs to leave out per user: .npy [m, 2] or text, one `user item` per line")
     p.add_argument("--candidates", help="(user, item) pairs: rank only each user's own candidates; .npy [m, 2] or text, one `user item` per line")
+    p.add_argument("--item_groups", help="quotas: the group id of every item, .npy [n_items] or text with one id per line (negative: no group)")
+    p.add_argument("--per_group", type=int, help="quotas: at most this many items of any one group per list (>= 1); needs --item_groups")
     p.add_argument("--out", required=True, help="the .npz to write")
     return p
 
 
 def split_argv(argv):
     """(this script's namespace, the arguments left for the drop-in's parser - in their order, untouched)."""
-    return own_parser().parse_known_args(list(argv))
+    p = own_parser()
+    own, rest = p.parse_known_args(list(argv))
+    if (own.item_groups is None) != (own.per_group is None):
+        p.error("--item_groups and --per_group go together")
+    if own.per_group is not None and own.per_group < 1:
+        p.error("--per_group must be at least 1")
+    return own, rest
 
 
 def read_ids(path: str) -> np.ndarray:
@@ -127,6 +139,7 @@ def main(argv=None):
     deny = read_ids(own.deny_items) if own.deny_items else None
     exclude = exclusion_lists(read_pairs(own.exclude), users) if own.exclude else None
     candidates = exclusion_lists(read_pairs(own.candidates), users) if own.candidates else None
+    quota = dict(group_of=read_ids(own.item_groups), per_group=own.per_group) if own.item_groups else {}
     m = load_dropin(rest)
     from llmrec_amd.serve import Recommender
     m.set_seed(m.args.seed)
@@ -136,13 +149,16 @@ def main(argv=None):
         histories = [histories.get(int(q), ()) for q in users]
         if candidates is not None:
             items, scores = rec.rank_new(histories, candidates, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen,
-                                         exclude=exclude)
+                                         exclude=exclude, **quota)
         else:
-            items, scores = rec.recommend_new(histories, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen, exclude=exclude)
+            items, scores = rec.recommend_new(histories, own.topk, allow_items=allow, deny_items=deny, exclude_history=not own.include_seen,
+                                              exclude=exclude, **quota)
     elif candidates is not None:
-        items, scores = rec.rank(users, candidates, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
+        items, scores = rec.rank(users, candidates, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude,
+                                 **quota)
     else:
-        items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude)
+        items, scores = rec.recommend(users, own.topk, allow_items=allow, deny_items=deny, exclude_seen=not own.include_seen, exclude=exclude,
+                                      **quota)
     out = own.out if own.out.endswith(".npz") else own.out + ".npz"
     np.savez(out, items=items.cpu().numpy(), scores=scores.cpu().numpy(), **{"rows" if own.histories else "users": users})
     print("recommend.py: %d users x top %d -> %s" % (len(users), own.topk, out))
