@@ -1298,6 +1298,11 @@ def _wide_train_nnz(train: Optional[Csr], q: torch.Tensor) -> int:
     return int((rp[q + 1].to(torch.int64) - rp[q].to(torch.int64)).sum().item())
 
 
+def _train_ptrs(train: Optional[Csr]):
+    """(train_rowptr, train_colidx) of a top-K entry: NULL, NULL without a train CSR."""
+    return (_p(train.rowptr), _p(train.colidx)) if train is not None else (None, None)
+
+
 def topk_wide_mode(mode=None, n_items: int = 0, d: int = 64, K: int = 50) -> int:
     """The mode of a call at K > LLMREC_TOPK_MAX (rounds of the single-sweep call, llmrec_score_topk_wide_f32): "auto" = the bf16 sweep, 56
     ranks per pass - a pass asks for at most LLMREC_TOPK_PREFILTER_MAX_K items, so the prefilter always has room to verify, and
@@ -1327,15 +1332,13 @@ def score_topk(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, 
         nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
         ws = topk_workspace(n, Ei.shape[0], Eu.device, Eu.shape[1], K, nnz)
         _lib.call("llmrec_score_topk_wide_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), Ei.shape[0], Eu.shape[1],
-                  _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-                  K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, Ei.shape[0], Eu.shape[1], K), nnz, _stream())
+                  *_train_ptrs(train), K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, Ei.shape[0], Eu.shape[1], K), nnz, _stream())
         if stats is not None:                                                                          # (the words describe single passes)
             stats.update(tiles=(n + 15) // 16, fallback_tiles=None, drains=None, bitmap_rows=None)
         return idx, sc
     ws = topk_workspace(n, Ei.shape[0], Eu.device, Eu.shape[1])
     _lib.call("llmrec_score_topk_mode_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), Ei.shape[0], Eu.shape[1],
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-              K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, topk_mode(mode, Ei.shape[0], Eu.shape[1], K), _stream())
+              *_train_ptrs(train), K, _p(idx), _p(sc), _p(ws), ws.numel() if ws is not None else 0, topk_mode(mode, Ei.shape[0], Eu.shape[1], K), _stream())
     if stats is not None:
         off = _lib.query("llmrec_score_topk_stats_offset", n, Ei.shape[0])
         stats["tiles"] = (n + 15) // 16
@@ -1390,21 +1393,26 @@ def topk_filtered_workspace(n_query: int, n_items: int, n_kept: int, device, d: 
     return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
 
 
-def _score_topk_served(name: str, Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=None):
-    """What score_topk_filtered and score_topk_excluded share: row-major tables, the query list, the K and filter-size checks, the outputs,
-    train_nnz, the workspace and the filter's pointer triple around llmrec_<name>_f32. exclude: the checked (rowptr, colidx) of the
-    excluded entry, whose three arguments go between train_nnz and the maps."""
+def _served(name: str, Eu, Ei, query_users, K: int, filt, wide_max: bool = True):
+    """What every served wrapper starts with: (Eu, Ei row-major and detached, q int64 contiguous, n, I, d, idx int32 [n, K], scores float32
+    [n, K]), K checked against LLMREC_TOPK_WIDE_MAX (wide_max: the entry has that limit) and the filter's size against the table."""
     _need_gpu(Eu, Ei, query_users)
     Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
     q = query_users.to(torch.int64).contiguous()
     n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
-    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
+    if wide_max and K > CONST["LLMREC_TOPK_WIDE_MAX"]:
         raise RuntimeError("%s: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (name, K, CONST["LLMREC_TOPK_WIDE_MAX"]))
     if filt is not None and filt.n_items != I:
         raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
+    return Eu, Ei, q, n, I, d, torch.empty(n, K, dtype=torch.int32, device=Eu.device), torch.empty(n, K, dtype=torch.float32, device=Eu.device)
+
+
+def _score_topk_served(name: str, Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=None):
+    """What score_topk_filtered and score_topk_excluded share: _served, train_nnz, the workspace and the filter's pointer triple around
+    llmrec_<name>_f32. exclude: the checked (rowptr, colidx) of the excluded entry, whose three arguments go between train_nnz and the
+    maps."""
+    Eu, Ei, q, n, I, d, idx, sc = _served(name, Eu, Ei, query_users, K, filt)
     kept = filt.n_kept if filt is not None else I
-    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
-    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
     nnz = (int(train_nnz) if train is not None else 0) if train_nnz is not None else _wide_train_nnz(train, q)
     excl = ()
     if exclude is not None:
@@ -1414,8 +1422,7 @@ def _score_topk_served(name: str, Eu, Ei, query_users, train, K, filt, mode, tra
         ws = (topk_filtered_workspace(n, I, kept, Eu.device, d, K, nnz) if exclude is None else
               topk_excluded_workspace(n, I, kept, Eu.device, d, K, nnz, excl_nnz))
     maps = (_p(filt.new_id), _p(filt.old_id), _p(filt.n_kept_dev)) if filt is not None else (None, None, None)
-    _lib.call("llmrec_%s_f32" % name, n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
+    _lib.call("llmrec_%s_f32" % name, n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d, *_train_ptrs(train),
               K, _p(idx), _p(sc), _p(ws), ws.numel(), topk_wide_mode(mode, kept, d, K), nnz, *excl, *maps, kept, _stream())
     return idx, sc
 
@@ -1456,14 +1463,8 @@ def score_topk_excluded(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr],
     train_nnz / ws (topk_excluded_workspace): as for score_topk_filtered; with both the call is capturable."""
     if exclude is None:
         return score_topk_filtered(Eu, Ei, query_users, train, K, filt, mode=mode, train_nnz=train_nnz, ws=ws)
-    rowptr, colidx = exclude
-    _need_gpu(Eu, Ei, query_users, rowptr, colidx)
-    n = query_users.numel()
-    if rowptr.dtype != torch.int32 or colidx.dtype != torch.int32 or rowptr.dim() != 1 or colidx.dim() != 1 or rowptr.numel() != n + 1:
-        raise RuntimeError("score_topk_excluded: exclude = (rowptr int32 [%d], colidx int32 [nnz]) expected, got %s %s and %s %s"
-                           % (n + 1, rowptr.dtype, tuple(rowptr.shape), colidx.dtype, tuple(colidx.shape)))
-    rowptr, colidx = rowptr.contiguous(), colidx.contiguous()
-    return _score_topk_served("score_topk_excluded", Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=(rowptr, colidx))
+    name = "score_topk_excluded"
+    return _score_topk_served(name, Eu, Ei, query_users, train, K, filt, mode, train_nnz, ws, exclude=_query_csr(name, "exclude", exclude, query_users.numel()))
 
 
 def _query_csr(name: str, what: str, csr, n: int):
@@ -1484,6 +1485,21 @@ def score_topk_candidates_workspace(n_query: int, K: int, cand_nnz: int, excl_nn
     return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
 
 
+def _score_topk_candidates(name: str, Eu, Ei, query_users, train, K, candidates, exclude, filt, ws, quota=None):
+    """Both candidate wrappers around llmrec_<name>_f32. quota: the capped entry's four arguments behind new_id (item_group, n_groups,
+    group_cap, cap) - with them K has the limit LLMREC_TOPK_WIDE_MAX."""
+    Eu, Ei, q, n, I, d, idx, sc = _served(name, Eu, Ei, query_users, K, filt, wide_max=quota is not None)
+    crp, cci = _query_csr(name, "candidates", candidates, n)
+    erp, eci = _query_csr(name, "exclude", exclude, n) if exclude is not None else (None, None)
+    cand_nnz, excl_nnz = cci.numel(), eci.numel() if eci is not None else 0
+    if ws is None:
+        ws = score_topk_candidates_workspace(n, K, cand_nnz, excl_nnz, Eu.device)
+    _lib.call("llmrec_%s_f32" % name, n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d, *_train_ptrs(train),
+              K, _p(idx), _p(sc), _p(ws), ws.numel(), _p(crp), _p(cci) if cand_nnz else None, cand_nnz,
+              _p(erp), _p(eci) if excl_nnz else None, excl_nnz, _p(filt.new_id) if filt is not None else None, *(quota or ()), _stream())
+    return idx, sc
+
+
 def score_topk_candidates(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, candidates, exclude=None,
                           filt: Optional[ItemFilter] = None, ws: Optional[torch.Tensor] = None):
     """Exact top-K among PER-QUERY candidate lists: (idx int32 [n, K] in item ids, -1 = none, scores float32 [n, K]) - for query q the first
@@ -1493,25 +1509,7 @@ def score_topk_candidates(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr
     carry two rows; entries in any order, repeats allowed, entries < 0 or >= n_items ignored, as are items a filter does not keep (only
     filt.new_id is read). colidx.numel() must be rowptr[n] (the device checks it; a mismatch returns empty lists). Any K >= 1 with
     n * K < 2^31. Nothing is read back: with a workspace `ws` of score_topk_candidates_workspace the call is capturable."""
-    name = "score_topk_candidates"
-    _need_gpu(Eu, Ei, query_users)
-    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
-    q = query_users.to(torch.int64).contiguous()
-    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
-    if filt is not None and filt.n_items != I:
-        raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
-    crp, cci = _query_csr(name, "candidates", candidates, n)
-    erp, eci = _query_csr(name, "exclude", exclude, n) if exclude is not None else (None, None)
-    cand_nnz, excl_nnz = cci.numel(), eci.numel() if eci is not None else 0
-    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
-    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
-    if ws is None:
-        ws = score_topk_candidates_workspace(n, K, cand_nnz, excl_nnz, Eu.device)
-    _lib.call("llmrec_score_topk_candidates_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-              K, _p(idx), _p(sc), _p(ws), ws.numel(), _p(crp), _p(cci) if cand_nnz else None, cand_nnz,
-              _p(erp), _p(eci) if excl_nnz else None, excl_nnz, _p(filt.new_id) if filt is not None else None, _stream())
-    return idx, sc
+    return _score_topk_candidates("score_topk_candidates", Eu, Ei, query_users, train, K, candidates, exclude, filt, ws)
 
 
 def score_topk_candidates_capped(Eu, Ei, query_users: torch.Tensor, train: Optional[Csr], K: int, candidates, item_group: torch.Tensor, cap,
@@ -1525,16 +1523,9 @@ def score_topk_candidates_capped(Eu, Ei, query_users: torch.Tensor, train: Optio
     candidates / exclude / filt: as for score_topk_candidates; ws: its workspace (score_topk_candidates_workspace) - with it (and n_groups
     or a cap tensor) the call is capturable."""
     name = "score_topk_candidates_capped"
-    _need_gpu(Eu, Ei, query_users, item_group)
-    Eu, Ei = _rowmajor(Eu.detach()), _rowmajor(Ei.detach())
-    q = query_users.to(torch.int64).contiguous()
-    n, I, d = q.numel(), Ei.shape[0], Eu.shape[1]
-    if K > CONST["LLMREC_TOPK_WIDE_MAX"]:
-        raise RuntimeError("%s: K = %d exceeds LLMREC_TOPK_WIDE_MAX = %d" % (name, K, CONST["LLMREC_TOPK_WIDE_MAX"]))
-    if filt is not None and filt.n_items != I:
-        raise RuntimeError("%s: the filter covers %d items, the table has %d" % (name, filt.n_items, I))
-    if item_group.dtype != torch.int32 or item_group.dim() != 1 or item_group.numel() != I:
-        raise RuntimeError("%s: item_group int32 [%d] expected, got %s %s" % (name, I, item_group.dtype, tuple(item_group.shape)))
+    _need_gpu(item_group)
+    if item_group.dtype != torch.int32 or item_group.dim() != 1 or item_group.numel() != Ei.shape[0]:
+        raise RuntimeError("%s: item_group int32 [%d] expected, got %s %s" % (name, Ei.shape[0], item_group.dtype, tuple(item_group.shape)))
     item_group = item_group.contiguous()
     if isinstance(cap, torch.Tensor):
         _need_gpu(cap)
@@ -1548,19 +1539,7 @@ def score_topk_candidates_capped(Eu, Ei, query_users: torch.Tensor, train: Optio
         groups = int(n_groups) if n_groups is not None else max(int(item_group.max()) + 1, 1)
         if groups < 1:
             raise RuntimeError("%s: n_groups = %d, at least 1 expected" % (name, groups))
-    crp, cci = _query_csr(name, "candidates", candidates, n)
-    erp, eci = _query_csr(name, "exclude", exclude, n) if exclude is not None else (None, None)
-    cand_nnz, excl_nnz = cci.numel(), eci.numel() if eci is not None else 0
-    idx = torch.empty(n, K, dtype=torch.int32, device=Eu.device)
-    sc = torch.empty(n, K, dtype=torch.float32, device=Eu.device)
-    if ws is None:
-        ws = score_topk_candidates_workspace(n, K, cand_nnz, excl_nnz, Eu.device)
-    _lib.call("llmrec_score_topk_candidates_capped_f32", n, _p(q), _p(Eu), _ld(Eu), _p(Ei), _ld(Ei), I, d,
-              _p(train.rowptr) if train is not None else None, _p(train.colidx) if train is not None else None,
-              K, _p(idx), _p(sc), _p(ws), ws.numel(), _p(crp), _p(cci) if cand_nnz else None, cand_nnz,
-              _p(erp), _p(eci) if excl_nnz else None, excl_nnz, _p(filt.new_id) if filt is not None else None,
-              _p(item_group), groups, _p(caps), one, _stream())
-    return idx, sc
+    return _score_topk_candidates(name, Eu, Ei, query_users, train, K, candidates, exclude, filt, ws, quota=(_p(item_group), groups, _p(caps), one))
 
 
 def export_candidates(Eu, Ei, k: int = 10, query_users: Optional[torch.Tensor] = None) -> torch.Tensor:

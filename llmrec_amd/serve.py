@@ -37,7 +37,7 @@ sets: rank); under quotas k <= 1024, and recommend()'s two rounds read one flag 
 from __future__ import annotations
 
 import sys
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -225,6 +225,17 @@ def csr_join(a: Tuple[np.ndarray, np.ndarray], b: Optional[Tuple[np.ndarray, np.
     return (ra.astype(np.int64) + rb).astype(np.int32), col.astype(np.int32)
 
 
+class _Side(NamedTuple):
+    """The query side of a request: who is asked for (Recommender._graph_side, ._new_side)."""
+    n: int                                                         # queries
+    keys: Callable[[], np.ndarray]                                 # the n host ids that dict-form lists are keyed by
+    rows: Callable[[int, int], tuple]                              # (a, b) -> (Eu, query ids into Eu, train CSR or None) of queries [a, b)
+    gone: Optional[Tuple[np.ndarray, np.ndarray]] = None           # a host CSR over the queries to leave out in front of `exclude`: a new user's history
+
+
+_CATALOGUE = object()                                              # Recommender._serve's `candidates` of recommend / recommend_new: no lists
+
+
 class Recommender:
     def __init__(self, E_u: torch.Tensor, E_i: torch.Tensor, train: Optional[ops.Csr], fold_in: Optional[ops.FoldInTables] = None,
                  iu: Optional[ops.Csr] = None):
@@ -291,6 +302,109 @@ class Recommender:
         self._filters[key] = filt                                  # (most recently used last)
         return filt
 
+    # -----------------------------------------------------------------------------------------
+    # A request = a query side (who asks: _Side) + what to rank among and what to leave out (_serve). The four public calls differ in
+    # the side - users of the graph or new users - and in whether each query brings a candidate list; everything else is one driver.
+    # -----------------------------------------------------------------------------------------
+    def _graph_side(self, users, exclude_seen: bool) -> _Side:
+        """The listed users of the graph: their rows of E_u and, with exclude_seen, the train CSR. Lists are keyed by user id."""
+        q = _ids(users, "users", self.n_users, self.E_u.device)
+        train = self.train if exclude_seen else None
+        return _Side(q.numel(), lambda: q.cpu().numpy(), lambda a, b: (self.E_u, q[a:b], train))
+
+    def _new_side(self, histories, id_rows, exclude_history: bool) -> _Side:
+        """Users who are not rows of the graph: each chunk is embedded from its histories when it is asked for and queried as rows
+        0 .. b - a of that table; there is no train CSR, the history is what exclude_history leaves out. Lists are keyed by position."""
+        hist, ids = self._histories(histories, id_rows)
+        n, dev = hist[0].size - 1, self.E_i.device
+        return _Side(n, lambda: np.arange(n), lambda a, b: (self._embed(hist, ids, a, b), torch.arange(b - a, device=dev), None),
+                     hist if exclude_history else None)
+
+    def _on_device(self, csr, take, *at):
+        """take(csr, *at) - csr_slice or csr_rows of a host CSR - on the device; None stays None."""
+        if csr is None:
+            return None
+        rp, ci = take(csr, *at)
+        dev = self.E_i.device
+        return torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
+
+    def _serve(self, side: _Side, k: int, allow_items, deny_items, exclude, chunk, candidates=_CATALOGUE, group_of=None, per_group=None,
+               overfetch=None):
+        """One request, for every public call: the filter, the host CSRs of `exclude` (behind the side's own history, if it leaves one out)
+        and of `candidates`, the quota, then per chunk of `chunk` queries the slices of those CSRs on the device and one of the routes
+          the catalogue              ops.score_topk_excluded (the sweeps)
+          candidate lists            ops.score_topk_candidates, under a quota ops.score_topk_candidates_capped
+          the catalogue under quota  the two rounds of _recommend_capped
+        and the parts joined: (items int64 [n, k], scores float32 [n, k])."""
+        dev, k, n = self.E_i.device, int(k), side.n
+        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
+        if candidates is None:
+            raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
+        keys = side.keys() if exclude is not None or candidates is not _CATALOGUE else None          # (users on the device: one host read)
+        cand = exclusion_csr(candidates, keys, self.n_items, what="candidates") if candidates is not _CATALOGUE else None
+        excl = exclusion_csr(exclude, keys, self.n_items)
+        if side.gone is not None:
+            excl = csr_join(side.gone, excl)
+        quota = group_quota(group_of, per_group, self.n_items)
+        if quota is not None:
+            group, cap, n_groups = quota
+            group, cap = torch.from_numpy(group).to(dev), cap if isinstance(cap, int) else torch.from_numpy(cap).to(dev)
+            capped = lambda Eu, qu, train, c, e, f: ops.score_topk_candidates_capped(Eu, self.E_i, qu, train, k, c, group, cap, e, f, n_groups=n_groups)
+            two_rounds = self._recommend_capped(n, k, overfetch, excl, filt, capped) if cand is None else None
+        step = n if not chunk or chunk >= n else int(chunk)
+        parts = []
+        for a in range(0, n, max(step, 1)):
+            b = min(a + step, n)
+            Eu, qu, train = side.rows(a, b)
+            c, e = self._on_device(cand, csr_slice, a, b), self._on_device(excl, csr_slice, a, b)
+            if quota is not None:
+                parts.append(two_rounds(Eu, qu, train, e, a) if c is None else capped(Eu, qu, train, c, e, filt))
+            elif c is None:
+                parts.append(ops.score_topk_excluded(Eu, self.E_i, qu, train, k, e, filt))
+            else:
+                parts.append(ops.score_topk_candidates(Eu, self.E_i, qu, train, k, c, e, filt))
+        if not parts:
+            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+        idx, sc = parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))
+        return idx.to(torch.int64), sc
+
+    def _recommend_capped(self, n: int, k: int, overfetch, excl, filt, capped):
+        """recommend / recommend_new under quotas, exact over the whole catalogue: the route f(Eu, query list, train CSR or None, e, a) of
+        the chunk of queries that starts at query a, e its exclusion rows on the device. excl: the host exclusion CSR over all n queries,
+        or None; capped: ops.score_topk_candidates_capped with the quota bound. Per chunk:
+          round 1  the first K1 = min(1024, overfetch * k) ids of every ranking (ops.score_topk_excluded: the sweeps), then those rows, -1
+                   padding included, as candidate rows of ops.score_topk_candidates_capped. A prefix of the ranking gives a prefix of the
+                   greedy walk, so a capped list that came back FULL is final; and a fetched row that was NOT full held every survivor,
+                   so its capped list is final too. Such queries are settled. Finding the others costs one host read.
+          round 2  the unsettled queries alone: the capped op with the whole catalogue as each query's candidate row, with the train rows,
+                   the exclusion rows and the filter; at most ROUND2_PAIRS (query, item) pairs per call. Its lists replace round 1's.
+        The lists therefore do not depend on overfetch or on the chunk. self.last_quota counts the queries and those sent to round 2."""
+        dev = self.E_i.device
+        top = ops.CONST["LLMREC_TOPK_WIDE_MAX"]
+        if k < 1 or k > top:
+            raise ValueError("k = %d: under quotas 1 <= k <= %d" % (k, top))
+        if isinstance(overfetch, bool) or not isinstance(overfetch, (int, np.integer)) or overfetch < 1:
+            raise ValueError("overfetch: an integer >= 1 expected, got %r" % (overfetch,))
+        K1 = min(top, int(overfetch) * k)
+        self.last_quota = {"queries": n, "round2": 0}
+        every = torch.arange(self.n_items, dtype=torch.int32, device=dev)
+        per_call = max(1, ROUND2_PAIRS // self.n_items)
+
+        def chunk(Eu, qu, train, e, a):
+            fetched, _ = ops.score_topk_excluded(Eu, self.E_i, qu, train, K1, e, filt)
+            rows = torch.arange(qu.numel() + 1, dtype=torch.int32, device=dev) * K1, fetched.reshape(-1)
+            idx, sc = capped(Eu, qu, None, rows, None, None)
+            unsettled = ((idx[:, k - 1] < 0) & (fetched[:, K1 - 1] >= 0)).nonzero().reshape(-1)
+            todo = unsettled.cpu().numpy()                         # (the one host read)
+            self.last_quota["round2"] += int(todo.size)
+            for s in range(0, todo.size, per_call):
+                u = unsettled[s:s + per_call]
+                m = u.numel()
+                whole = torch.arange(m + 1, dtype=torch.int32, device=dev) * self.n_items, every.repeat(m)
+                idx[u], sc[u] = capped(Eu, qu[u], train, whole, self._on_device(excl, csr_rows, a + todo[s:s + per_call]), filt)
+            return idx, sc
+        return chunk
+
     def recommend(self, users, k: int, allow_items=None, deny_items=None, exclude_seen: bool = True, chunk: Optional[int] = 65536,
                   exclude=None, group_of=None, per_group=None, overfetch: int = 2):
         """(items int64 [n, k], scores float32 [n, k]) for the listed users (any order, repeats allowed): the k best eligible items,
@@ -305,103 +419,8 @@ class Recommender:
         its cap: the greedy walk down the user's ranking that takes an item while its group has room - exactly, over the whole catalogue,
         in two rounds (_recommend_capped). overfetch: round 1 looks at the first min(1024, overfetch * k) items of each ranking; the lists
         do not depend on it, only the number of users who need round 2 (self.last_quota = {"queries": n, "round2": r} after the call)."""
-        dev = self.E_u.device
-        q = _ids(users, "users", self.n_users, dev)
-        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
-        train = self.train if exclude_seen else None
-        n = q.numel()
-        step = n if not chunk or chunk >= n else int(chunk)
-        excl = exclusion_csr(exclude, q.cpu().numpy(), self.n_items) if exclude is not None else None
-        quota = group_quota(group_of, per_group, self.n_items)
-        if quota is not None:
-            return self._recommend_capped(n, int(k), step, excl, filt, quota, overfetch, lambda a, b: (self.E_u, q[a:b], train))
-
-        def rows(a):
-            if excl is None:
-                return None
-            rp, ci = csr_slice(excl, a, min(a + step, n))
-            return torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
-
-        parts = [ops.score_topk_excluded(self.E_u, self.E_i, q[a:a + step], train, int(k), rows(a), filt) for a in range(0, n, max(step, 1))]
-        if not parts:
-            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
-        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
-        return idx.to(torch.int64), sc
-
-    def _quota_on_device(self, quota):
-        """(item_group int32 [n_items], cap: int or int32 [n_groups], n_groups) of group_quota, the arrays on the device."""
-        group, cap, n_groups = quota
-        dev = self.E_i.device
-        return torch.from_numpy(group).to(dev), cap if isinstance(cap, int) else torch.from_numpy(cap).to(dev), n_groups
-
-    def _recommend_capped(self, n: int, k: int, step: int, excl, filt, quota, overfetch, side):
-        """recommend / recommend_new under quotas, exact over the whole catalogue. side(a, b) = (Eu, query list, train CSR or None) of queries
-        [a, b); excl: the host exclusion CSR over all n queries, or None. Per chunk:
-          round 1  the first K1 = min(1024, overfetch * k) ids of every ranking (ops.score_topk_excluded: the sweeps), then those rows, -1
-                   padding included, as candidate rows of ops.score_topk_candidates_capped. A prefix of the ranking gives a prefix of the
-                   greedy walk, so a capped list that came back FULL is final; and a fetched row that was NOT full held every survivor,
-                   so its capped list is final too. Such queries are settled. Finding the others costs one host read.
-          round 2  the unsettled queries alone: the capped op with the whole catalogue as each query's candidate row, with the train rows,
-                   the exclusion rows and the filter; at most ROUND2_PAIRS (query, item) pairs per call. Its lists replace round 1's.
-        The lists therefore do not depend on overfetch or on the chunk. self.last_quota counts the queries and those sent to round 2."""
-        dev = self.E_i.device
-        top = ops.CONST["LLMREC_TOPK_WIDE_MAX"]
-        if k < 1 or k > top:
-            raise ValueError("k = %d: under quotas 1 <= k <= %d" % (k, top))
-        if isinstance(overfetch, bool) or not isinstance(overfetch, (int, np.integer)) or overfetch < 1:
-            raise ValueError("overfetch: an integer >= 1 expected, got %r" % (overfetch,))
-        group, cap, n_groups = self._quota_on_device(quota)
-        K1 = min(top, int(overfetch) * k)
-        self.last_quota = {"queries": n, "round2": 0}
-        every = torch.arange(self.n_items, dtype=torch.int32, device=dev)
-        per_call = max(1, ROUND2_PAIRS // self.n_items)
-        on_dev = lambda csr: (torch.from_numpy(csr[0]).to(dev), torch.from_numpy(np.ascontiguousarray(csr[1])).to(dev))
-        parts = []
-        for a in range(0, n, max(step, 1)):
-            b = min(a + step, n)
-            Eu, qu, train = side(a, b)
-            fetched, _ = ops.score_topk_excluded(Eu, self.E_i, qu, train, K1, on_dev(csr_slice(excl, a, b)) if excl is not None else None, filt)
-            rows = torch.arange(b - a + 1, dtype=torch.int32, device=dev) * K1, fetched.reshape(-1)
-            idx, sc = ops.score_topk_candidates_capped(Eu, self.E_i, qu, None, k, rows, group, cap, n_groups=n_groups)
-            unsettled = ((idx[:, k - 1] < 0) & (fetched[:, K1 - 1] >= 0)).nonzero().reshape(-1)
-            todo = unsettled.cpu().numpy()                         # (the one host read)
-            self.last_quota["round2"] += int(todo.size)
-            for s in range(0, todo.size, per_call):
-                u = unsettled[s:s + per_call]
-                m = u.numel()
-                whole = torch.arange(m + 1, dtype=torch.int32, device=dev) * self.n_items, every.repeat(m)
-                gone = on_dev(csr_rows(excl, a + todo[s:s + per_call])) if excl is not None else None
-                idx[u], sc[u] = ops.score_topk_candidates_capped(Eu, self.E_i, qu[u], train, k, whole, group, cap, gone, filt, n_groups=n_groups)
-            parts.append((idx, sc))
-        if not parts:
-            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
-        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
-        return idx.to(torch.int64), sc
-
-    def _ranker(self, k: int, quota):
-        """ops.score_topk_candidates, or with quotas its capped form, as f(Eu, query list, train, candidates, exclude, filt)."""
-        if quota is None:
-            return lambda Eu, qu, train, c, e, f: ops.score_topk_candidates(Eu, self.E_i, qu, train, k, c, e, f)
-        group, cap, n_groups = self._quota_on_device(quota)
-        return lambda Eu, qu, train, c, e, f: ops.score_topk_candidates_capped(Eu, self.E_i, qu, train, k, c, group, cap, e, f, n_groups=n_groups)
-
-    def _rank_chunks(self, n: int, k: int, chunk, cand, excl, filt, call):
-        """What rank and rank_new share: the chunks of n queries, the candidate and exclusion CSRs sliced per chunk and sent to the device;
-        call(a, b, candidates, exclude, filt) ranks queries [a, b)."""
-        dev = self.E_i.device
-        step = n if not chunk or chunk >= n else int(chunk)
-
-        def rows(csr, a, b):
-            if csr is None:
-                return None
-            rp, ci = csr_slice(csr, a, b)
-            return torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
-
-        parts = [call(a, min(a + step, n), rows(cand, a, min(a + step, n)), rows(excl, a, min(a + step, n)), filt) for a in range(0, n, max(step, 1))]
-        if not parts:
-            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
-        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
-        return idx.to(torch.int64), sc
+        return self._serve(self._graph_side(users, exclude_seen), k, allow_items, deny_items, exclude, chunk, _CATALOGUE, group_of, per_group,
+                           overfetch)
 
     def rank(self, users, candidates, k: int, allow_items=None, deny_items=None, exclude_seen: bool = True, exclude=None,
              chunk: Optional[int] = 65536, group_of=None, per_group=None):
@@ -413,69 +432,7 @@ class Recommender:
         chunk: as for recommend (an ineligible, seen or excluded candidate is left out). Any k >= 1.
         group_of / per_group: quotas, as for recommend - the greedy walk down the ranking of the user's own list
         (ops.score_topk_candidates_capped; then k <= 1024)."""
-        dev = self.E_u.device
-        q = _ids(users, "users", self.n_users, dev)
-        host_users = q.cpu().numpy()
-        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
-        train = self.train if exclude_seen else None
-        if candidates is None:
-            raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
-        cand = exclusion_csr(candidates, host_users, self.n_items, what="candidates")
-        excl = exclusion_csr(exclude, host_users, self.n_items) if exclude is not None else None
-        ranker = self._ranker(int(k), group_quota(group_of, per_group, self.n_items))
-        return self._rank_chunks(q.numel(), int(k), chunk, cand, excl, filt, lambda a, b, c, e, f: ranker(self.E_u, q[a:b], train, c, e, f))
-
-    def rank_new(self, histories, candidates, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None,
-                 id_rows=None, chunk: Optional[int] = 65536, group_of=None, per_group=None):
-        """rank() for users who are not rows of the graph, as recommend_new is to recommend: n item histories, one candidate list per new
-        user (a dict is keyed by position here), the scores the bits of ops.scores(embed_new(histories, id_rows), E_i, arange(n)).
-        exclude_history: leave out the history's own items. group_of / per_group: quotas, as for rank. Needs fold_in=True at
-        construction."""
-        self._tables()
-        dev = self.E_i.device
-        ranker = self._ranker(int(k), group_quota(group_of, per_group, self.n_items))
-        ids = self._id_rows(id_rows)
-        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
-        n = hist[0].size - 1
-        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
-        if candidates is None:
-            raise ValueError("candidates: a dict, a (rowptr, colidx) tuple, an [n, m] array or a sequence of n id sequences expected")
-        cand = exclusion_csr(candidates, np.arange(n), self.n_items, what="candidates")
-        excl = exclusion_csr(exclude, np.arange(n), self.n_items) if exclude is not None else None
-        if exclude_history:
-            excl = csr_join(hist, excl)
-        return self._rank_chunks(n, int(k), chunk, cand, excl, filt,
-                                 lambda a, b, c, e, f: ranker(self._embed(hist, ids, a, b), torch.arange(b - a, device=dev), None, c, e, f))
-
-    def _tables(self) -> ops.FoldInTables:
-        if self.fold_in is None:
-            raise RuntimeError("Recommender: built without fold_in=True - Recommender.from_trainer / from_checkpoint(..., fold_in=True) "
-                               "build the item-side tables that new users are embedded from")
-        return self.fold_in
-
-    def _id_rows(self, id_rows) -> Optional[torch.Tensor]:
-        if id_rows is None:
-            return None
-        t = torch.as_tensor(id_rows).to(device=self.E_i.device, dtype=torch.float32)
-        if t.dim() != 2 or t.shape[1] != self.E_i.shape[1]:
-            raise ValueError("id_rows: [n, %d] expected, got %s" % (self.E_i.shape[1], tuple(t.shape)))
-        return t.contiguous()
-
-    def _embed(self, hist: Tuple[np.ndarray, np.ndarray], id_rows: Optional[torch.Tensor], a: int, b: int) -> torch.Tensor:
-        dev = self.E_i.device
-        rp, ci = csr_slice(hist, a, b)
-        return ops.fold_in_users(self._tables(), torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev),
-                                 id_rows=id_rows[a:b] if id_rows is not None else None)
-
-    def embed_new(self, histories, id_rows=None) -> torch.Tensor:
-        """E_new float32 [n, d]: the embeddings of n users who are not rows of the graph, from their item histories - what the trained
-        model's forward gives a user with that row of the adjacency, the item side held fixed (ops.fold_in_users). histories: any form
-        history_csr accepts (a history is a SET: order and repeats do not matter). id_rows [n, d]: the users' own id rows - a new
-        user has none: zeros (None)."""
-        self._tables()
-        ids = self._id_rows(id_rows)
-        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
-        return self._embed(hist, ids, 0, hist[0].size - 1)
+        return self._serve(self._graph_side(users, exclude_seen), k, allow_items, deny_items, exclude, chunk, candidates, group_of, per_group)
 
     def recommend_new(self, histories, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None, id_rows=None,
                       chunk: Optional[int] = 65536, group_of=None, per_group=None, overfetch: int = 2):
@@ -484,30 +441,43 @@ class Recommender:
         ops.scores(embed_new(histories, id_rows), E_i, arange(n)). exclude_history: leave out the history's own items; exclude: one more
         list per new user, in any form exclusion_csr accepts (a dict is keyed by position here). allow_items / deny_items / chunk: as
         for recommend, as are group_of / per_group / overfetch (quotas, exact in two rounds). Needs fold_in=True at construction."""
+        return self._serve(self._new_side(histories, id_rows, exclude_history), k, allow_items, deny_items, exclude, chunk, _CATALOGUE, group_of,
+                           per_group, overfetch)
+
+    def rank_new(self, histories, candidates, k: int, allow_items=None, deny_items=None, exclude_history: bool = True, exclude=None,
+                 id_rows=None, chunk: Optional[int] = 65536, group_of=None, per_group=None):
+        """rank() for users who are not rows of the graph, as recommend_new is to recommend: n item histories, one candidate list per new
+        user (a dict is keyed by position here), the scores the bits of ops.scores(embed_new(histories, id_rows), E_i, arange(n)).
+        exclude_history: leave out the history's own items. group_of / per_group: quotas, as for rank. Needs fold_in=True at
+        construction."""
+        return self._serve(self._new_side(histories, id_rows, exclude_history), k, allow_items, deny_items, exclude, chunk, candidates, group_of,
+                           per_group)
+
+    def _tables(self) -> ops.FoldInTables:
+        if self.fold_in is None:
+            raise RuntimeError("Recommender: built without fold_in=True - Recommender.from_trainer / from_checkpoint(..., fold_in=True) "
+                               "build the item-side tables that new users are embedded from")
+        return self.fold_in
+
+    def _histories(self, histories, id_rows) -> Tuple[Tuple[np.ndarray, np.ndarray], Optional[torch.Tensor]]:
+        """(history_csr of `histories`, `id_rows` as float32 [n, d] on the device or None); without fold-in tables the RuntimeError of
+        _tables comes before anything else."""
         self._tables()
-        dev = self.E_i.device
-        ids = self._id_rows(id_rows)
-        hist = history_csr(histories, self.n_items, None if ids is None else ids.shape[0])
-        n = hist[0].size - 1
-        filt = self.item_filter(allow_flags(self.n_items, allow_items, deny_items, dev))
-        excl = exclusion_csr(exclude, np.arange(n), self.n_items) if exclude is not None else None
-        if exclude_history:
-            excl = csr_join(hist, excl)
-        step = n if not chunk or chunk >= n else int(chunk)
-        quota = group_quota(group_of, per_group, self.n_items)
-        if quota is not None:
-            return self._recommend_capped(n, int(k), step, excl, filt, quota, overfetch,
-                                          lambda a, b: (self._embed(hist, ids, a, b), torch.arange(b - a, device=dev), None))
-        parts = []
-        for a in range(0, n, max(step, 1)):
-            b = min(a + step, n)
-            E_new = self._embed(hist, ids, a, b)
-            rows = None
-            if excl is not None:
-                rp, ci = csr_slice(excl, a, b)
-                rows = torch.from_numpy(rp).to(dev), torch.from_numpy(np.ascontiguousarray(ci)).to(dev)
-            parts.append(ops.score_topk_excluded(E_new, self.E_i, torch.arange(b - a, device=dev), None, int(k), rows, filt))
-        if not parts:
-            return torch.empty(0, k, dtype=torch.int64, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
-        idx, sc = (parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts)))
-        return idx.to(torch.int64), sc
+        ids = id_rows
+        if ids is not None:
+            ids = torch.as_tensor(ids).to(device=self.E_i.device, dtype=torch.float32)
+            if ids.dim() != 2 or ids.shape[1] != self.E_i.shape[1]:
+                raise ValueError("id_rows: [n, %d] expected, got %s" % (self.E_i.shape[1], tuple(ids.shape)))
+            ids = ids.contiguous()
+        return history_csr(histories, self.n_items, None if ids is None else ids.shape[0]), ids
+
+    def _embed(self, hist: Tuple[np.ndarray, np.ndarray], id_rows: Optional[torch.Tensor], a: int, b: int) -> torch.Tensor:
+        return ops.fold_in_users(self._tables(), *self._on_device(hist, csr_slice, a, b), id_rows=id_rows[a:b] if id_rows is not None else None)
+
+    def embed_new(self, histories, id_rows=None) -> torch.Tensor:
+        """E_new float32 [n, d]: the embeddings of n users who are not rows of the graph, from their item histories - what the trained
+        model's forward gives a user with that row of the adjacency, the item side held fixed (ops.fold_in_users). histories: any form
+        history_csr accepts (a history is a SET: order and repeats do not matter). id_rows [n, d]: the users' own id rows - a new
+        user has none: zeros (None)."""
+        hist, ids = self._histories(histories, id_rows)
+        return self._embed(hist, ids, 0, hist[0].size - 1)
